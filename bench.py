@@ -6,7 +6,12 @@ metric    cells*steps/s of the whole sim_step() path (one step = one 0.1 s frame
 
 output    ONE compact JSON line on stdout (rank 0; < 8 KB: compact_line, tests/test_bench_line.py - round 3's 25.7 KB line came back unparsed from the driver):
           the contract's keys, `roofline`, `pcg_iteration`, `kernels`, `cpu_baseline`, the `converged` block and one-number summaries of the secondary blocks.
-          The whole object goes to bench_full.json beside it (and under gpurun_out/).  Inputs are resident in HBM when a timed region starts.
+          The whole object goes to bench_full.json beside it.  Inputs are resident in HBM when a timed region starts.
+
+plain     `bench.py --gpus 1 --steps K --warmup W` does what the headline needs and no more: set up, pre-roll, W warm-up frames, K timed frames (the dominant
+          kernel class sampled by HIP events inside them, as always: `roofline`), the line.  Everything else below - the PMC passes, the per-kernel pass behind the
+          timed region (`kernels`, `stages`, `pcg_iteration`), the copy ceiling, `converged`, the secondary and strong blocks, `cpu_baseline`, the exchange latency of
+          an N > 1 job and bench_full.json - runs with --full only.  --dump-outputs DIR writes what the last timed frame computed (bench_blocks/outputs.py).
 
 headline  N=1: configs[2], the 8192x8192 half-filled tank, "pressure-solve roofline run" (SURVEY 8d config 3): tol = 0 and
           max_iterations = 100, so every substep runs exactly 100 PCG iterations; the timed frames lie in the tank's saturated
@@ -25,7 +30,7 @@ beside it `converged` - the same workload with EVERY solve run to the reference'
           reference's own IC(0), bit-identical iterates); `summary.quality_100_iterations` - what the reference's budget is worth in every mode against the converged
           solution; `summary.configs1_1024_dam_break` - BASELINE configs[1]: parity mode checked in-run against the oracle, the resident solver (one persistent launch
           per solve), its float variant ("fp32") and the multi-kernel form; `summary.projection_16384` with its own PMC pass; `summary.time_to_solution_2048_ms`;
-          `summary.strong_16384_dam_break` - configs[3] on this many GPUs (N = 1: the strong-scaling denominator).  `--quality` adds the long studies (equal-residual
+          `summary.strong_16384_dam_break` - configs[3] on this many GPUs (N = 1: the strong-scaling denominator).  `--full --quality` adds the long studies (equal-residual
           budget scans, one frame per BASELINE workload against the reference's IC(0) on the oracle) to bench_full.json.
 """
 import argparse
@@ -48,6 +53,7 @@ from bench_blocks.workload import load_workload, preroll_into_solves, balanced_p
 from bench_blocks.timing import kernel_rows, time_frames, summarize  # noqa: E402,F401
 from bench_blocks.studies import equal_residual_scan, equal_residual, PARITY_CASES, parity_vs_reference, quality_summary, converged_block, converged_deviation, strong_block  # noqa: E402,F401
 from bench_blocks.line import LINE_LIMIT, _pick, _r, _short, ROOF_KEYS, ITER_KEYS, _block, compact_line, write_full  # noqa: E402,F401
+from bench_blocks.outputs import dump_outputs  # noqa: E402
 
 
 set_as_stored(False)
@@ -100,11 +106,18 @@ def parse_args():
     ap.add_argument("--no-secondary", action="store_true", help="headline case only (no parity-mode / 1024^2 / 16384^2 / time-to-solution blocks)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes (roofline.traffic is then null)")
     ap.add_argument("--no-16384", action="store_true", help="skip the 16384^2 projection block")
-    ap.add_argument("--quality", action="store_true", help="also run the long quality studies (equal-residual budget scans, one frame per BASELINE workload against the "
+    ap.add_argument("--quality", action="store_true", help="with --full: also run the long quality studies (equal-residual budget scans, one frame per BASELINE workload against the "
                                                            "reference's IC(0) on the oracle); their results go to bench_full.json")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong_16384_dam_break block (BASELINE configs[3]; N = 1: its denominator)")
     ap.add_argument("--strong-size", type=int, default=16384, help="N of the strong block's N x N dam break (tests use a small one)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # this process runs under rocprofv3 --pmc
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: live PMC passes, per-kernel timing behind the timed region, the copy ceiling, the parity / quality / "
+                         "converged / 1024^2 / 16384^2 / time-to-solution blocks, the strong-scaling block, the CPU baseline, the exchange latency (N > 1) and "
+                         "bench_full.json.  Without it a run sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write what the last one computed (u, v, pressure, fluid counts, markers, counters) as DIR/<name>.npy, "
+                         "float32 / float64; arrays above 2^20 elements as a fixed seeded sample (bench_blocks/outputs.py)")
     return ap.parse_args()
 
 
@@ -139,7 +152,7 @@ def main():
     traffic_exact = traffic_exact_note = None
     traffic_mg = traffic_mg_note = None
     t_start, t_pmc = time.perf_counter(), 0.0
-    if single and not args.no_pmc and not args.pmc_child:
+    if single and args.full and not args.no_pmc and not args.pmc_child:
         t0 = time.perf_counter()
         traffic, traffic_note = pmc_live(child_common + ["--precond", args.precond])
         if not args.no_secondary and args.precond != "ic0":
@@ -203,7 +216,12 @@ def main():
         sim.copy_bandwidth(1 << 30, 2)     # the calibration launches of pmc_live(): a known 2^30 bytes read and written each
 
     big = GX * GY >= 4096 * 4096
-    t = time_frames(sim, ea, grp, args, args.precond, args.steps, 0, args.warmup, big)
+    dumped = {}
+    dump = None
+    if args.dump_outputs and rank == 0:      # (row slabs: rank 0's rows)
+        def dump(s):
+            dumped.update(dump_outputs(s, ea, args.dump_outputs))
+    t = time_frames(sim, ea, grp, args, args.precond, args.steps, 0, args.warmup, big, after_timed=dump)
     if comm is not None and comm.error:
         raise RuntimeError(comm.error)
     cells = GX * GY
@@ -226,9 +244,10 @@ def main():
         if os.environ.get("EULER_SHARE_GPU"):      # (euler_amd/dist.py: more local ranks than devices, or a test that asked for it)
             comm_info["ranks_share_devices"] = True
         try:
-            comm_info["exchange_us"] = {"g1_edge_rows_and_pair": round(sim.exchange_latency(100, GX, 2), 2), "g2_scalar": round(sim.exchange_latency(100, 0, 1), 2)}
-            l = sum(comm_info["exchange_us"].values())
-            comm_info["exchange_us"]["per_iteration"] = round(l, 2)
+            if args.full:      # (runs of their own over the communicator)
+                comm_info["exchange_us"] = {"g1_edge_rows_and_pair": round(sim.exchange_latency(100, GX, 2), 2), "g2_scalar": round(sim.exchange_latency(100, 0, 1), 2)}
+                l = sum(comm_info["exchange_us"].values())
+                comm_info["exchange_us"]["per_iteration"] = round(l, 2)
         except Exception as e:
             comm_info["exchange_us"] = {"error": repr(e)}
         if args.precond == "ic0_tile_mg":      # the multilevel cycle on row slabs: split by rows (a third exchange point) or replicated - and by which rule
@@ -258,15 +277,18 @@ def main():
             rank_cells, share = GX * GY // world, 1.0 / world
         head = summarize(t, GX, GY, args.precond, tile_w, traffic, traffic_note, args.steps, fused_search=True, rank_cells=rank_cells,
                          rank_fluid_share=share)
-        try:      # the ceiling a plain device-to-device copy reaches on this very GPU (read + write), next to the 8 TB/s spec peak
-            copy_gbps = round(sim.copy_bandwidth(1 << 30, 10), 1)
-        except Exception:
-            copy_gbps = None
-        if head["roofline"]:
+        if not args.full and isinstance(head["pcg_iteration"], dict) and head["pcg_iteration"].get("complete") is False:
+            head["pcg_iteration"] = None      # (only the dominant class is timed without --full: the iteration's other launches are timed behind the region)
+        if args.full:
+            try:      # the ceiling a plain device-to-device copy reaches on this very GPU (read + write), next to the 8 TB/s spec peak
+                copy_gbps = round(sim.copy_bandwidth(1 << 30, 10), 1)
+            except Exception:
+                copy_gbps = None
+        if head["roofline"] and args.full:
             head["roofline"]["measured_copy_GBps"] = copy_gbps
         device = sim.device_name()
     secondary = {}
-    extras = single and not args.no_secondary and not args.pmc_child
+    extras = single and args.full and not args.no_secondary and not args.pmc_child
     big_head = GX * GY >= 4096 * 4096
     if extras and args.precond == "ic0_tile":
         # the SAME handle goes on (no second preroll): the parity mode on the same frames, what 100 iterations are worth per mode, then the converged frames
@@ -299,7 +321,7 @@ def main():
     del sim
     # BASELINE configs[3], the strong-scaling unit: N > 1 (the driver's scaling run) measures it beside the weak line, N = 1 its denominator
     strong = None
-    want_strong = not args.no_strong and not args.pmc_child and not args.force_slab and args.scaling == "weak" and N < args.strong_size and \
+    want_strong = args.full and not args.no_strong and not args.pmc_child and not args.force_slab and args.scaling == "weak" and N < args.strong_size and \
         ((rows and world > 1) or (single and not args.no_secondary))
     if want_strong:
         try:
@@ -428,7 +450,7 @@ def main():
             except Exception as e:
                 secondary["projection_16384"] = {"error": repr(e)}
             lap("projection_16384")
-    if extras or (world > 1 and not args.no_cpu_baseline):
+    if extras or (world > 1 and args.full and not args.no_cpu_baseline):
         if not single:
             libs = build_native_oracle()
         # (8) the CPU path beside it (rank 0): single thread, bounded sample
@@ -515,7 +537,11 @@ def main():
         "device": device,
         "timings_s": timings,
     }
-    full["full"] = write_full(full)
+    if dumped:
+        full["outputs"] = dumped
+        print("bench: the last timed frame's outputs in %s: %s" % (args.dump_outputs, ", ".join(sorted(dumped))), file=sys.stderr)
+    if args.full:
+        full["full"] = write_full(full)
     emit(json.dumps(compact_line(full)))
     os.dup2(2, 1)
     grp.close()

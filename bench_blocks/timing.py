@@ -41,12 +41,13 @@ def kernel_rows(prof, precond, cells_fluid, traffic, iters):
 PROFILE_STRIDE = 7      # large grids: every 7th launch of the dominant class carries its event pair in the timed region (coprime with the p-update's period of 8 iterations)
 
 
-def time_frames(sim, ea, grp, args, precond, steps, warmup_done, warmup, big):
+def time_frames(sim, ea, grp, args, precond, steps, warmup_done, warmup, big, after_timed=None):
     """the timed region + per-kernel HIP-event timing.  An event pair serialises the stream for a few microseconds: with every launch of every class bracketed the 8192^2
     headline ran 3.9 % slower than without (399.8 against 384.4 ms per frame).  So INSIDE the timed region only the dominant class is bracketed - on large grids every
     PROFILE_STRIDE-th launch of it (EULER_OPT_PROFILE_STRIDE: ~2300 samples over the default 20 frames, every phase of the iteration's 8-cycle alike; the resident solver's
     one launch per solve: every one) - and the other classes are timed in a second pass BEHIND it (large grids: two frames, every launch; their totals are scaled to the
-    timed region's substeps, so averages stand and per-substep sums compare; small grids: as many frames as the timed region)."""
+    timed region's substeps, so averages stand and per-substep sums compare; small grids: as many frames as the timed region).  That second pass is a run of its
+    own: it is made under --full (or --profile-all) only.  after_timed(sim), if given, is called right after the timed region, before anything else steps the handle."""
     for _ in range(max(warmup - warmup_done, 0)):
         sim.step()
     dominant = {"ic0": "backward_solve", "ic0_tile": "apply_a", "ic0_tile2": "apply_a", "ic0_tile_mg": "apply_a", "jacobi": "update_pr"}[precond]
@@ -62,6 +63,8 @@ def time_frames(sim, ea, grp, args, precond, steps, warmup_done, warmup, big):
     st0 = sim.stats()
     elapsed = grp.timed(sim.step, steps)
     st1 = sim.stats()
+    if after_timed is not None:
+        after_timed(sim)
     prof = sim.profile() if timed else {}
     sim.profile_enable([])
     sim.set_option(ea.OPT_PROFILE_STRIDE, 1)
@@ -71,7 +74,7 @@ def time_frames(sim, ea, grp, args, precond, steps, warmup_done, warmup, big):
     iters = st1.total_pcg_iterations - st0.total_pcg_iterations
     substeps = st1.total_substeps - st0.total_substeps
     iters2 = iters
-    if not args.no_kernel_timing:
+    if not args.no_kernel_timing and (args.full or args.profile_all):
         steps2 = min(steps, 2) if big else steps
         sim.profile_reset()
         sim.profile_enable([k for k in classes_all if k != dominant])

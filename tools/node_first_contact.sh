@@ -20,10 +20,10 @@ if [ "$N" -ge 2 ]; then
   for G in $N 1; do
     PORT=$((PORT + 1))
     if [ "$G" -gt 1 ]; then
-      timeout 1800 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$G" --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus "$G" --steps 10 --warmup 3 \
+      timeout 1800 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$G" --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus "$G" --steps 10 --warmup 3 \
         > "$OUT/bench_gpus$G.json" 2> "$OUT/bench_gpus$G.log"
     else
-      timeout 1800 python3 bench.py --gpus 1 --steps 10 --warmup 3 --no-pmc > "$OUT/bench_gpus$G.json" 2> "$OUT/bench_gpus$G.log"
+      timeout 1800 python3 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-pmc > "$OUT/bench_gpus$G.json" 2> "$OUT/bench_gpus$G.log"
     fi
     cp bench_full.json "$OUT/bench_full_gpus$G.json" 2>/dev/null
     python3 - "$OUT/bench_gpus$G.json" <<'P'

@@ -16,7 +16,7 @@ ARGS="bench.py --size $SIZE --workload $WORKLOAD --precond $PRECOND --steps $STE
 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- python3 $ARGS > "$OUT/bench_trace.json" 2> "$OUT/trace.log"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o fetch -- python3 $ARGS > /dev/null 2> "$OUT/fetch.log"
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o write -- python3 $ARGS > /dev/null 2> "$OUT/write.log"
-python3 bench.py --size $SIZE --workload $WORKLOAD --precond $PRECOND --steps $STEPS --warmup 1 --no-secondary --no-pmc $EXTRA > "$OUT/bench_events.json" 2>> "$OUT/trace.log"
+python3 bench.py --full --size $SIZE --workload $WORKLOAD --precond $PRECOND --steps $STEPS --warmup 1 --no-secondary --no-pmc $EXTRA > "$OUT/bench_events.json" 2>> "$OUT/trace.log"
 python3 tools/summarize_profile.py "$OUT" > "$OUT/summary.md" 2>> "$OUT/trace.log"
 # keep only small artefacts for the merge back
 find "$OUT" -type f -size +4M -delete
