@@ -49,7 +49,8 @@ struct PcgScalars {
   int done;      // inf_norm(r) <= tol reached (main.c:756)
   int iters;     // apply_a calls so far (main.c:750)
   int max_iters;
-  unsigned int n_chunks, pad_;   // active 16-record chunks of this solve (euler_sim.chunk_list)
+  unsigned int n_chunks;        // active 16-record chunks of this solve (euler_sim.chunk_list)
+  unsigned int zfix;            // S->z holds only the halo of the solve's last z (k_pcg.hip TileArgs::zform): the pass at the end of the solve forms it whole
   // peer-to-peer mailboxes (comm_p2p.hip), set once by euler_p2p_connect and never reset: the mapped mailboxes of all
   // ranks, this rank, and the DEVICE-side exchange counters (only exchanges that really run count, so that the tags of
   // all ranks stay in step although launches after convergence return at once)
@@ -243,6 +244,9 @@ struct euler_sim {
   uint8_t* chunk_part;    // this solve: some cell of the chunk is not CM_INTERIOR (the listed entry of an interior chunk carries EU_CHUNK_INTERIOR)
   size_t hbm_bytes;       // device memory this handle allocated: at creation, plus the search directions' ring when the first multi-kernel solve needs it (euler_hbm_bytes)
   int lean_ok;            // the solver arrays have only been written by solves since chunk_prev was current (else k_build_system writes them whole)
+  double* zhalo;          // tile-local mode on one GPU (k_pcg.hip tile_z_recompute): [band][T / 16][2][64] - records 0 and 15 of every tile's z; allocated by the first solve that needs them
+  double* zrows;          // [band][2][X]: lane 0's / lane 63's z by column (with zhalo)
+  int z_halo_last;        // the solve's last k_precond_tile left z as its halo only: the next k_search_apply forms z again (ZR)
   double* tile_table;     // [8][64][2]: E^-1 of an interior tile of 16 records (k_tile_table) - the same for every interior tile, so k_precond_tile never streams it
   unsigned long long* chunk_bits;
   unsigned int* chunk_list;

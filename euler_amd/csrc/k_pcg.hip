@@ -349,6 +349,47 @@ __device__ __forceinline__ double ld_system(const double* p) {
 // INTERIOR chunks (EU_CHUNK_INTERIOR in the list entry: every cell fluid, four fluid neighbours, a_diag 4 - most of a deep tank)
 // take a second instantiation of the run body with the masks as compile-time constants: no mask loads, no selects.
 #define SA_THREADS 256
+// z = M^-1 r of ONE tile of W records (tile-local IC(0), main.c:602-626 restricted to the tile): L q = r, then L^T z = q from the tile's last
+// record down.  mm: the cells' masks by pair-record, rr: r, pp: E^-1, zz: q on the way, z at the end.  k_precond_tile (DOT: dot(z, r) over the
+// fluid cells, accumulated into dsum in the order of the backward recurrence) and k_search_apply<.., ZR> (forming z again from r) share it:
+// the same expressions under -ffp-contract=off, so both get the same bits.  Every lane of the wave takes part (DPP shifts).
+template <int W, bool DOT>
+__device__ __forceinline__ void tile_solve(const unsigned int* mm, const sw_d2* rr, const sw_d2* pp, sw_d2* zz, double& dsum) {
+  // L q = r (main.c:602-613).  What travels from cell to cell is m = (-1 * precon) * q, the term both consumers subtract.
+  double own = -0.0, out = -0.0;
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
+    const double cin = (j & 1) ? rr[j >> 1].y : rr[j >> 1].x, cpre = (j & 1) ? pp[j >> 1].y : pp[j >> 1].x;
+    const double nbv = wave_shift_inject<DPP_WAVE_SHR1>(out, -0.0);
+    const double t = cin - own - nbv;
+    const double qv = t * cpre;
+    const double res = (cm & CM_FLUID) ? qv : 0.0;
+    const double carry = -1.0 * cpre * res;
+    own = carry; out = carry;
+    if (j & 1) zz[j >> 1].y = res; else zz[j >> 1].x = res;
+  }
+  // L^T z = q (main.c:615-626), from the tile's last record down
+  own = 0.0; out = 0.0;
+#pragma unroll
+  for (int j = W - 1; j >= 0; --j) {
+    const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
+    const double cin = (j & 1) ? zz[j >> 1].y : zz[j >> 1].x, cpre = (j & 1) ? pp[j >> 1].y : pp[j >> 1].x;
+    const double nbv = wave_shift_inject<DPP_WAVE_SHL1>(out, 0.0);
+    const double kr = ((cm & CM_RIGHT) ? -1.0 : 0.0) * cpre, ku = ((cm & CM_UP) ? -1.0 : 0.0) * cpre;
+    const double t = cin - kr * own - ku * nbv;
+    const double zv = t * cpre;
+    const double res = (cm & CM_FLUID) ? zv : 0.0;
+    own = res; out = res;
+    if (DOT && (cm & CM_FLUID)) dsum += res * ((j & 1) ? rr[j >> 1].y : rr[j >> 1].x);
+    if (j & 1) zz[j >> 1].y = res; else zz[j >> 1].x = res;
+  }
+}
+// ZR (k_search_apply<.., ZR>, k_pcg.hip tile_z_recompute): z is not read from memory but formed again from r; what the run's window and its edge lanes
+// need of the NEIGHBOURING tiles' z, k_precond_tile left behind in its "z halo only" form (TileArgs::zform 1):
+//   halo  [band][tile][2][64]: record 0 / record 15 of every tile, all lanes (the records next to the neighbouring tiles)
+//   rows  [band][2][X]: lane 0's / lane 63's z by column (what the bands below / above read across the band boundary)
+struct ZrArgs { const double* r; const double* pre; const double* table; const double* halo; const double* rows; int X; };
 struct SaPair { sw_d2 z, so; double ez0, es0, ez1, es1; };   // one pair-record of a lane + the out-of-band vertical neighbours of its two elements
 
 // SA_RUN pair-records per wave: 8 (more waves in flight - at 1024^2 runs of 32 would leave 300 waves for 256 CUs - and the granularity
@@ -373,7 +414,9 @@ struct SaHist { const double* s[6]; };   // PMODE N: the arrays of s_(k-N+1) .. 
 // STORE false: A s' is not stored (`out` is ignored) - k_precond_tile<16, true> forms it again from s' instead of reading it back
 // COARSE 2 (multilevel preconditioner, k_mg.hip): z + P_0 x_0 with P_0 bilinear from the level-0 nodes - the lane combines its two node rows once per run (four node columns
 // cover the run and its window), every cell then interpolates along its row; the expression is mg_interp0's, so a cell gets the same bits whoever forms its s'.
-template <int SLAB, int PMODE, int SA_RUN, int COARSE = 0, bool STORE = true>   // SLAB 1: several ranks, the neighbouring slabs' arrays are mapped; 2: their edge rows as compact rows (nbr); 0: nbr is ignored
+// ZR (SLAB 0, SA_RUN 8, the list of active chunks; k_pcg.hip tile_z_recompute): z is formed again from r by the run's own tile solve (tile_solve, E^-1 from the
+// LDS table for interior chunks as in k_precond_tile) - the previous k_precond_tile stored only what the neighbouring tiles' z contributes (ZrArgs)
+template <int SLAB, int PMODE, int SA_RUN, int COARSE = 0, bool STORE = true, bool ZR = false>   // SLAB 1: several ranks, the neighbouring slabs' arrays are mapped; 2: their edge rows as compact rows (nbr); 0: nbr is ignored
 // (multilevel mode, one GPU, seven of eight passes: four waves per SIMD - 128 registers, one of them spilled - since the lanes' level-0 node values live in LDS: 212 -> 197 us at 8192^2;
 // forced onto the 150 registers of the select-chain form the same bound cost 100 bytes of scratch and 288 us)
 // (the tile-local mode's pass has 98 registers, four waves; squeezed to 96 for five - 12 bytes of scratch - it takes 180 us instead of 169)
@@ -384,10 +427,16 @@ __global__ __launch_bounds__(SA_THREADS, (COARSE == 2 && PMODE == 1 && SLAB == 0
                                                              unsigned int* counter, int fin_op, SlabNeighbours nbr,
                                                              double* __restrict__ p, double* s_new_base, double* s_old_base,
                                                              const unsigned int* __restrict__ chunk_list,      // SA_RUN == 8 only: the solve's active runs
-                                                             CoarseRef cref, SaHist hist) {
+                                                             CoarseRef cref, SaHist hist, ZrArgs zr) {
+  static_assert(!ZR || (SLAB == 0 && SA_RUN == 8 && COARSE == 0), "ZR: one GPU, runs of one tile, no coarse part");
   __shared__ double s_cy[COARSE == 2 ? SA_THREADS / 64 : 1][COARSE == 2 ? MG_NI + 1 : 1][64];      // multilevel mode: a lane's node values of the run (own row / the row across the band boundary)
   __shared__ double s_ce[COARSE == 2 ? SA_THREADS / 64 : 1][COARSE == 2 ? MG_NI + 1 : 1][64];
   if (!force && pcg_idle(sc)) return;
+  __shared__ sw_d2 s_ztab[ZR ? 8 : 1][64];      // ZR: E^-1 of an interior tile (k_tile_table), as k_precond_tile keeps it
+  if (ZR) {
+    for (int k = threadIdx.x; k < 8 * 64; k += SA_THREADS) (&s_ztab[0][0])[k] = reinterpret_cast<const sw_d2*>(zr.table)[k];
+    __syncthreads();
+  }
   const double beta = sc->beta;
   (void)s_new_base; (void)s_old_base;
   // PMODE N: alpha of the iterations k - N .. k - 1 (k = the iterations counted so far: this launch's own alpha is written by its LAST block)
@@ -415,7 +464,7 @@ __global__ __launch_bounds__(SA_THREADS, (COARSE == 2 && PMODE == 1 && SLAB == 0
     int c = i, per = cpb;
     bool interior = false;
     if (listed) { const unsigned int ent = chunk_list[i]; interior = (ent & EU_CHUNK_INTERIOR) != 0; c = (int)(ent & ~EU_CHUNK_INTERIOR); per = ntb16; }
-    const int lb = c / per, P0 = (c % per) * SA_RUN, P1 = P0 + SA_RUN < npairs ? P0 + SA_RUN : npairs;
+    const int lb = c / per, P0 = (c % per) * SA_RUN, P1 = ZR ? P0 + SA_RUN : (P0 + SA_RUN < npairs ? P0 + SA_RUN : npairs);      // (ZR: a listed tile ends below T < TS)
     const size_t bbase = (size_t)lb * TS * 64 + 2 * lane;     // element (band, record 0, lane)
     auto run = [&](auto full_tag) {
       constexpr bool FULL = decltype(full_tag)::value;
@@ -429,6 +478,19 @@ __global__ __launch_bounds__(SA_THREADS, (COARSE == 2 && PMODE == 1 && SLAB == 0
         any |= mm[j];
       }
       if (!FULL && !listed && !__ballot(((any | (any >> 8)) & CM_FLUID) != 0)) return;
+      // ZR: z of the run's tile from r, the same bits as the k_precond_tile that updated r
+      sw_d2 zz[ZR ? SA_RUN : 1];
+      if (ZR) {
+        sw_d2 rr[SA_RUN], pp[SA_RUN];
+#pragma unroll
+        for (int j = 0; j < SA_RUN; ++j) {
+          rr[j] = *reinterpret_cast<const sw_d2*>(zr.r + bbase + (size_t)(P0 + j) * 128);
+          pp[j] = FULL ? s_ztab[j][lane] : *reinterpret_cast<const sw_d2*>(zr.pre + bbase + (size_t)(P0 + j) * 128);
+        }
+        double none = 0.0;
+        tile_solve<2 * SA_RUN, false>(mm, rr, pp, zz, none);
+      }
+      const int ztile = P0 / SA_RUN;      // ZR: the run's tile within its band
       // where lane 0 / lane 63 find the row below / above their band (the adjacent band's lane 63 / lane 0), relative to pair 0:
       // even element (record 2P):  below = record 2P + 63 of band - 1, above = record 2P - 63 of band + 1; odd element: + 1
       const bool up_remote = SLAB == 1 && nbr.z_up && lb + 1 == nb_local, dn_remote = SLAB == 1 && nbr.z_dn && lb == 0;
@@ -445,6 +507,8 @@ __global__ __launch_bounds__(SA_THREADS, (COARSE == 2 && PMODE == 1 && SLAB == 0
       const double* gs = lane == 0 ? nbr.srow_dn : nbr.srow_up;
       double* gsn = lane == 0 ? nbr.snew_dn : nbr.snew_up;
       const int gcol = lane == 0 ? 0 : -63;
+      // ZR: the rows across the band boundary are lane 63's of the band below / lane 0's of the band above, by column (ZrArgs::rows)
+      const double* zrow = ZR ? zr.rows + (long long)(lane == 0 ? 2 * lb - 1 : 2 * lb + 2) * zr.X : nullptr;
       // COARSE: this lane's columns in the run (pairs P0 - 1 .. P1: 20 records at most) start in aggregate column Ja, reach Ja + 1 at record
       // tb1 and Ja + 2 at record tb2 (aggregates of 16: three columns; of 64 and more: two); the lane's row decides the aggregate row
       double cy0 = 0.0, cy1 = 0.0, cy2 = 0.0, ce0 = 0.0, ce1 = 0.0, ce2 = 0.0;
@@ -507,17 +571,26 @@ __global__ __launch_bounds__(SA_THREADS, (COARSE == 2 && PMODE == 1 && SLAB == 0
       auto load_pair = [&](int P, SaPair& d, unsigned int m) __attribute__((always_inline)) {
         d.ez0 = d.es0 = d.ez1 = d.es1 = 0.0;
         if (P < 0 || P >= npairs) { d.z = sw_d2{0.0, 0.0}; d.so = sw_d2{0.0, 0.0}; return; }   // outside the band: never a fluid cell's neighbour
-        d.z = *reinterpret_cast<const sw_d2*>(z + bbase + (size_t)P * 128);
+        if (ZR) {      // (P - P0 is a constant once the run's loop is unrolled) the window's pairs of the neighbouring tiles: record 15 of the one before, record 0 of the one after
+          const int j = P - P0;
+          if (j >= 0 && j < SA_RUN) d.z = zz[j >= 0 && j < SA_RUN ? j : 0];
+          else if (j < 0) d.z = sw_d2{0.0, zr.halo[((size_t)lb * ntb16 + ztile - 1) * 128 + 64 + lane]};
+          else d.z = sw_d2{ztile + 1 < ntb16 ? zr.halo[((size_t)lb * ntb16 + ztile + 1) * 128 + lane] : 0.0, 0.0};
+        } else {
+          d.z = *reinterpret_cast<const sw_d2*>(z + bbase + (size_t)P * 128);
+        }
         d.so = *reinterpret_cast<const sw_d2*>(s_old + bbase + (size_t)P * 128);
         if (edge_lane) {
           if ((m & CM_FLUID) && (m & vbit)) {
             const long long k = e0_base + (long long)P * 128;
-            if (SLAB == 2 && ghost) { d.ez0 = gz[2 * P + gcol]; d.es0 = gs[2 * P + gcol]; }
+            if (ZR) { d.ez0 = zrow[2 * P + gcol]; d.es0 = s_old[k]; }
+            else if (SLAB == 2 && ghost) { d.ez0 = gz[2 * P + gcol]; d.es0 = gs[2 * P + gcol]; }
             else if (SLAB == 1 && remote) { d.ez0 = ld_system(ez + k); d.es0 = ld_system(es + k); } else { d.ez0 = ez[k]; d.es0 = es[k]; }
           }
           if (((m >> 8) & CM_FLUID) && ((m >> 8) & vbit)) {
             const long long k = e1_base + (long long)P * 128;
-            if (SLAB == 2 && ghost) { d.ez1 = gz[2 * P + 1 + gcol]; d.es1 = gs[2 * P + 1 + gcol]; }
+            if (ZR) { d.ez1 = zrow[2 * P + 1 + gcol]; d.es1 = s_old[k]; }
+            else if (SLAB == 2 && ghost) { d.ez1 = gz[2 * P + 1 + gcol]; d.es1 = gs[2 * P + 1 + gcol]; }
             else if (SLAB == 1 && remote) { d.ez1 = ld_system(ez + k); d.es1 = ld_system(es + k); } else { d.ez1 = ez[k]; d.es1 = es[k]; }
           }
           if (COARSE == 1) {      // (harmless where nothing was loaded: the value is then never selected)
@@ -1333,6 +1406,11 @@ struct TileArgs {
   // RECOMP (k_precond_tile<16, true>): `as` is the search direction s' itself and the pass forms A s' from it.  On row slabs the rows across
   // the slab boundary are the compact ghost rows of s' that k_search_apply SLAB 2 keeps (indexed by the column); null = no neighbouring slab
   const double *gs_lo, *gs_hi;
+  // W == 16, one GPU (k_pcg.hip tile_z_recompute): how z leaves the pass and what it tells the solve's flag PcgScalars::zfix.  -1: stored whole, the flag is left alone;
+  // 0: stored whole, flag cleared; 1: "z halo only" - only what the next k_search_apply<.., ZR> cannot form itself goes to zhalo / zrows (ZrArgs), flag set;
+  // 2: the end of a solve: runs only where the flag is set (z is then M^-1 of the r in memory: nothing has touched r since) and stores z whole, flag cleared
+  int zform;
+  double *zhalo, *zrows;
 };
 
 // fixed-shape reductions of a PT_THREADS block; result valid in thread 0
@@ -1439,7 +1517,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_factor_tile(TileArgs a) {
 // tile-local mode's own instantiation keeps its registers (151: three waves per SIMD)
 template <int W, bool RECOMP = false, int CMODE = 0>
 __global__ __launch_bounds__(PT_THREADS, RECOMP ? PT_RECOMP_BLOCKS : 1) void k_precond_tile(TileArgs a) {
-  if (!a.force && pcg_idle(a.sc)) return;
+  if (!a.force && (a.zform == 2 ? a.sc->zfix == 0 : pcg_idle(a.sc))) return;
   const int lane = threadIdx.x & 63;
   const int ntb = a.g.T / W, total = a.nb_local * ntb;
   const int n_waves = gridDim.x * (PT_THREADS / 64);
@@ -1631,38 +1709,24 @@ __global__ __launch_bounds__(PT_THREADS, RECOMP ? PT_RECOMP_BLOCKS : 1) void k_p
 #pragma unroll
         for (int P = 0; P < W / 2; ++P) pp[P] = FULL ? s_tab[P < TABP ? P : 0][lane] : *reinterpret_cast<const sw_d2*>(a.pre + base + P * 128);
       }
-      // L q = r (main.c:602-613).  What travels from cell to cell is m = (-1 * precon) * q, the term both consumers subtract.
-      double own = -0.0, out = -0.0;
+      // z = M_tile^-1 r (L q = r, L^T z = q: main.c:602-626) with dot(z, r) on the fly
+      tile_solve<W, true>(mm, rr, pp, qq, dsum);
+      if (W == 16 && a.zform == 1) {      // (wave-uniform) "z halo only": what the next k_search_apply<.., ZR> cannot form itself (ZrArgs)
+        double* h = a.zhalo + ((size_t)band * ntb + k) * 128;
+        h[lane] = qq[0].x;
+        h[64 + lane] = qq[W / 2 - 1].y;
+        if (lane == 0 || lane == 63) {
+          double* row = a.zrows + ((size_t)band * 2 + (lane == 63 ? 1 : 0)) * a.g.X;
 #pragma unroll
-      for (int j = 0; j < W; ++j) {
-        const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
-        const double cin = (j & 1) ? rr[j >> 1].y : rr[j >> 1].x, cpre = (j & 1) ? pp[j >> 1].y : pp[j >> 1].x;
-        const double nbv = wave_shift_inject<DPP_WAVE_SHR1>(out, -0.0);
-        const double t = cin - own - nbv;
-        const double qv = t * cpre;
-        const double res = (cm & CM_FLUID) ? qv : 0.0;
-        const double carry = -1.0 * cpre * res;
-        own = carry; out = carry;
-        if (j & 1) qq[j >> 1].y = res; else qq[j >> 1].x = res;
+          for (int j = 0; j < W; ++j) {
+            const int x = k * W + j - lane;      // the lane's column in record k W + j
+            if (x >= 0 && x < a.g.X) row[x] = (j & 1) ? qq[j >> 1].y : qq[j >> 1].x;
+          }
+        }
+      } else {
+#pragma unroll
+        for (int P = 0; P < W / 2; ++P) *reinterpret_cast<sw_d2*>(a.z + base + P * 128) = qq[P];
       }
-      // L^T z = q (main.c:615-626), from the tile's last record down; dot(z, r) on the fly
-      own = 0.0; out = 0.0;
-#pragma unroll
-      for (int j = W - 1; j >= 0; --j) {
-        const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
-        const double cin = (j & 1) ? qq[j >> 1].y : qq[j >> 1].x, cpre = (j & 1) ? pp[j >> 1].y : pp[j >> 1].x;
-        const double crr = (j & 1) ? rr[j >> 1].y : rr[j >> 1].x;
-        const double nbv = wave_shift_inject<DPP_WAVE_SHL1>(out, 0.0);
-        const double kr = ((cm & CM_RIGHT) ? -1.0 : 0.0) * cpre, ku = ((cm & CM_UP) ? -1.0 : 0.0) * cpre;
-        const double t = cin - kr * own - ku * nbv;
-        const double zv = t * cpre;
-        const double res = (cm & CM_FLUID) ? zv : 0.0;
-        own = res; out = res;
-        if (cm & CM_FLUID) dsum += res * crr;
-        if (j & 1) qq[j >> 1].y = res; else qq[j >> 1].x = res;
-      }
-#pragma unroll
-      for (int P = 0; P < W / 2; ++P) *reinterpret_cast<sw_d2*>(a.z + base + P * 128) = qq[P];
       if (band == a.edge_lo || band == a.edge_hi) {      // (wave-uniform) the rows the neighbouring slabs need, as compact rows
         const bool lo = band == a.edge_lo && lane == 0, hi = band == a.edge_hi && lane == 63;
 #pragma unroll
@@ -1705,6 +1769,7 @@ __global__ __launch_bounds__(PT_THREADS, RECOMP ? PT_RECOMP_BLOCKS : 1) void k_p
       if (a.rupd) pcg_scalar_step(a.sc, FIN_RNORM, vmax);
       if (a.fin_dot >= 0 && !(a.rupd && a.sc->done)) pcg_scalar_step(a.sc, a.fin_dot, vsum);
     }
+    if (a.zform >= 0) a.sc->zfix = a.zform == 1 ? 1u : 0u;
     __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -2015,6 +2080,27 @@ static inline bool tile_recompute(const euler_sim* S) {
   if (S->has_comm) return ghost_mode(S);
   return S->cfg.dot_mode != EULER_DOT_SEQUENTIAL;
 }
+// z is not stored either (round 7): the r update's k_precond_tile leaves only z's halo (TileArgs::zform 1) and the next k_search_apply<.., ZR> forms z again from r
+// with the same tile solve.  8 bytes per fluid cell and iteration less: 8192^2 (docs/solver_tile_local.md).  One GPU, the plain tile-local mode, tree dots, runs of one tile;
+// EULER_OPT_TILE_STORE_Z restores the stored form.  z stays observable: every solve ends with z stored whole (tile_z_begin / eu_launch_project)
+static inline bool tile_z_recompute(const euler_sim* S) {
+  return tile_recompute(S) && tile_fused(S) && !eu_is_two_level(S) && S->tile_w == 16 && !S->has_comm && !S->slab_on && S->band_lo == 0 &&
+         S->opt[EULER_OPT_TILE_STORE_Z] == 0 && S->chunk_list && S->tile_table;
+}
+// the halo buffers (ZrArgs), allocated by the first solve that runs the form; false: no room - the solve keeps the stored form (the same bits)
+static bool tile_z_begin(euler_sim* S) {
+  S->z_halo_last = 0;
+  if (!tile_z_recompute(S)) return false;
+  if (!S->zhalo) {
+    const size_t nh = (size_t)S->geom.nbands * (S->geom.T / 16) * 128, nr = (size_t)S->geom.nbands * 2 * S->X;
+    if (hipMalloc(&S->zhalo, nh * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); S->zhalo = nullptr; return false; }
+    if (hipMalloc(&S->zrows, nr * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(S->zhalo); S->zhalo = S->zrows = nullptr; return false; }
+    S->hbm_bytes += (nh + nr) * sizeof(double);
+    HIPCHK(hipMemsetAsync(S->zhalo, 0, nh * sizeof(double), S->stream));
+    HIPCHK(hipMemsetAsync(S->zrows, 0, nr * sizeof(double), S->stream));
+  }
+  return true;
+}
 // max |r| and dot(z,r) of all ranks after ONE exchange ("fuse the latter two into one ... message pair"): every rank
 // folds the gathered pairs in rank order - identical bits everywhere - and applies the two scalar epilogues
 __global__ void k_pair_fold(PcgScalars* sc, const double* __restrict__ pairs, int stride, int R, int rupd, int fin_dot, int force) {
@@ -2040,6 +2126,7 @@ static TileArgs make_tile_args(euler_sim* S, int force) {
   a.reverse = S->opt[EULER_OPT_TILE_REVERSE] != 0;
   a.cpart = nullptr; a.cshift = 0; a.cmode = 0; a.cnx = a.cny = 0;
   a.gs_lo = a.gs_hi = nullptr;
+  a.zform = -1; a.zhalo = S->zhalo; a.zrows = S->zrows;
   if (ghost_mode(S)) {
     if (S->band_lo > 0) { a.zsend_lo = xrow(S, XR_ZSEND_LO); a.edge_lo = S->band_lo; }
     if (S->band_hi < S->geom.nbands) { a.zsend_hi = xrow(S, XR_ZSEND_HI); a.edge_hi = S->band_hi - 1; }
@@ -2062,10 +2149,11 @@ static int launch_factor_tile(euler_sim* S, int force) {
 // [r -= alpha A s, max |r|,] z = M^-1 r, dot(z, r) with its scalar epilogue fin_dot (FIN_SIGMA_INIT / FIN_BETA / FIN_STORE_ONLY)
 // r_only: the kernel's first half alone - r -= alpha A s and max |r| with its epilogue (`done`) - over 16-record chunks whatever the
 // handle's tile width: how EVERY non-tile configuration (the reference's IC(0), Jacobi) updates r since round 3 (p rides in k_search_apply)
-static int launch_precond_tile(euler_sim* S, int rupd, int sweeps, int fin_dot, int force, double alpha, bool r_only = false) {
+static int launch_precond_tile(euler_sim* S, int rupd, int sweeps, int fin_dot, int force, double alpha, bool r_only = false, int zform = -1) {
   const bool seq = S->cfg.dot_mode == EULER_DOT_SEQUENTIAL && !S->has_comm;
   TileArgs a = make_tile_args(S, force);
   a.rupd = rupd; a.sweeps = sweeps; a.fin_dot = (seq || !sweeps) ? -1 : fin_dot; a.alpha_arg = alpha;
+  a.zform = zform;
   // two-level mode: the tile pass also leaves P^T r per tile and only STORES its share of dot(z, r); k_coarse_solve adds the coarse
   // share and applies the epilogue
   const bool two_level = eu_is_two_level(S) && sweeps && !r_only && !force && a.list != nullptr;
@@ -2091,7 +2179,7 @@ static int launch_precond_tile(euler_sim* S, int rupd, int sweeps, int fin_dot, 
       if (a.zsend_hi) a.zsend_hi = eu_mg_split_msg(S, 1);
     }
   }
-  const int w = r_only ? 16 : S->tile_w, cls = r_only ? KC_UPDATE_PR : KC_PRECOND_TILE;
+  const int w = r_only ? 16 : S->tile_w, cls = r_only ? KC_UPDATE_PR : zform == 2 ? KC_MISC : KC_PRECOND_TILE;      // (the pass at the end of a solve is not an iteration's)
   const unsigned nblk = eu_blocks((size_t)(S->band_hi - S->band_lo) * (S->geom.T / w), PT_THREADS / 64, 2048);
   // (r_only: the other modes' r update - A s' would sit in q behind k_search_apply, in z behind the solve's first k_apply_a, which stores it)
   const bool recomp = rupd && !force && tile_recompute(S) && (r_only ? S->tile_as_override == S->q : !S->tile_as_override);
@@ -2287,13 +2375,17 @@ static int launch_search_apply_and_alpha(euler_sim* S, int it) {
   const bool store = !tile_recompute(S);      // false: A s' is not stored (k_precond_tile<16, true> forms it again)
   const bool mg = eu_is_mg(S);
   const CoarseRef cref = {mg ? S->mg_x : S->cc_y, mg ? 0 : S->coarse_shift, mg ? S->mg_nx[0] : S->coarse_nx, mg ? S->mg_ny[0] : S->coarse_ny, S->band_lo};
-#define SA_LAUNCH_CS(SLABF, PM, RUNV, CF, ST)                                                                                                \
-  LAUNCH(S, KC_APPLY_A, (k_search_apply<SLABF, PM, RUNV, CF, ST>), dim3(sa_blocks(S, RUNV)), dim3(SA_THREADS), LOC(S->s), LOC(S->z), LOC(S->s2), \
-         LOC(S->q), LOC(S->cellmask), gl, S->partial, S->sc, 0, S->red_counter, fin, nbr, pp, S->s2, S->s, (RUNV) == 8 ? S->chunk_list : (const unsigned int*)nullptr, cref, hist)
+  const ZrArgs zr = {S->r, S->precon, S->tile_table, S->zhalo, S->zrows, S->X};
+#define SA_LAUNCH_CSZ(SLABF, PM, RUNV, CF, ST, ZRF)                                                                                                \
+  LAUNCH(S, KC_APPLY_A, (k_search_apply<SLABF, PM, RUNV, CF, ST, ZRF>), dim3(sa_blocks(S, RUNV)), dim3(SA_THREADS), LOC(S->s), LOC(S->z), LOC(S->s2), \
+         LOC(S->q), LOC(S->cellmask), gl, S->partial, S->sc, 0, S->red_counter, fin, nbr, pp, S->s2, S->s, (RUNV) == 8 ? S->chunk_list : (const unsigned int*)nullptr, cref, hist, zr)
+#define SA_LAUNCH_CS(SLABF, PM, RUNV, CF, ST) SA_LAUNCH_CSZ(SLABF, PM, RUNV, CF, ST, false)
 #define SA_LAUNCH_C(SLABF, PM, RUNV, CF) do { if ((RUNV) == 8 && !store) SA_LAUNCH_CS(SLABF, PM, RUNV, CF, ((RUNV) != 8)); else SA_LAUNCH_CS(SLABF, PM, RUNV, CF, true); } while (0)
 #define SA_LAUNCH(SLABF, PM, RUNV) SA_LAUNCH_C(SLABF, PM, RUNV, 0)
 #define SA_RUNS(SLABF, PM) do { if (run == 8) SA_LAUNCH(SLABF, PM, 8); else if (run == 16) SA_LAUNCH(SLABF, PM, 16); else SA_LAUNCH(SLABF, PM, 32); } while (0)
-  if (eu_is_two_level(S) && tile_fused(S) && ghost) {      // coarse correction on row slabs (multilevel mode): the ghost rows of z get their P y here as well
+  if (S->z_halo_last) {      // z formed again from r (tile_z_recompute): the previous k_precond_tile left its halo only - odd passes only (PMODE 1, below)
+    SA_LAUNCH_CSZ(0, 1, 8, 0, false, true);
+  } else if (eu_is_two_level(S) && tile_fused(S) && ghost) {      // coarse correction on row slabs (multilevel mode): the ghost rows of z get their P y here as well
     if (pmode == 8) SA_LAUNCH_C(2, 8, 8, 2); else if (pmode == 4) SA_LAUNCH_C(2, 4, 8, 2); else if (pmode == 2) SA_LAUNCH_C(2, 2, 8, 2); else SA_LAUNCH_C(2, 1, 8, 2);
   } else if (eu_is_two_level(S) && tile_fused(S)) {      // two-level / multilevel preconditioner on one GPU: runs of 8 (the list), z + P y
     if (mg) { if (pmode == 8) SA_LAUNCH_C(0, 8, 8, 2); else if (pmode == 4) SA_LAUNCH_C(0, 4, 8, 2); else if (pmode == 2) SA_LAUNCH_C(0, 2, 8, 2); else SA_LAUNCH_C(0, 1, 8, 2); }
@@ -2311,6 +2403,7 @@ static int launch_search_apply_and_alpha(euler_sim* S, int it) {
 #undef SA_LAUNCH
 #undef SA_LAUNCH_C
 #undef SA_LAUNCH_CS
+#undef SA_LAUNCH_CSZ
   S->s = S->s_ring[it % steps]; S->s2 = S->s_ring[(it + 1) % steps];      // (two arrays: the swap of rounds 1-4)
   S->s_launched = it + 1;
   if (seq)
@@ -2324,7 +2417,7 @@ int eu_launch_velocity_update(euler_sim* S, float dt, int finish);
 
 __global__ void k_pcg_reset(PcgScalars* sc, double tol, int max_iters) {
   sc->sigma = sc->zs = sc->sigma_new = sc->alpha = sc->alpha_prev = sc->beta = sc->rnorm = 0.0;
-  sc->tol = tol; sc->nonzero = 0; sc->done = 0; sc->iters = 0; sc->max_iters = max_iters;
+  sc->tol = tol; sc->nonzero = 0; sc->done = 0; sc->iters = 0; sc->max_iters = max_iters; sc->zfix = 0;
 }
 
 // project() (main.c:709-806).  With a communicator every launch below covers this rank's bands
@@ -2333,6 +2426,7 @@ __global__ void k_pcg_reset(PcgScalars* sc, double tol, int max_iters) {
 // the all-gather of p before the (replicated) velocity update.
 int eu_launch_project(euler_sim* S, float dt) {
   S->s_launched = 0;      // (EULER_F_PCG_S: no multi-kernel iteration of this solve has run yet)
+  S->z_halo_last = 0;
   S->p_pending = 0;       // (the assembly writes p afresh: whatever the last solve left unfinished in memory is gone with it)
   S->pcg_fields_resident = 0;
   const PcgScalars prev_solve = *S->sc_host;      // (the previous solve's final scalars: a resident launch that has to be redone must not leave its own in their place)
@@ -2411,6 +2505,8 @@ int eu_launch_project(euler_sim* S, float dt) {
   }
   if (two_level && (rc = eu_launch_coarse_setup(S))) return rc;   // P^T A P of this system, its factor and inverse (k_coarse.hip)
   if (two_level && (rc = eu_launch_coarse_consistent(S))) return rc;   // (water cut off from the air: r = b made compatible with the singular A)
+  const bool zr = tile && tile_z_begin(S);      // (the first pass stores z whole: the copy s_0 = z and k_apply_a read it)
+  bool zr_ran = false;
   if (tile) {                                                     // E^-1 per tile, then z = M^-1 r and sigma = dot(z, r) in one pass
     if ((rc = launch_factor_tile(S, 0))) return rc;
     if ((rc = launch_precond_tile(S, 0, 1, FIN_SIGMA_INIT, 0, 0.0))) return rc;
@@ -2468,7 +2564,14 @@ int eu_launch_project(euler_sim* S, float dt) {
         // r -= alpha A s, max |r| (sets `done`), z = M^-1 r, beta = dot(z, r) / sigma: one pass; on the last iteration of the
         // budget only r and its norm (main.c:760-765 would be computed and never consumed)
         S->prof_iter = it;
-        if ((rc = launch_precond_tile(S, 1, it + 1 < max_it, FIN_BETA, 0, 0.0))) return rc;
+        // tile_z_recompute: z's halo only where the next k_search_apply forms z again - a PMODE 1 pass (the ring's flush, PMODE N, keeps the stored form: with the
+        // tile solve on top of its N - 1 extra streams it would hold 204 registers, two waves per SIMD) that is not the last (iteration max_it - 2 stores z whole)
+        const int nx = it + 1, steps = S->s_ring_n;
+        const bool next_odd = !(nx >= steps && nx % steps == 0);
+        const int zform = zr && it + 1 < max_it ? (it + 2 < max_it && next_odd ? 1 : 0) : -1;
+        if ((rc = launch_precond_tile(S, 1, it + 1 < max_it, FIN_BETA, 0, 0.0, false, zform))) return rc;
+        S->z_halo_last = zform == 1;
+        zr_ran = zr_ran || zform == 1;
         continue;
       }
       // r -= alpha A s, max |r| (sets `done`): the first half of the tile pass, over the solve's active chunks (A s sits in q, or in z
@@ -2501,6 +2604,9 @@ int eu_launch_project(euler_sim* S, float dt) {
     }
   }
   S->prof_iter = -2;
+  // z whole again where the solve's last z-forming pass left its halo only (converged before iteration max_it - 2): from r, which nothing has touched since - the same bits
+  S->z_halo_last = 0;
+  if (zr_ran && (rc = launch_precond_tile(S, 0, 1, -1, 0, 0.0, false, 2))) return rc;
   // the last p += alpha s (the others rode along with the apply_a passes): in memory where a communicator needs the finished rows (and in the two-pass form), else inside the
   // velocity update's pass (k_grid.hip k_velocity_update_para)
   const bool finish_in_update = !S->has_comm && !S->slab_on && S->opt[EULER_OPT_VELOCITY_TWO_PASS] == 0;

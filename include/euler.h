@@ -384,6 +384,8 @@ enum {
   EULER_OPT_PROFILE_STRIDE = 20,    /* n >= 1 (default 1): euler_profile_enable brackets every n-th launch of an enabled kernel class with its event pair (a pair costs the stream
                                        a few microseconds of serialisation: all ~230 launches of an 8192^2 substep bracketed cost bench.py's headline 3.9 %); the class's time and
                                        launch count are those of the bracketed launches */
+  EULER_OPT_TILE_STORE_Z = 21,      /* 1: k_precond_tile stores z and k_search_apply reads it (rounds 2-6; the same bits); 0 (default): the tile-local mode on one GPU stores only z's halo
+                                       and k_search_apply forms z again from r; every solve still ends with z stored whole */
   EULER_OPT__COUNT
 };
 int euler_set_option(euler_sim* sim, int32_t key, int64_t value);
