@@ -178,6 +178,9 @@ extern "C" int euler_set_option(euler_sim* S, int32_t key, int64_t value) {
     case EULER_OPT_MG_SPLIT_LEVEL: ok = value >= -1 && value < 12; break;
     case EULER_OPT_PROFILE_STRIDE: ok = value >= 1 && value <= 1024; break;
     case EULER_OPT_MG_SPLIT_ACTIVE: ok = false; break;
+    case EULER_OPT_ADVECT_RK2: ok = value == 0 || value == 1;
+      if (ok && value == 1 && S->slab_on) when = "on a whole-grid handle (row slabs: the midpoint samples reach one row beyond the ghost rows)";
+      break;
     default: ok = value == 0 || value == 1; break;
   }
   if (!ok) { eu_set_error("euler_set_option: key %d does not take the value %lld", (int)key, (long long)value); return EULER_EINVAL; }

@@ -505,6 +505,31 @@ __device__ __forceinline__ float eu_interp(const GridRef& g, const float* __rest
   return eu_lerp(lv, rv, hf);
 }
 
+// EULER_OPT_ADVECT_RK2 (docs/advection_rk2.md): the midpoint rule.  The start-point velocity (d0x, d0y) at index (x, y) of the given index space is carried half a step,
+// hdt = 0.5f * dt, back; the velocity interpolated there replaces it in the unchanged back-trace.  Index spaces (EU_H = 1): a position maps to u index pos - (1, 0.5),
+// v index pos - (0.5, 1), p index pos - (0.5, 0.5).  The two gathers of each helper do not depend on each other: they are issued together.
+template <bool TR = false>
+__device__ __forceinline__ float2 eu_mid_vel_uidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
+  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
+  return make_float2(eu_interp<1, TR>(g, u, mx, my), eu_interp<2, TR>(g, v, mx + 0.5f, my - 0.5f));      // (vidx_from_u)
+}
+template <bool TR = false>
+__device__ __forceinline__ float2 eu_mid_vel_vidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
+  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
+  return make_float2(eu_interp<1, TR>(g, u, mx - 0.5f, my + 0.5f), eu_interp<2, TR>(g, v, mx, my));      // (uidx_from_v)
+}
+template <bool TR = false>
+__device__ __forceinline__ float2 eu_mid_vel_pidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
+  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
+  return make_float2(eu_interp<1, TR>(g, u, mx - 0.5f, my), eu_interp<2, TR>(g, v, mx, my - 0.5f));
+}
+// a marker: velocity_at (main.c:440-449) half a step FORWARD from position (px, py)
+template <bool TR = false>
+__device__ __forceinline__ float2 eu_mid_vel_pos(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float px, float py, float v0x, float v0y, float hdt) {
+  const float mx = px + hdt * v0x, my = py + hdt * v0y;
+  return make_float2(eu_interp<1, TR>(g, u, mx / EU_H - 1.f, my / EU_H - 0.5f), eu_interp<2, TR>(g, v, mx / EU_H - 0.5f, my / EU_H - 1.f));
+}
+
 // xorshift64* (misc/rng.c:5-20) jump-ahead.  The state update x ^= x >> 12; x ^= x << 25; x ^= x >> 27 is linear over GF(2):
 // one step is a 64 x 64 bit matrix M, k steps are M^k.  jump[i][b] = M^(2^i) e_b (the image of bit b), filled once on the
 // host (driver.hip); a state is advanced k steps by applying M^(2^i) for the set bits of k - 64 conditional XORs each.  This

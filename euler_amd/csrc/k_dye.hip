@@ -62,7 +62,9 @@ __global__ __launch_bounds__(256) void k_dye_sources(float* r, float* g, float* 
   b[i] = hsv_basis(t - 2.f);
 }
 
-// advect_p (main.c:424-438) for the three channels; only fluid cells of the outputs are written
+// advect_p (main.c:424-438) for the three channels; only fluid cells of the outputs are written.  RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the
+// velocity at the midpoint of the face average (euler_dev.h eu_mid_vel_pidx)
+template <bool RK2>
 __global__ __launch_bounds__(256) void k_advect_dye(const float* __restrict__ r, const float* __restrict__ g,
                                                     const float* __restrict__ b, float* __restrict__ rout,
                                                     float* __restrict__ gout, float* __restrict__ bout,
@@ -73,8 +75,9 @@ __global__ __launch_bounds__(256) void k_advect_dye(const float* __restrict__ r,
   if (x >= X || y >= y1) return;
   const size_t i = (size_t)y * X + x;
   if (!gr.count[i]) return;                     // never fluid on the border ring (all sink): i - X, i - 1 exist
-  const float dy = (v[i] + v[i - X]) / 2;
-  const float dx = (u[i] + u[i - 1]) / 2;
+  float dy = (v[i] + v[i - X]) / 2;
+  float dx = (u[i] + u[i - 1]) / 2;
+  if (RK2) { const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
   const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
   rout[i] = eu_interp<0>(gr, r, px, py);
   gout[i] = eu_interp<0>(gr, g, px, py);
@@ -107,8 +110,12 @@ int eu_launch_dye_sources(euler_sim* S) {
 int eu_launch_dye_advect(euler_sim* S, float dt) {
   if (!S->dye[0]) return EULER_OK;
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
-  LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
-         S->u, S->v, g, dt, S->row_lo, S->row_hi);
+  if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye<true>, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
+           S->u, S->v, g, dt, S->row_lo, S->row_hi);
+  else
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye<false>, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
+           S->u, S->v, g, dt, S->row_lo, S->row_hi);
   // memcpy(g_r, g_rtmp, sizeof(g_r)) x3 (main.c:875,878,881): the WHOLE scratch array, stale non-fluid entries included (a row slab: its own rows)
   const size_t o = (size_t)S->row_lo * S->X, n = (size_t)(S->row_hi - S->row_lo) * S->X;
   for (int k = 0; k < 3; ++k) HIPCHK(hipMemcpyAsync(S->dye[k] + o, S->dye[3 + k] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));

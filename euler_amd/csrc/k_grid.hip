@@ -249,6 +249,8 @@ int eu_launch_extrapolate(euler_sim* S) {
 // outputs (main.c:888-889), fused: what reaches utmp/vtmp equals the reference's arrays after its
 // second zero_bounds pair (non-fluid or solid faces are 0, so the reference's stale entries and the
 // gravity it adds to non-fluid faces never survive).
+// RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the midpoint velocity (euler_dev.h eu_mid_vel_*); everything else as it stands
+template <bool RK2>
 __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict__ u, const float* __restrict__ v,
                                                          float* __restrict__ uout, float* __restrict__ vout,
                                                          const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
@@ -267,8 +269,9 @@ __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict
     if (x < X - 1) {
       float out = 0.f;
       if (eu_prop_u(g.count, i) && !eu_prop_u(solid, i)) {
-        const float dx = u[i];
-        const float dy = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);          // vidx_from_u, main.c:378-380
+        float dx = u[i];
+        float dy = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);                // vidx_from_u, main.c:378-380
+        if (RK2) { const float2 m = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
         const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;     // main.c:392-393
         out = eu_interp<1>(g, u, px, py);
       }
@@ -277,8 +280,9 @@ __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict
     if (y < Y - 1) {
       float out = 0.f;
       if (eu_prop_v(g.count, i, X) && !eu_prop_v(solid, i, X)) {
-        const float dy = v[i];
-        const float dx = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);          // uidx_from_v, main.c:401-403
+        float dy = v[i];
+        float dx = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);                // uidx_from_v, main.c:401-403
+        if (RK2) { const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
         const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
         out = eu_interp<2>(g, v, px, py);
         out += EU_G * dt;                                                 // main.c:542
@@ -346,8 +350,11 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   int rep = 1;
   if (lean) while (rep < 16 && ((size_t)S->X * S->Y >> 22) >= (size_t)(2 * rep)) rep *= 2;      // (2048^2: 1, 4096^2: 4, 8192^2 and beyond: 16 - at least 16 K workgroups)
   grid.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
-  LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi,
-         lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr, S->tmap_nx, S->tmap_n, rep);
+  const uint8_t* tm = lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr;
+  if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+  else
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
   S->utmp_clean = (S->cfg.viscosity > 0.f) ? 0 : 1;      // (the diffusion extension writes utmp / vtmp behind this)
   // (a row-slab handle exchanges the ghost rows of utmp / vtmp between the two: eu_slab_substep calls eu_launch_diffuse itself)
   return S->slab_on ? EULER_OK : eu_launch_diffuse(S, dt);

@@ -172,14 +172,21 @@ __device__ __forceinline__ float time_to(float p0, float p1, float vel) {   // m
 
 // TR: u, v, g.count and solid are the COLUMN-major copies (k_transpose_for_markers): the marker array walks the grid column by column (main.c:243-266), so a wave's
 // 64 markers sit in ~16 cells of one column - 16-17 cache lines per gather in the row-major fields, one or two in the column-major ones.  The same values: the same bits.
-template <bool TR>
+// RK2 (EULER_OPT_ADVECT_RK2): the walk runs with the velocity at the midpoint p + (dt_mid / 2) v(p) instead of v(p); nothing else changes.  dt_mid is always the
+// SUBSTEP's dt, never the one the chain shortened (dt): theta and delta then do not depend on the chain, and the walk / pass-B replay stays valid as it is.
+// The midpoint's components are bounded by the maxima calculate_timestep uses (a masked bilinear interpolation is a convex combination of live samples, or 0), so it lies
+// <= 0.375 cells from p and the displacement stays <= 0.75 cells: still at most one boundary per axis.  With TR, uT / vT are not refreshed in tiles the last copy left
+// alone (k_transpose_for_markers, lean): such stale samples are never read here either - eu_interp<.., TR> uses a sample only where its corner bit in countT is set, and
+// that bit belongs to the sample's cell, not to the query point, so a midpoint lookup sees exactly the live samples a start-point lookup there would.
+template <bool TR, bool RK2>
 __device__ __forceinline__ AdvectOut advect_one(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v,
-                                                const uint8_t* __restrict__ solid, float px, float py, float dt) {
+                                                const uint8_t* __restrict__ solid, float px, float py, float dt, float dt_mid) {
   AdvectOut o;
   o.events = 0; o.theta = 0.f; o.delta = 0.f;
   // velocity_at (main.c:440-449)
   float vx = eu_interp<1, TR>(g, u, px / EU_H - 1.f, py / EU_H - 0.5f);
   float vy = eu_interp<2, TR>(g, v, px / EU_H - 0.5f, py / EU_H - 1.f);
+  if (RK2) { const float2 m = eu_mid_vel_pos<TR>(g, u, v, px, py, vx, vy, 0.5f * dt_mid); vx = m.x; vy = m.y; }
   auto is_solid = [&](int sy_, int sx_) -> bool { return solid[TR ? (size_t)sx_ * g.Y + sy_ : (size_t)sy_ * g.X + sx_] != 0; };
   int xi = (int)floorf(px / EU_H), yi = (int)floorf(py / EU_H);
   const int xdir = vx > 0 ? 1 : -1;
@@ -225,7 +232,7 @@ __device__ __forceinline__ AdvectOut advect_one(const GridRef& g, const float* _
   return o;
 }
 
-template <bool TR>
+template <bool TR, bool RK2>
 __global__ __launch_bounds__(256) void k_advect_markers_a(const float2* __restrict__ in, float2* __restrict__ out,
                                                           const float* __restrict__ u, const float* __restrict__ v,
                                                           const uint8_t* __restrict__ solid, GridRef g, float dt,
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(256) void k_advect_markers_a(const float2* __restri
   bool ev = false;
   if (i < n) {
     const float2 p = in[i];
-    const AdvectOut o = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
+    const AdvectOut o = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt);
     out[i] = make_float2(o.px, o.py);
     if (o.events) {
       ev = true;
@@ -258,7 +265,7 @@ __device__ __forceinline__ unsigned long long mk_spread32(unsigned long long x) 
   x = (x | (x << 2)) & 0x3333333333333333ull; x = (x | (x << 1)) & 0x5555555555555555ull;
   return x;
 }
-template <bool TR>
+template <bool TR, bool RK2>
 __global__ __launch_bounds__(256) void k_advect_markers_a2(const float2* __restrict__ in, float2* __restrict__ out,
                                                            const float* __restrict__ u, const float* __restrict__ v,
                                                            const uint8_t* __restrict__ solid, GridRef g, float dt,
@@ -269,14 +276,14 @@ __global__ __launch_bounds__(256) void k_advect_markers_a2(const float2* __restr
   bool ev0 = false, ev1 = false;
   if (i + 1 < n) {
     const float4 p = *reinterpret_cast<const float4*>(in + i);
-    const AdvectOut o0 = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
-    const AdvectOut o1 = advect_one<TR>(g, u, v, solid, p.z, p.w, dt);
+    const AdvectOut o0 = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt);
+    const AdvectOut o1 = advect_one<TR, RK2>(g, u, v, solid, p.z, p.w, dt, dt);
     *reinterpret_cast<float4*>(out + i) = make_float4(o0.px, o0.py, o1.px, o1.py);
     if (o0.events) { ev0 = true; ev_theta[i] = o0.theta; ev_delta[i] = o0.delta; if (o0.events > 1) atomicAdd(&ms->multi_events, 1ull); }
     if (o1.events) { ev1 = true; ev_theta[i + 1] = o1.theta; ev_delta[i + 1] = o1.delta; if (o1.events > 1) atomicAdd(&ms->multi_events, 1ull); }
   } else if (i < n) {
     const float2 p = in[i];
-    const AdvectOut o0 = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
+    const AdvectOut o0 = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt);
     out[i] = make_float2(o0.px, o0.py);
     if (o0.events) { ev0 = true; ev_theta[i] = o0.theta; ev_delta[i] = o0.delta; if (o0.events > 1) atomicAdd(&ms->multi_events, 1ull); }
   }
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(256) void k_advect_markers_a2(const float2* __restr
 // refresh_marker_counts (main.c:102-117) bins the positions advect_markers (main.c:464-537) has just written.  As two kernels that is 8 B per marker read a second time and a
 // pass whose time is the memory-side adds of the counters, while the advection pass is bound by its arithmetic and gathers: the two do not compete.  Here the speculative pass
 // bins what it has computed - cell, sink | solid test (the delete ballot), the run-aggregated adds - and pass B, which recomputes the markers behind a firing dt collision,
-// moves the counts of those whose cell changed (k_advect_markers_b<TR, true>).  Integer adds: the counters come out the same whatever the order.
+// moves the counts of those whose cell changed (k_advect_markers_b<TR, true, RK2>).  Integer adds: the counters come out the same whatever the order.
 // A thread holds TWO markers: their cells mostly coincide (markers are seeded four to a cell, consecutively), so the thread's item is (cell, weight 1 or 2) and a run of lanes
 // adds the sum of its weights; the rare thread with two different cells bins the second one in a second, wave-uniform round.
 __device__ __forceinline__ void bin_aggregated_w(unsigned int* count32, bool live, size_t c, unsigned int w) {      // bin_aggregated (euler_dev.h) with a weight of 1 or 2 per lane
@@ -335,7 +342,7 @@ __device__ __forceinline__ size_t mk_cell_touch(float ox, float oy, float px, fl
   if (live && (((nx ^ (int)ox) | (ny ^ (int)oy)) >> 6) != 0) touch[(ny >> 6) * tnx + (nx >> 6)] = 1;      // (16384^2 dam break: + 55 us here, - 170 us in k_narrow_counts)
   return (size_t)nx * H + ny;
 }
-template <bool TR>
+template <bool TR, bool RK2>
 __global__ __launch_bounds__(256) void k_advect_bin_a2(const float2* __restrict__ in, float2* __restrict__ out,
                                                        const float* __restrict__ u, const float* __restrict__ v,
                                                        const uint8_t* __restrict__ solid, GridRef g, float dt,
@@ -348,8 +355,8 @@ __global__ __launch_bounds__(256) void k_advect_bin_a2(const float2* __restrict_
   size_t c0 = 0, c1 = 0;
   if (i + 1 < n) {
     const float4 p = *reinterpret_cast<const float4*>(in + i);
-    const AdvectOut o0 = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
-    const AdvectOut o1 = advect_one<TR>(g, u, v, solid, p.z, p.w, dt);
+    const AdvectOut o0 = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt);
+    const AdvectOut o1 = advect_one<TR, RK2>(g, u, v, solid, p.z, p.w, dt, dt);
     *reinterpret_cast<float4*>(out + i) = make_float4(o0.px, o0.py, o1.px, o1.py);
     if (o0.events) { ev0 = true; ev_theta[i] = o0.theta; ev_delta[i] = o0.delta; if (o0.events > 1) atomicAdd(&ms->multi_events, 1ull); }
     if (o1.events) { ev1 = true; ev_theta[i + 1] = o1.theta; ev_delta[i + 1] = o1.delta; if (o1.events > 1) atomicAdd(&ms->multi_events, 1ull); }
@@ -358,7 +365,7 @@ __global__ __launch_bounds__(256) void k_advect_bin_a2(const float2* __restrict_
     live0 = !del0; live1 = !del1;
   } else if (i < n) {
     const float2 p = in[i];
-    const AdvectOut o0 = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
+    const AdvectOut o0 = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt);
     out[i] = make_float2(o0.px, o0.py);
     if (o0.events) { ev0 = true; ev_theta[i] = o0.theta; ev_delta[i] = o0.delta; if (o0.events > 1) atomicAdd(&ms->multi_events, 1ull); }
     c0 = mk_cell_touch(p.x, p.y, o0.px, o0.py, H, true, touch, tnx);
@@ -404,7 +411,7 @@ __global__ __launch_bounds__(64) void k_marker_walk(const unsigned int* __restri
 
 // FIX (behind k_advect_bin_a2): a recomputed marker whose cell changed takes its count along, and the delete ballot of its word is made current.
 // A workgroup walks the array with a stride (the launch leaves at once when no collision fired: half a million workgroups took 110 us to do so at 8192^2).
-template <bool TR, bool FIX>
+template <bool TR, bool FIX, bool RK2>
 __global__ __launch_bounds__(256) void k_advect_markers_b(const float2* __restrict__ in, float2* __restrict__ out,
                                                           const float* __restrict__ u, const float* __restrict__ v,
                                                           const uint8_t* __restrict__ solid, GridRef g,
@@ -412,7 +419,7 @@ __global__ __launch_bounds__(256) void k_advect_markers_b(const float2* __restri
                                                           const float* __restrict__ act_dt, const MarkerState* ms,
                                                           const unsigned int* __restrict__ keys,      // keys: slab mode, the markers' GLOBAL array indices
                                                           const uint8_t* __restrict__ blockedT, unsigned int* count32, unsigned long long* delmask, int H,
-                                                          uint8_t* touch, int tnx) {
+                                                          uint8_t* touch, int tnx, float dt_sub) {      // dt_sub: the substep's dt (RK2's midpoint)
   const unsigned int M = ms->n_actual;
   if (M == 0) return;
   const unsigned int first = act_idx[0];
@@ -427,7 +434,7 @@ __global__ __launch_bounds__(256) void k_advect_markers_b(const float2* __restri
         while (lo < hi) { const unsigned int mid = (lo + hi) >> 1; if (act_idx[mid] < gi) lo = mid + 1; else hi = mid; }
         const float dt = act_dt[lo - 1];
         const float2 p = in[i];
-        const AdvectOut o = advect_one<TR>(g, u, v, solid, p.x, p.y, dt);
+        const AdvectOut o = advect_one<TR, RK2>(g, u, v, solid, p.x, p.y, dt, dt_sub);
         if (FIX) {
           const float2 was = out[i];      // pass A's result: binned already
           const size_t oc = mk_cell_colmajor(was.x, was.y, H), nc = mk_cell_colmajor(o.px, o.py, H);
@@ -560,7 +567,8 @@ static int eu_count32_clean(euler_sim* S) {
   return EULER_OK;
 }
 
-int eu_launch_advect_markers(euler_sim* S, float dt) {
+template <bool RK2>
+static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
   const unsigned long long n = S->n_markers_host;
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
   const float2* in = S->markers[S->cur];
@@ -575,33 +583,36 @@ int eu_launch_advect_markers(euler_sim* S, float dt) {
       int rc = eu_blocked_current(S);
       if (!rc) rc = eu_count32_clean(S);
       if (rc) return rc;
-      LAUNCH(S, KC_MARKER_ADVECT, k_advect_bin_a2<true>, dim3(eu_blocks((size_t)((n + 1) / 2), 256)), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, dt, n, S->evmask, S->ev_theta, S->ev_delta, S->ms,
+      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_bin_a2<true, RK2>), dim3(eu_blocks((size_t)((n + 1) / 2), 256)), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, dt, n, S->evmask, S->ev_theta, S->ev_delta, S->ms,
              S->blockedT, S->count32, S->delmask, S->Y, S->tmap + 2 * (size_t)S->tmap_n, S->tmap_nx);
     } else
-      LAUNCH(S, KC_MARKER_ADVECT, k_advect_markers_a2<true>, dim3(eu_blocks((size_t)((n + 1) / 2), 256)), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, dt, n, S->evmask, S->ev_theta, S->ev_delta, S->ms);
+      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_a2<true, RK2>), dim3(eu_blocks((size_t)((n + 1) / 2), 256)), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, dt, n, S->evmask, S->ev_theta, S->ev_delta, S->ms);
     int rc = eu_ordered_select(S, S->evmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_events);
     if (rc) return rc;
     LAUNCH(S, KC_MARKER_EVENTS, k_marker_walk, dim3(1), dim3(64), S->sel_idx, S->ev_theta, S->ev_delta, S->act_idx, S->act_dt, S->ms, dt);
     if (fuse) {
-      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, true>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
-             S->blockedT, S->count32, S->delmask, S->Y, S->tmap + 2 * (size_t)S->tmap_n, S->tmap_nx);
+      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, true, RK2>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
+             S->blockedT, S->count32, S->delmask, S->Y, S->tmap + 2 * (size_t)S->tmap_n, S->tmap_nx, dt);
       S->prebin_valid = 1;      // (consumed by the refresh that follows; anything else in between drops it: driver.hip)
     } else
-      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, false>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
-             (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0);
+      LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, false, RK2>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
+             (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, dt);
     S->cur ^= 1;
     return EULER_OK;
   }
-  LAUNCH(S, KC_MARKER_ADVECT, k_advect_markers_a<false>, dim3(nb), dim3(256), in, out, S->u, S->v, S->solid, g, dt, n,
+  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_a<false, RK2>), dim3(nb), dim3(256), in, out, S->u, S->v, S->solid, g, dt, n,
          S->evmask, S->ev_theta, S->ev_delta, S->ms);
   int rc = eu_ordered_select(S, S->evmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_events);
   if (rc) return rc;
   LAUNCH(S, KC_MARKER_EVENTS, k_marker_walk, dim3(1), dim3(64), S->sel_idx, S->ev_theta, S->ev_delta, S->act_idx,
          S->act_dt, S->ms, dt);
-  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false>), dim3(nb_b), dim3(256), in, out, S->u, S->v, S->solid, g, n,
-         S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0);
+  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false, RK2>), dim3(nb_b), dim3(256), in, out, S->u, S->v, S->solid, g, n,
+         S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, dt);
   S->cur ^= 1;
   return EULER_OK;
+}
+int eu_launch_advect_markers(euler_sim* S, float dt) {      // (never RK2 on a row slab: euler_set_option refuses it there)
+  return S->opt[EULER_OPT_ADVECT_RK2] ? eu_launch_advect_markers_t<true>(S, dt) : eu_launch_advect_markers_t<false>(S, dt);
 }
 
 // ==========================================================================================
@@ -761,14 +772,14 @@ int eu_marker_narrow_counts(euler_sim* S) {
 }
 int eu_marker_advect_a(euler_sim* S, float dt, unsigned long long n) {
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
-  LAUNCH(S, KC_MARKER_ADVECT, k_advect_markers_a<false>, dim3(eu_blocks((size_t)n, 256)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, dt, n,
+  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_a<false, false>), dim3(eu_blocks((size_t)n, 256)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, dt, n,
          S->evmask, S->ev_theta, S->ev_delta, S->ms);
   return eu_ordered_select(S, S->evmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_events);
 }
 int eu_marker_advect_b(euler_sim* S, unsigned long long n, const unsigned int* keys) {
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
-  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false>), dim3(eu_blocks((size_t)n, 256, 4096)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, n,
-         S->act_idx, S->act_dt, S->ms, keys, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0);
+  LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false, false>), dim3(eu_blocks((size_t)n, 256, 4096)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, n,
+         S->act_idx, S->act_dt, S->ms, keys, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, 0.f);      // (RK1: dt_sub unread)
   return EULER_OK;
 }
 

@@ -386,6 +386,9 @@ enum {
                                        launch count are those of the bracketed launches */
   EULER_OPT_TILE_STORE_Z = 21,      /* 1: k_precond_tile stores z and k_search_apply reads it (rounds 2-6; the same bits); 0 (default): the tile-local mode on one GPU stores only z's halo
                                        and k_search_apply forms z again from r; every solve still ends with z stored whole */
+  EULER_OPT_ADVECT_RK2 = 22,        /* CHANGES THE BITS.  0 (default): the reference's forward-Euler transport; 1: the midpoint rule (RK2) for the back-traces of u, v and the dye and for
+                                       the marker move (docs/advection_rk2.md).  May change between any two calls; a row-slab handle refuses 1 (EULER_ESTATE: the midpoint
+                                       samples reach one row beyond the slab's ghost rows) */
   EULER_OPT__COUNT
 };
 int euler_set_option(euler_sim* sim, int32_t key, int64_t value);
