@@ -28,7 +28,7 @@
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
-                  "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] <scenario>\n", argv0);
+                  "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -99,7 +99,7 @@ static int gated_step(app_t* a) {
 int main(int argc, char** argv) {
   euler_config cfg;
   euler_config_default(&cfg);
-  int upscale = 0, frames = -1, wx = 98, wy = 38, dump = 0, pace = 1, window_given = 0, advect_rk2 = 0;
+  int upscale = 0, frames = -1, wx = 98, wy = 38, dump = 0, pace = 1, window_given = 0, advect_rk2 = 0, maccormack = 0;
   const char* scenario = NULL;
   const char* resume = NULL;
   const char* checkpoint = NULL;
@@ -135,6 +135,8 @@ int main(int argc, char** argv) {
       else if (!strcmp(v, "rk2")) advect_rk2 = 1;
       else { usage(argv[0]); return 1; }
     }
+    /* include/euler.h EULER_OPT_ADVECT_MACCORMACK: the MacCormack correction with the clamp on top of either trace (docs/advection_maccormack.md); not recorded in a snapshot */
+    else if (!strcmp(argv[i], "--maccormack")) maccormack = 1;
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
@@ -155,6 +157,7 @@ int main(int argc, char** argv) {
   memset(&app, 0, sizeof app);
   app.rainbow = cfg.rainbow;
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
+      euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK) {
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;

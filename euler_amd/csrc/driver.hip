@@ -181,11 +181,28 @@ extern "C" int euler_set_option(euler_sim* S, int32_t key, int64_t value) {
     case EULER_OPT_ADVECT_RK2: ok = value == 0 || value == 1;
       if (ok && value == 1 && S->slab_on) when = "on a whole-grid handle (row slabs: the midpoint samples reach one row beyond the ghost rows)";
       break;
+    case EULER_OPT_ADVECT_MACCORMACK: ok = value == 0 || value == 1;
+      if (ok && value == 1 && S->slab_on) when = "on a whole-grid handle (row slabs: the correction reads the forward result one row beyond the own rows)";
+      break;
     default: ok = value == 0 || value == 1; break;
   }
   if (!ok) { eu_set_error("euler_set_option: key %d does not take the value %lld", (int)key, (long long)value); return EULER_EINVAL; }
   if (when) { eu_set_error("euler_set_option: key %d must be set %s", (int)key, when); return EULER_ESTATE; }
   HIPCHK(hipStreamSynchronize(S->stream));
+  if (key == EULER_OPT_ADVECT_MACCORMACK && value == 1 && !S->mc_u) {      // the forward results of u, v (and the dye's corrected channels): allocated on first use
+    float *a = nullptr, *b = nullptr;
+    const size_t bytes = S->C * sizeof(float);
+    if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess || hipMemset(a, 0, bytes) != hipSuccess ||
+        hipMemset(b, 0, bytes) != hipSuccess) {
+      if (a) (void)hipFree(a);
+      if (b) (void)hipFree(b);
+      (void)hipGetLastError();
+      eu_set_error("euler_set_option: EULER_OPT_ADVECT_MACCORMACK needs %zu bytes of scratch", 2 * bytes);
+      return EULER_ENOMEM;
+    }
+    S->mc_u = a; S->mc_v = b;
+    S->hbm_bytes += 2 * bytes;
+  }
   if (key == EULER_OPT_P_STEPS || key == EULER_OPT_SA_RUN) {      // the ring is about to be forgotten: the pressure the last velocity update left unfinished in memory is finished from it first
     int rcp = eu_pressure_current(S);
     if (rcp) return rcp;
@@ -274,7 +291,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   if (S->sys_div) (void)hipFree(S->sys_div);
   void* dev[] = {S->markers[0], S->markers[1], S->keys[0], S->keys[1], S->ms, S->evmask, S->delmask, S->ev_theta, S->ev_delta, S->sel_idx, S->act_idx,
                  S->act_dt, S->cellmask64, S->draws, S->sel.block_sums, S->sc, S->partial, S->red_counter, S->granules, S->ticket, S->sweep_timeline, S->halo_buf, S->band_ranges, S->partial2, S->pair_buf, S->xrows, S->alpha_buf, S->rng_jump, S->chunk_flag, S->chunk_prev, S->chunk_part, S->tile_table, S->chunk_bits, S->chunk_list, S->zhalo, S->zrows,
-                 S->rowmajor_tmp};
+                 S->rowmajor_tmp, S->mc_u, S->mc_v};
   for (void* p : dev) if (p) (void)hipFree(p);
   for (float* d : S->dye) if (d) (void)hipFree(d + wo);
   // band-skewed arrays: shifted to global element indexing as well (skew_off), behind EU_SKEW_SLACK elements of slack

@@ -161,6 +161,8 @@ struct euler_sim {
   float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when blocked_dirty): whole-grid handles only
   int solidT_dirty;
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
+  float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
+                          // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
   float2* markers[2];
   int cur;
@@ -503,6 +505,54 @@ __device__ __forceinline__ float eu_interp(const GridRef& g, const float* __rest
   const float lv = eu_lerp(q00, q10, lf), rv = eu_lerp(q01, q11, rf);
   const float hf = eu_frac(fx, v00 | v10, v01 | v11);
   return eu_lerp(lv, rv, hf);
+}
+
+// EULER_OPT_ADVECT_MACCORMACK (docs/advection_maccormack.md): eu_interp<TYPE> over row-major q with the count masks - the same value, the same expression forms - that
+// also reports whether any corner is valid and, with LIM, the min (lo) and max (hi) of q over the valid corners, folded in the order 00, 01, 10, 11 with strict compares
+template <int TYPE, bool LIM>
+__device__ __forceinline__ float eu_interp_mc(const GridRef& g, const float* __restrict__ q, float ix, float iy, bool& any, float& lo, float& hi) {
+  ix = eu_clampf(0.f, ix, TYPE == 1 ? g.ux_lim : g.vx_lim);
+  iy = eu_clampf(0.f, iy, TYPE == 2 ? g.vy_lim : g.uy_lim);
+  float wx, wy;
+  const float fx = modff(ix, &wx), fy = modff(iy, &wy);
+  const int bx = (int)wx, by = (int)wy;
+  const size_t sx = 1, sy = (size_t)g.X;
+  const size_t i00 = (size_t)by * sy + (size_t)bx * sx;
+  const float r00 = q[i00], r01 = q[i00 + sx], r10 = q[i00 + sy], r11 = q[i00 + sy + sx];
+  bool v00, v01, v10, v11;
+  if (TYPE == 0) {
+    v00 = g.count[i00] != 0; v01 = g.count[i00 + sx] != 0;
+    v10 = g.count[i00 + sy] != 0; v11 = g.count[i00 + sy + sx] != 0;
+  } else if (TYPE == 1) {
+    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0, c2 = g.count[i00 + 2 * sx] != 0;
+    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0, d2 = g.count[i00 + sy + 2 * sx] != 0;
+    v00 = c0 | c1; v01 = c1 | c2; v10 = d0 | d1; v11 = d1 | d2;
+  } else {
+    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0;
+    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0;
+    const bool e0 = g.count[i00 + 2 * sy] != 0, e1 = g.count[i00 + 2 * sy + sx] != 0;
+    v00 = c0 | d0; v01 = c1 | d1; v10 = d0 | e0; v11 = d1 | e1;
+  }
+  any = v00 | v01 | v10 | v11;
+  if (LIM) {
+    lo = __builtin_inff(); hi = -__builtin_inff();
+    if (v00) { lo = r00 < lo ? r00 : lo; hi = r00 > hi ? r00 : hi; }
+    if (v01) { lo = r01 < lo ? r01 : lo; hi = r01 > hi ? r01 : hi; }
+    if (v10) { lo = r10 < lo ? r10 : lo; hi = r10 > hi ? r10 : hi; }
+    if (v11) { lo = r11 < lo ? r11 : lo; hi = r11 > hi ? r11 : hi; }
+  }
+  const float q00 = v00 ? r00 : 0.f, q01 = v01 ? r01 : 0.f;
+  const float q10 = v10 ? r10 : 0.f, q11 = v11 ? r11 : 0.f;
+  const float lf = eu_frac(fy, v00, v10), rf = eu_frac(fy, v01, v11);
+  const float lv = eu_lerp(q00, q10, lf), rv = eu_lerp(q01, q11, rf);
+  const float hf = eu_frac(fx, v00 | v10, v01 | v11);
+  return eu_lerp(lv, rv, hf);
+}
+// out = f + 0.5 (q0 - b), clamped to [lo, hi]; f alone where the forward or the backward interpolation had no valid corner
+__device__ __forceinline__ float eu_mc_correct(float f, float q0, float b, bool a1, bool a2, float lo, float hi) {
+  if (!(a1 && a2)) return f;
+  const float out = f + 0.5f * (q0 - b);
+  return out < lo ? lo : (out > hi ? hi : out);
 }
 
 // EULER_OPT_ADVECT_RK2 (docs/advection_rk2.md): the midpoint rule.  The start-point velocity (d0x, d0y) at index (x, y) of the given index space is carried half a step,

@@ -84,6 +84,47 @@ __global__ __launch_bounds__(256) void k_advect_dye(const float* __restrict__ r,
   bout[i] = eu_interp<0>(gr, b, px, py);
 }
 
+// EULER_OPT_ADVECT_MACCORMACK, the correction pass of one or two channels (q1 null: one) behind k_advect_dye<RK2> (docs/advection_maccormack.md): per fluid cell the forward
+// trace again (its value and the limiter's lo / hi), the backward trace - the same code with -dt - into the forward result qf, half the round-trip error added, the result
+// clamped.  Every other cell takes qf's value: out is what the whole-array copy moves into g_r / g_g / g_b, as main.c:875-881 moves the scratch array
+template <bool RK2>
+__global__ __launch_bounds__(256) void k_mc_correct_dye(const float* __restrict__ q0, const float* __restrict__ qf0, float* __restrict__ out0,
+                                                        const float* __restrict__ q1, const float* __restrict__ qf1, float* __restrict__ out1,
+                                                        const float* __restrict__ u, const float* __restrict__ v, GridRef gr, float dt, int y0, int y1) {
+  const int X = gr.X;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = y0 + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= X || y >= y1) return;
+  const size_t i = (size_t)y * X + x;
+  if (!gr.count[i]) {
+    out0[i] = qf0[i];
+    if (q1) out1[i] = qf1[i];
+    return;
+  }
+  const float dy0 = (v[i] + v[i - X]) / 2;
+  const float dx0 = (u[i] + u[i - 1]) / 2;
+  const float bdt = -dt;
+  float fdx = dx0, fdy = dy0, bdx = dx0, bdy = dy0;
+  if (RK2) {
+    const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * dt); fdx = m.x; fdy = m.y;
+    const float2 n = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * bdt); bdx = n.x; bdy = n.y;
+  }
+  const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
+  const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
+  bool a1, a2;
+  float lo, hi;
+  {
+    const float f = eu_interp_mc<0, true>(gr, q0, px, py, a1, lo, hi);
+    const float b = eu_interp_mc<0, false>(gr, qf0, qx, qy, a2, lo, hi);
+    out0[i] = eu_mc_correct(f, q0[i], b, a1, a2, lo, hi);
+  }
+  if (q1) {
+    const float f = eu_interp_mc<0, true>(gr, q1, px, py, a1, lo, hi);
+    const float b = eu_interp_mc<0, false>(gr, qf1, qx, qy, a2, lo, hi);
+    out1[i] = eu_mc_correct(f, q1[i], b, a1, a2, lo, hi);
+  }
+}
+
 static inline dim3 cell_grid(const euler_sim* S) { return dim3((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4); }   // this rank's rows (all of them without slabs)
 
 int eu_launch_colorize(euler_sim* S) {
@@ -118,6 +159,23 @@ int eu_launch_dye_advect(euler_sim* S, float dt) {
            S->u, S->v, g, dt, S->row_lo, S->row_hi);
   // memcpy(g_r, g_rtmp, sizeof(g_r)) x3 (main.c:875,878,881): the WHOLE scratch array, stale non-fluid entries included (a row slab: its own rows)
   const size_t o = (size_t)S->row_lo * S->X, n = (size_t)(S->row_hi - S->row_lo) * S->X;
+  if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (a whole-grid handle): the corrected r, g into the velocity scratch, copied over the old ones; then b the same way
+    float* sc[2] = {S->mc_u, S->mc_v};
+    if (S->opt[EULER_OPT_ADVECT_RK2]) {
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<true>, cell_grid(S), dim3(256), S->dye[0], S->dye[3], sc[0], S->dye[1], S->dye[4], sc[1], S->u, S->v, g, dt, S->row_lo, S->row_hi);
+    } else {
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<false>, cell_grid(S), dim3(256), S->dye[0], S->dye[3], sc[0], S->dye[1], S->dye[4], sc[1], S->u, S->v, g, dt, S->row_lo, S->row_hi);
+    }
+    for (int k = 0; k < 2; ++k) HIPCHK(hipMemcpyAsync(S->dye[k] + o, sc[k] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
+    const float* none = nullptr;
+    if (S->opt[EULER_OPT_ADVECT_RK2]) {
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<true>, cell_grid(S), dim3(256), S->dye[2], S->dye[5], sc[0], none, none, (float*)nullptr, S->u, S->v, g, dt, S->row_lo, S->row_hi);
+    } else {
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<false>, cell_grid(S), dim3(256), S->dye[2], S->dye[5], sc[0], none, none, (float*)nullptr, S->u, S->v, g, dt, S->row_lo, S->row_hi);
+    }
+    HIPCHK(hipMemcpyAsync(S->dye[2] + o, sc[0] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
+    return EULER_OK;
+  }
   for (int k = 0; k < 3; ++k) HIPCHK(hipMemcpyAsync(S->dye[k] + o, S->dye[3 + k] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
   return EULER_OK;
 }

@@ -250,7 +250,8 @@ int eu_launch_extrapolate(euler_sim* S) {
 // second zero_bounds pair (non-fluid or solid faces are 0, so the reference's stale entries and the
 // gravity it adds to non-fluid faces never survive).
 // RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the midpoint velocity (euler_dev.h eu_mid_vel_*); everything else as it stands
-template <bool RK2>
+// MC (EULER_OPT_ADVECT_MACCORMACK): the forward pass - the same values without gravity, into the scratch grids that k_mc_correct_velocity reads
+template <bool RK2, bool MC = false>
 __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict__ u, const float* __restrict__ v,
                                                          float* __restrict__ uout, float* __restrict__ vout,
                                                          const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
@@ -285,7 +286,69 @@ __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict
         if (RK2) { const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
         const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
         out = eu_interp<2>(g, v, px, py);
-        out += EU_G * dt;                                                 // main.c:542
+        if (!MC) out += EU_G * dt;                                        // main.c:542
+      }
+      vout[i] = out;
+    }
+  }
+}
+
+// EULER_OPT_ADVECT_MACCORMACK, the correction pass (docs/advection_maccormack.md): per live face the forward trace again (its value and the limiter's lo / hi, recomputed
+// rather than stored), the backward trace - the same code with -dt - into the forward results uf / vf, half the round-trip error added, the result clamped to [lo, hi].
+// Writes utmp / vtmp like k_advect_velocity<RK2> (0 on faces that are not live, gravity last); the same tile-map skip.
+template <bool RK2>
+__global__ __launch_bounds__(256) void k_mc_correct_velocity(const float* __restrict__ u, const float* __restrict__ v,
+                                                             const float* __restrict__ uf, const float* __restrict__ vf,
+                                                             float* __restrict__ uout, float* __restrict__ vout,
+                                                             const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
+                                                             const uint8_t* __restrict__ tmap, int tnx, int tn, int rep) {
+  const int X = g.X, Y = g.Y;
+  if (tmap && eu_tiles_idle(tmap, tnx, tn, (y0 + (int)blockIdx.y * 4 * rep) >> 6, (int)blockIdx.x, 1)) return;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (x >= X) return;
+  const float bdt = -dt;
+  for (int r = 0; r < rep; ++r) {
+    const int y = y0 + ((int)blockIdx.y * rep + r) * 4 + (int)(threadIdx.x >> 6);
+    if (y >= y1) return;
+    const size_t i = (size_t)y * X + x;
+    if (x < X - 1) {
+      float out = 0.f;
+      if (eu_prop_u(g.count, i) && !eu_prop_u(solid, i)) {
+        const float u0 = u[i];
+        const float dy0 = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);
+        float fdx = u0, fdy = dy0, bdx = u0, bdy = dy0;
+        if (RK2) {
+          const float2 m = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, u0, dy0, 0.5f * dt); fdx = m.x; fdy = m.y;
+          const float2 n = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, u0, dy0, 0.5f * bdt); bdx = n.x; bdy = n.y;
+        }
+        const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
+        const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
+        bool a1, a2;
+        float lo, hi;
+        const float f = eu_interp_mc<1, true>(g, u, px, py, a1, lo, hi);
+        const float b = eu_interp_mc<1, false>(g, uf, qx, qy, a2, lo, hi);
+        out = eu_mc_correct(f, u0, b, a1, a2, lo, hi);
+      }
+      uout[i] = out;
+    }
+    if (y < Y - 1) {
+      float out = 0.f;
+      if (eu_prop_v(g.count, i, X) && !eu_prop_v(solid, i, X)) {
+        const float v0 = v[i];
+        const float dx0 = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);
+        float fdx = dx0, fdy = v0, bdx = dx0, bdy = v0;
+        if (RK2) {
+          const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx0, v0, 0.5f * dt); fdx = m.x; fdy = m.y;
+          const float2 n = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx0, v0, 0.5f * bdt); bdx = n.x; bdy = n.y;
+        }
+        const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
+        const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
+        bool a1, a2;
+        float lo, hi;
+        const float f = eu_interp_mc<2, true>(g, v, px, py, a1, lo, hi);
+        const float b = eu_interp_mc<2, false>(g, vf, qx, qy, a2, lo, hi);
+        out = eu_mc_correct(f, v0, b, a1, a2, lo, hi);
+        out += EU_G * dt;                                                 // main.c:542, after the clamp
       }
       vout[i] = out;
     }
@@ -351,7 +414,17 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   if (lean) while (rep < 16 && ((size_t)S->X * S->Y >> 22) >= (size_t)(2 * rep)) rep *= 2;      // (2048^2: 1, 4096^2: 4, 8192^2 and beyond: 16 - at least 16 K workgroups)
   grid.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
   const uint8_t* tm = lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr;
-  if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
+  if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (never on a row slab either; the forward pass skips the same tiles: no mask reads the scratch there)
+    if (S->opt[EULER_OPT_ADVECT_RK2]) {
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<true, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+             S->tmap_nx, S->tmap_n, rep);
+    } else {
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<false, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+             S->tmap_nx, S->tmap_n, rep);
+    }
+  } else if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
   else
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);

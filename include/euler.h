@@ -389,6 +389,10 @@ enum {
   EULER_OPT_ADVECT_RK2 = 22,        /* CHANGES THE BITS.  0 (default): the reference's forward-Euler transport; 1: the midpoint rule (RK2) for the back-traces of u, v and the dye and for
                                        the marker move (docs/advection_rk2.md).  May change between any two calls; a row-slab handle refuses 1 (EULER_ESTATE: the midpoint
                                        samples reach one row beyond the slab's ghost rows) */
+  EULER_OPT_ADVECT_MACCORMACK = 23, /* CHANGES THE BITS.  0 (default): the reference's semi-Lagrangian transport; 1: MacCormack with the Selle et al. clamp for u, v and the dye
+                                       (docs/advection_maccormack.md), with either trace of EULER_OPT_ADVECT_RK2.  May change between any two calls; the first switch to 1
+                                       allocates two grids of scratch (EULER_ENOMEM: nothing changed); a row-slab handle refuses 1 (EULER_ESTATE: the correction reads the
+                                       forward result one row beyond the own rows) */
   EULER_OPT__COUNT
 };
 int euler_set_option(euler_sim* sim, int32_t key, int64_t value);

@@ -8,6 +8,7 @@ table and one JSON line.
 
   python tools/advection_cost.py --size 8192 --workload half_tank              # the headline state (roofline mode)
   python tools/advection_cost.py --size 4096 --workload dam_break --warmup 40  # moving, after the impact
+  python tools/advection_cost.py --scheme maccormack                           # EULER_OPT_ADVECT_MACCORMACK instead (docs/advection_maccormack.md)
 """
 import argparse
 import json
@@ -21,6 +22,8 @@ import euler_amd as ea  # noqa: E402
 from euler_amd import scenarios  # noqa: E402
 
 CLASSES = ("advect_velocity", "marker_advect", "marker_events")
+SCHEMES = {"rk2": ("RK2", ((ea.OPT_ADVECT_RK2, 1),)), "maccormack": ("MC", ((ea.OPT_ADVECT_MACCORMACK, 1),)),
+           "rk2+maccormack": ("RK2+MC", ((ea.OPT_ADVECT_RK2, 1), (ea.OPT_ADVECT_MACCORMACK, 1)))}
 
 
 def make(args):
@@ -47,12 +50,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3, help="frames both handles step with RK1 before the second is switched to RK2")
     ap.add_argument("--frames", type=int, default=6, help="frames per handle and phase")
     ap.add_argument("--max-iterations", type=int, default=100)
+    ap.add_argument("--scheme", default="rk2", choices=list(SCHEMES), help="what the second handle switches to (default rk2)")
     args = ap.parse_args()
+    label = SCHEMES[args.scheme][0]
 
     a, b = make(args), make(args)
     for _ in range(args.warmup):
         a.step(); b.step()
-    b.set_option(ea.OPT_ADVECT_RK2, 1)
+    for key, val in SCHEMES[args.scheme][1]:
+        b.set_option(key, val)
     a.step(); b.step()      # (one untimed frame each in the new mode)
 
     wall = {0: [], 1: []}
@@ -76,9 +82,11 @@ def main():
            "frame_substeps": {k: statistics.median(subs[k]) for k in (0, 1)},
            "class_ms_per_substep": {k: {c: prof[k].get(c, (0.0, 0))[0] / max(nsub[k], 1) for c in CLASSES} for k in (0, 1)},
            "multi_events": b.stats().marker_multi_events}
+    if args.scheme != "rk2":
+        res["scheme"] = args.scheme
     f1, f2 = res["frame_ms"][0], res["frame_ms"][1]
     per_sub = {k: res["frame_ms"][k] / max(res["frame_substeps"][k], 1) for k in (0, 1)}
-    print("| %d^2 %s | RK1 | RK2 | RK2 / RK1 |" % (args.size, args.workload))
+    print("| %d^2 %s | RK1 | %s | %s / RK1 |" % (args.size, args.workload, label, label))
     print("|---|---|---|---|")
     for c in CLASSES:
         x, y = res["class_ms_per_substep"][0][c], res["class_ms_per_substep"][1][c]
