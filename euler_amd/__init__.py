@@ -22,6 +22,11 @@ PRECOND_IC0, PRECOND_JACOBI, PRECOND_IC0_TILE, PRECOND_IC0_TILE2, PRECOND_IC0_TI
 SWEEP_AUTO, SWEEP_BAND, SWEEP_SIMPLE = 0, 1, 2
 PCG_F64, PCG_F32 = 0, 1
 RESIDENT_AUTO, RESIDENT_OFF = 0, 1
+IMAGE_COVERAGE, IMAGE_DYE, IMAGE_SPEED = 0, 1, 2      # EULER_IMAGE_*: euler_overview_rgb's modes
+# euler_overview_px (include/euler.h): one pixel of the whole-domain overview = one box of interior cells
+OVERVIEW_DTYPE = np.dtype({"names": ["cells", "solid", "sink", "water", "marks", "max_speed2", "dye"],
+                           "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.uint32, np.float32, (np.uint64, 3)],
+                           "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 48})
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
  F_PRESSURE, F_PCG_B, F_PCG_R, F_PCG_Z, F_PCG_S, F_PCG_Q, F_CELLMASK,
  F_DYE_R, F_DYE_G, F_DYE_B, F_DYE_RTMP, F_DYE_GTMP, F_DYE_BTMP, F_MARKER_KEYS) = range(25)
@@ -80,6 +85,7 @@ EXPORTS = [
     "euler_rccl_unique_id", "euler_rccl_version", "euler_set_comm_rccl", "euler_comm_calls",
     "euler_p2p_export", "euler_p2p_connect", "euler_p2p_disconnect", "euler_p2p_calls", "euler_resident_info",
     "euler_set_option", "euler_get_option",
+    "euler_overview", "euler_overview_text", "euler_overview_rgb", "euler_render_fit",
 ]
 
 
@@ -150,6 +156,10 @@ def load_library():
         "euler_p2p_calls": (C.c_int, [vp, C.POINTER(u64)]),
         "euler_set_option": (C.c_int, [vp, i32, C.c_int64]),
         "euler_get_option": (C.c_int, [vp, i32, C.POINTER(C.c_int64)]),
+        "euler_overview": (C.c_int, [vp, i32, i32, vp, C.c_size_t]),
+        "euler_overview_text": (C.c_int, [vp, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
+        "euler_overview_rgb": (C.c_int, [vp, i32, i32, i32, f32, vp, C.c_size_t]),
+        "euler_render_fit": (C.c_int, [vp, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -200,6 +210,44 @@ def render_grids(solid, sink, count, wx, wy, rgb=None):
     buf = C.create_string_buffer(max(n.value, 1))
     _check(fn(*ptrs, X, Y, wx, wy, buf, n.value, C.byref(n)))
     return buf.raw[: n.value]
+
+
+def _overview_records(px):
+    px = np.ascontiguousarray(px, OVERVIEW_DTYPE)
+    if px.ndim != 2 or px.size == 0:
+        raise ValueError("overview records: an array of shape (h, w)")
+    return px
+
+
+def overview_text(px, rainbow=False):
+    """The fit-to-window frame of overview records (euler_overview_text): one glyph per record through the formatter of draw()."""
+    px = _overview_records(px)
+    h, w = px.shape
+    L = load_library()
+    n = C.c_int32(0)
+    _check(L.euler_overview_text(px.ctypes.data, w, h, int(rainbow), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    _check(L.euler_overview_text(px.ctypes.data, w, h, int(rainbow), buf, n.value, C.byref(n)))
+    return buf.raw[: n.value]
+
+
+def overview_rgb(px, mode=IMAGE_COVERAGE, speed_scale=1.0):
+    """Overview records -> uint8 (h, w, 3), row 0 = top (euler_overview_rgb)."""
+    px = _overview_records(px)
+    h, w = px.shape
+    rgb = np.empty((h, w, 3), np.uint8)
+    _check(load_library().euler_overview_rgb(px.ctypes.data, w, h, int(mode), float(speed_scale), rgb.ctypes.data, rgb.nbytes))
+    return rgb
+
+
+def write_ppm(path, rgb):
+    """uint8 (h, w, 3) -> a binary PPM (P6, maxval 255)."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("write_ppm: an array of shape (h, w, 3)")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        f.write(rgb.tobytes())
 
 
 SNAPSHOT_F32 = ("u", "v", "utmp", "vtmp")
@@ -333,6 +381,20 @@ class Simulation:
         _check(self.L.euler_render(self.h, wx, wy, None, 0, C.byref(n)))
         buf = C.create_string_buffer(max(n.value, 1))
         _check(self.L.euler_render(self.h, wx, wy, buf, n.value, C.byref(n)))
+        return buf.raw[: n.value]
+
+    def overview(self, w, h):
+        """The whole interior reduced on the device to h x w boxes of cells (euler_overview): an array of OVERVIEW_DTYPE, shape (h, w), row 0 = top."""
+        px = np.zeros((max(int(h), 0), max(int(w), 0)), OVERVIEW_DTYPE)
+        _check(self.L.euler_overview(self.h, w, h, px.ctypes.data if px.size else np.zeros(1, OVERVIEW_DTYPE).ctypes.data, px.nbytes))
+        return px
+
+    def render_fit(self, wx, wy):
+        """draw() of the WHOLE interior fitted into wx x wy glyphs (euler_render_fit)."""
+        n = C.c_int32(0)
+        _check(self.L.euler_render_fit(self.h, wx, wy, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(self.L.euler_render_fit(self.h, wx, wy, buf, n.value, C.byref(n)))
         return buf.raw[: n.value]
 
     def colorize(self):

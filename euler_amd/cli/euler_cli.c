@@ -10,9 +10,14 @@
  * handler one character per frame ('.' = no key) so that the gate is testable without a tty.
  *
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
- *         [--keys STRING] [--resume FILE] [--checkpoint FILE] <scenario>
+ *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit]
+ *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
+ * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
+ * one glyph per cell of the window's corner.  --ppm writes PREFIX%06d.ppm (binary P6) of the whole interior after every N-th frame (default 1;
+ * frame 0 included), WxH boxes (default: the interior divided by the smallest integer that brings both sides to <= 1024), coloured by
+ * coverage, by the dye (the default with --rainbow) or by speed (blue = 0 ... red = SCALE cells per second and above).
  */
 #include <errno.h>
 #include <signal.h>
@@ -28,7 +33,8 @@
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
-                  "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] <scenario>\n", argv0);
+                  "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
+                  "[--fit] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -71,6 +77,29 @@ static int window_size(int* wx, int* wy) {
   return 0;
 }
 
+/* ---- --ppm: the whole interior as a binary PPM (euler_overview + euler_overview_rgb) ---------------- */
+static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, int W, int H, int mode, float scale) {
+  const size_t n = (size_t)W * (size_t)H;
+  euler_overview_px* px = (euler_overview_px*)malloc(n * sizeof *px);
+  uint8_t* rgb = (uint8_t*)malloc(n * 3);
+  char* path = (char*)malloc(strlen(prefix) + 32);
+  int ok = px && rgb && path;
+  if (!ok) fprintf(stderr, "--ppm: out of memory\n");
+  if (ok && (euler_overview(sim, W, H, px, n * sizeof *px) != EULER_OK || euler_overview_rgb(px, W, H, mode, scale, rgb, n * 3) != EULER_OK)) {
+    fprintf(stderr, "%s\n", euler_last_error());
+    ok = 0;
+  }
+  if (ok) {
+    sprintf(path, "%s%06d.ppm", prefix, frame);
+    FILE* f = fopen(path, "wb");
+    ok = f && fprintf(f, "P6\n%d %d\n255\n", W, H) > 0 && fwrite(rgb, 1, n * 3, f) == n * 3;
+    if (f && fclose(f) != 0) ok = 0;
+    if (!ok) fprintf(stderr, "--ppm: cannot write %s: %s\n", path, strerror(errno));
+  }
+  free(px); free(rgb); free(path);
+  return ok ? 0 : -1;
+}
+
 /* ---- the reference's loop state (main.c:85-88) ----------------------------------------------- */
 typedef struct app {
   euler_sim* sim;
@@ -104,6 +133,9 @@ int main(int argc, char** argv) {
   const char* resume = NULL;
   const char* checkpoint = NULL;
   const char* keys = NULL;
+  int fit = 0, ppm_w = 0, ppm_h = 0, ppm_every = 1, ppm_mode = -1;
+  float ppm_scale = 1.f;
+  const char* ppm = NULL;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -137,11 +169,36 @@ int main(int argc, char** argv) {
     }
     /* include/euler.h EULER_OPT_ADVECT_MACCORMACK: the MacCormack correction with the clamp on top of either trace (docs/advection_maccormack.md); not recorded in a snapshot */
     else if (!strcmp(argv[i], "--maccormack")) maccormack = 1;
+    /* the whole-domain overview (docs/overview.md) */
+    else if (!strcmp(argv[i], "--fit")) fit = 1;
+    else if (!strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
+    else if (!strcmp(argv[i], "--ppm-size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &ppm_w, &ppm_h) != 2 || ppm_w < 1 || ppm_h < 1) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--ppm-every") && i + 1 < argc) { ppm_every = atoi(argv[++i]); if (ppm_every < 1) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--ppm-mode") && i + 1 < argc) {
+      const char* v = argv[++i];
+      char tail;
+      if (!strcmp(v, "coverage")) ppm_mode = EULER_IMAGE_COVERAGE;
+      else if (!strcmp(v, "dye")) ppm_mode = EULER_IMAGE_DYE;
+      else if (sscanf(v, "speed:%f%c", &ppm_scale, &tail) == 1 && ppm_scale > 0.f) ppm_mode = EULER_IMAGE_SPEED;
+      else { usage(argv[0]); return 1; }
+    }
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
   }
   if (!scenario && !resume) { usage(argv[0]); return 1; }                                                       /* main.c:986-989 */
+
+  if (ppm) {
+    const int xi = cfg.X - 2, yi = cfg.Y - 2;
+    if (!ppm_w) {      /* the interior divided by the smallest integer that brings both sides to <= 1024 */
+      int d = 1;
+      while (xi / d > 1024 || yi / d > 1024) ++d;
+      ppm_w = xi / d > 1 ? xi / d : 1; ppm_h = yi / d > 1 ? yi / d : 1;
+    }
+    if (ppm_w > xi || ppm_h > yi) { usage(argv[0]); return 1; }
+    if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
+  }
+  int (*render)(euler_sim*, int32_t, int32_t, char*, int32_t, int32_t*) = fit ? euler_render_fit : euler_render;
 
   const int interactive = !dump && isatty(STDIN_FILENO) && isatty(STDOUT_FILENO);
   if (interactive && !window_given) {
@@ -194,14 +251,14 @@ int main(int argc, char** argv) {
       if (window_size(&wx, &wy) == 0) write_all("\x1b[2J\x1b[H", 7);
     }
     int32_t len = 0;
-    if (euler_render(app.sim, wx, wy, NULL, 0, &len) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    if (render(app.sim, wx, wy, NULL, 0, &len) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
     if (len > cap) {
       cap = len + 4096;
       char* nb = (char*)realloc(buf, (size_t)cap);
       if (!nb) { rc_exit = 1; break; }
       buf = nb;
     }
-    if (euler_render(app.sim, wx, wy, buf, cap, &len) != EULER_OK || len > cap) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    if (render(app.sim, wx, wy, buf, cap, &len) != EULER_OK || len > cap) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
     if (dump) {
       printf("--- frame %d (%d bytes)\n", f, (int)len);
       fwrite(buf, 1, (size_t)len, stdout);
@@ -212,6 +269,7 @@ int main(int argc, char** argv) {
       write_all(buf, (size_t)len);
       write_all("\x1b[?25l", 6);           /* hide cursor */
     }
+    if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, ppm_w, ppm_h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }

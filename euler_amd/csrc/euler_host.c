@@ -1,6 +1,7 @@
 /*
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
- * xorshift64* stream, initial marker seeding, and the ASCII frame formatter.
+ * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
+ * whole-domain overview's records (text through the same frame formatter, RGB).
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -285,4 +286,76 @@ int euler_render_grids_rgb(const uint8_t* solid, const uint8_t* sink, const uint
                            int32_t X, int32_t Y, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {
   if (!r || !g || !b) return EULER_EINVAL;
   return render_rows(solid, sink, count, r, g, b, X, Y, wx, wy, out, cap, len);
+}
+
+/* ---- whole-domain overview: host formatters over euler_overview_px records (include/euler.h, docs/overview.md) ---- */
+
+enum { OV_AIR = 0, OV_SOLID = 4, OV_SINK = 5 };   /* 1..3: the glyph index of draw_rows */
+
+static int overview_class(const euler_overview_px* p) {
+  if (2ull * p->solid >= p->cells) return OV_SOLID;
+  const uint64_t open = (uint64_t)p->cells - p->solid - p->sink;
+  if (p->sink > 0 && p->sink >= open) return OV_SINK;
+  const uint64_t k = ((uint64_t)p->marks + open - 1) / open;     /* open >= 1 here: solid < cells / 2 and sink < open */
+  return k < 3 ? (int)k : 3;
+}
+
+/* buffer_append_color's byte (main.c:902-912) as render_rows forms it */
+static int overview_srgb_byte(float lin) {
+  const float end = nextafterf(256.f, 0.f);
+  float v = end * powf(lin, 1 / 2.2f);
+  return (int)(v < 0.f ? 0.f : (v > end ? end : v));
+}
+
+static float overview_mean_dye(const euler_overview_px* p, int c) {
+  return p->water ? (float)((double)p->dye[c] / ((double)p->water * 16777216.0)) : 0.f;
+}
+
+int euler_overview_text(const euler_overview_px* px, int32_t W, int32_t H, int32_t rainbow,
+                        char* out, int32_t cap, int32_t* len) {
+  if (!px || !len || W < 1 || H < 1) return EULER_EINVAL;
+  /* a (W + 2) x (H + 2) grid of the classes with a border ring that is never drawn: render_rows does the rest */
+  const int32_t X = W + 2, Y = H + 2;
+  const size_t C = (size_t)X * (size_t)Y;
+  uint8_t* g = (uint8_t*)calloc(3, C);
+  float* col = rainbow ? (float*)calloc(3 * C, sizeof(float)) : NULL;
+  if (!g || (rainbow && !col)) { free(g); free(col); return EULER_ENOMEM; }
+  for (int32_t py = 0; py < H; ++py)
+    for (int32_t p = 0; p < W; ++p) {
+      const euler_overview_px* r = px + (size_t)py * W + p;
+      const size_t i = (size_t)(H - py) * X + (size_t)(p + 1);      /* pixel row 0 is the top: grid row Y - 2 */
+      const int k = overview_class(r);
+      if (k == OV_SOLID) g[i] = 1;
+      else if (k == OV_SINK) g[C + i] = 1;
+      else g[2 * C + i] = (uint8_t)k;
+      if (col) for (int c = 0; c < 3; ++c) col[c * C + i] = overview_mean_dye(r, c);
+    }
+  int rc = render_rows(g, g + C, g + 2 * C, col, col ? col + C : NULL, col ? col + 2 * C : NULL, X, Y, W, H, out, cap, len);
+  free(g);
+  free(col);
+  return rc;
+}
+
+int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_t mode, float speed_scale,
+                       uint8_t* rgb, size_t rgb_bytes) {
+  if (!px || !rgb || W < 1 || H < 1 || rgb_bytes != (size_t)W * (size_t)H * 3) return EULER_EINVAL;
+  if (mode != EULER_IMAGE_COVERAGE && mode != EULER_IMAGE_DYE && mode != EULER_IMAGE_SPEED) return EULER_EINVAL;
+  if (mode == EULER_IMAGE_SPEED && !(speed_scale > 0.f)) return EULER_EINVAL;      /* (a NaN fails the comparison too) */
+  const size_t n = (size_t)W * (size_t)H;
+  for (size_t i = 0; i < n; ++i) {
+    const euler_overview_px* r = px + i;
+    int wc[3] = {64, 128, 255};
+    if (mode == EULER_IMAGE_DYE) {
+      for (int c = 0; c < 3; ++c) wc[c] = overview_srgb_byte(overview_mean_dye(r, c));
+    } else if (mode == EULER_IMAGE_SPEED) {
+      float t = sqrtf(r->max_speed2) / speed_scale;
+      if (!(t < 1.f)) t = 1.f;
+      wc[0] = (int)(255.f * t + 0.5f); wc[1] = 128; wc[2] = (int)(255.f * (1.f - t) + 0.5f);
+    }
+    for (int c = 0; c < 3; ++c) {
+      const uint64_t cells = r->cells ? r->cells : 1;
+      rgb[3 * i + c] = (uint8_t)(((uint64_t)r->solid * 128 + (uint64_t)r->sink * 64 + (uint64_t)r->water * (uint64_t)wc[c] + cells / 2) / cells);
+    }
+  }
+  return EULER_OK;
 }

@@ -1,0 +1,296 @@
+// k_overview.hip — euler_overview (include/euler.h, docs/overview.md): the whole interior reduced on the device to a W x H raster of
+// euler_overview_px records, one box of cells per record.  Every field of a record is an integer sum or a maximum of non-negative
+// floats (compared as unsigned bit patterns): whatever order the cells arrive in, the record is the same.
+//
+// One launch.  A workgroup owns a run of WHOLE pixel boxes of one pixel row - npc <= OV_NPC pixel columns, about OV_SPAN cells wide -
+// and, where the boxes are tall, one of nsplit slices of their rows.  Lanes lie along a grid row (four cells each where the rows are
+// 16-byte aligned) and walk down the rows of the slice: a lane's columns - and with them its pixels - do not change on the way, so a
+// lane sums in registers and goes to the LDS table of its workgroup's pixels ONCE per walk; lanes of a wave that all sit in one pixel fold by shuffles
+// first.  The table is written out once: with plain stores where the workgroup saw the whole box (nsplit = 1), else with integer
+// atomics into records the host zeroed.  With the tile map, a 64 x 64 tile without water is read for its solid / sink bytes only.
+//
+// The pass only reads the state and touches none of the handle's validity flags.
+#include "euler_dev.h"
+
+#include <stdlib.h>
+
+#define OV_T 256        // threads per workgroup
+#define OV_NPC 256      // pixels in a workgroup's LDS table
+#define OV_SPAN 1024    // cells along x a workgroup aims at: OV_T lanes x 4 cells
+#define OV_WG_CELLS (1 << 15)   // cells a workgroup should walk before the boxes' rows are split
+
+struct OvArgs {
+  const uint8_t *solid, *sink, *count;
+  const float *u, *v, *dye[3];
+  const uint8_t* tmap;      // null: every tile is read whole
+  int tnx;
+  int X, Y, W, H, npc, nsplit;
+  euler_overview_px* out;
+};
+
+struct OvAcc {
+  unsigned int solid, sink, water, marks, max_bits;
+  unsigned long long dye[3];
+};
+__device__ __forceinline__ void ov_clear(OvAcc& a) { a.solid = a.sink = a.water = a.marks = a.max_bits = 0u; a.dye[0] = a.dye[1] = a.dye[2] = 0ull; }
+__device__ __forceinline__ void ov_merge(OvAcc& a, const OvAcc& b) {
+  a.solid += b.solid; a.sink += b.sink; a.water += b.water; a.marks += b.marks;
+  a.max_bits = b.max_bits > a.max_bits ? b.max_bits : a.max_bits;
+  a.dye[0] += b.dye[0]; a.dye[1] += b.dye[1]; a.dye[2] += b.dye[2];
+}
+// q(x) of include/euler.h: clamp to [0, 1] (a NaN: 0), times 2^24 (exact), truncated
+__device__ __forceinline__ unsigned int ov_q(float x) {
+  const float c = x > 0.f ? (x > 1.f ? 1.f : x) : 0.f;
+  return (unsigned int)(c * 16777216.f);
+}
+
+struct OvTable {
+  unsigned int w[5][OV_NPC];          // solid, sink, water, marks, max_speed2 bits
+  unsigned long long dye[3][OV_NPC];
+};
+template <bool DYE>
+__device__ __forceinline__ void ov_to_table(OvTable& t, int p, const OvAcc& a) {
+  if (a.solid) atomicAdd(&t.w[0][p], a.solid);
+  if (a.sink) atomicAdd(&t.w[1][p], a.sink);
+  if (a.water) {
+    atomicAdd(&t.w[2][p], a.water);
+    atomicAdd(&t.w[3][p], a.marks);
+    if (a.max_bits) atomicMax(&t.w[4][p], a.max_bits);
+    if (DYE) for (int c = 0; c < 3; ++c) if (a.dye[c]) atomicAdd(&t.dye[c][p], a.dye[c]);
+  }
+}
+__device__ __forceinline__ unsigned int ov_wave_sum(unsigned int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned long long ov_wave_sum64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned int ov_wave_max(unsigned int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const unsigned int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+  return v;
+}
+__device__ __forceinline__ int ov_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
+  return v;
+}
+
+// VEC: cells per lane - 4 where X % 4 == 0 (every row starts 16-byte aligned: one dword of each mask, one float4 of each field), else 1
+template <int VEC, bool DYE>
+__global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
+  __shared__ OvTable tab;
+  const int tid = threadIdx.x;
+  const unsigned int Xi = (unsigned int)(a.X - 2), Yi = (unsigned int)(a.Y - 2);
+  const unsigned int groups = (unsigned int)((a.W + a.npc - 1) / a.npc), slice = blockIdx.x / groups;      // (neighbouring workgroups lie along a row)
+  const int p0 = (int)(blockIdx.x % groups) * a.npc, p1 = p0 + a.npc < a.W ? p0 + a.npc : a.W;      // this workgroup's pixel columns [p0, p1)
+  const int py = (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
+  const int xa = 1 + (int)((unsigned long long)p0 * Xi / (unsigned int)a.W), xb = (int)((unsigned long long)p1 * Xi / (unsigned int)a.W);      // its columns [xa, xb]
+  const int ytop = a.Y - 2 - (int)((unsigned long long)py * Yi / (unsigned int)a.H), ybot = a.Y - 1 - (int)((unsigned long long)(py + 1) * Yi / (unsigned int)a.H);
+  const int nrows = ytop - ybot + 1;
+  const int yhi = ytop - (int)((long long)sp * nrows / a.nsplit), ylo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows yhi down to ylo
+  for (int k = tid; k < OV_NPC; k += OV_T) {
+    for (int f = 0; f < 5; ++f) tab.w[f][k] = 0u;
+    for (int c = 0; c < 3; ++c) tab.dye[c][k] = 0ull;
+  }
+  __syncthreads();
+  const size_t X = (size_t)a.X;
+  const int xbase = VEC == 4 ? (xa & ~3) : xa;
+  // (the trip count is the same for the lanes of a wave up to the last pass: the shuffles below run behind a wave-uniform test)
+  for (int xc = xbase; xc <= xb; xc += OV_T * VEC) {
+    const int x0 = xc + tid * VEC;
+    OvAcc acc[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) ov_clear(acc[k]);
+    if (x0 <= xb) {
+      const int tx = x0 >> 6;      // (four aligned cells share a tile column)
+      for (int y = yhi; y >= ylo;) {
+        const int ty = y >> 6;
+        const int yend = (ty << 6) > ylo ? (ty << 6) : ylo;
+        const bool wet = !a.tmap || a.tmap[ty * a.tnx + tx] != 0;      // the tile map is a superset: a cleared flag means no cell of the tile holds markers
+        for (; y >= yend; --y) {
+          const size_t i = (size_t)y * X + (size_t)x0;
+          unsigned int so, si, cn = 0u;
+          float uu[VEC + 1], vv[VEC], vd[VEC], dr[VEC], dg[VEC], db[VEC];
+          if constexpr (VEC == 4) {
+            so = *reinterpret_cast<const unsigned int*>(a.solid + i);
+            si = *reinterpret_cast<const unsigned int*>(a.sink + i);
+          } else { so = a.solid[i]; si = a.sink[i]; }
+          if (wet) {
+            if constexpr (VEC == 4) {
+              cn = *reinterpret_cast<const unsigned int*>(a.count + i);
+              const float4 u4 = *reinterpret_cast<const float4*>(a.u + i);
+              const float4 v4 = *reinterpret_cast<const float4*>(a.v + i);
+              const float4 w4 = *reinterpret_cast<const float4*>(a.v + i - X);
+              uu[0] = a.u[i - 1]; uu[1] = u4.x; uu[2] = u4.y; uu[3] = u4.z; uu[4] = u4.w;
+              vv[0] = v4.x; vv[1] = v4.y; vv[2] = v4.z; vv[3] = v4.w;
+              vd[0] = w4.x; vd[1] = w4.y; vd[2] = w4.z; vd[3] = w4.w;
+              if (DYE) {
+                const float4 r4 = *reinterpret_cast<const float4*>(a.dye[0] + i);
+                const float4 g4 = *reinterpret_cast<const float4*>(a.dye[1] + i);
+                const float4 b4 = *reinterpret_cast<const float4*>(a.dye[2] + i);
+                dr[0] = r4.x; dr[1] = r4.y; dr[2] = r4.z; dr[3] = r4.w;
+                dg[0] = g4.x; dg[1] = g4.y; dg[2] = g4.z; dg[3] = g4.w;
+                db[0] = b4.x; db[1] = b4.y; db[2] = b4.z; db[3] = b4.w;
+              }
+            } else {
+              cn = a.count[i];
+              uu[0] = a.u[i - 1]; uu[1] = a.u[i];
+              vv[0] = a.v[i]; vd[0] = a.v[i - X];
+              if (DYE) { dr[0] = a.dye[0][i]; dg[0] = a.dye[1][i]; db[0] = a.dye[2][i]; }
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const unsigned int s = (so >> (8 * k)) & 0xffu, n = (si >> (8 * k)) & 0xffu, c = (cn >> (8 * k)) & 0xffu;
+            if (s) acc[k].solid += 1u;
+            else if (n) acc[k].sink += 1u;
+            else if (wet && c) {
+              acc[k].water += 1u;
+              acc[k].marks += c < 3u ? c : 3u;
+              const float dx = (uu[k + 1] + uu[k]) / 2.f, dy = (vv[k] + vd[k]) / 2.f;
+              const float s2 = dx * dx + dy * dy;
+              const unsigned int bits = __float_as_uint(s2);
+              if (s2 == s2 && bits > acc[k].max_bits) acc[k].max_bits = bits;      // (s2 >= +0 unless it is a NaN: unsigned order = float order)
+              if (DYE) { acc[k].dye[0] += ov_q(dr[k]); acc[k].dye[1] += ov_q(dg[k]); acc[k].dye[2] += ov_q(db[k]); }
+            }
+          }
+        }
+      }
+    }
+    // the walk is over: each cell column to its pixel of the table
+    int pk[VEC], pmin = 0x7fffffff, pmax = -1;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const int x = x0 + k;
+      pk[k] = x >= xa && x <= xb ? (int)(((unsigned long long)x * (unsigned int)a.W - 1ull) / Xi) - p0 : -1;      // the column px whose range holds x
+      if (pk[k] >= 0) { pmin = pk[k] < pmin ? pk[k] : pmin; pmax = pk[k] > pmax ? pk[k] : pmax; }
+    }
+    const int wmin = ov_wave_min(pmin), wmax = -ov_wave_min(-pmax);
+    if (wmin == wmax) {      // the whole wave sits in one pixel (wide boxes): fold across the lanes, one lane goes to the table
+      OvAcc t;
+      ov_clear(t);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) if (pk[k] >= 0) ov_merge(t, acc[k]);
+      t.solid = ov_wave_sum(t.solid); t.sink = ov_wave_sum(t.sink); t.water = ov_wave_sum(t.water); t.marks = ov_wave_sum(t.marks);
+      t.max_bits = ov_wave_max(t.max_bits);
+      if (DYE) for (int c = 0; c < 3; ++c) t.dye[c] = ov_wave_sum64(t.dye[c]);
+      if ((tid & 63) == 0) ov_to_table<DYE>(tab, wmin, t);
+    } else {
+      OvAcc t;
+      int cur = -1;
+      ov_clear(t);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        if (pk[k] < 0) continue;
+        if (pk[k] != cur) { if (cur >= 0) ov_to_table<DYE>(tab, cur, t); cur = pk[k]; ov_clear(t); }
+        ov_merge(t, acc[k]);
+      }
+      if (cur >= 0) ov_to_table<DYE>(tab, cur, t);
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < p1 - p0; k += OV_T) {
+    const int p = p0 + k;
+    const unsigned int wpx = (unsigned int)((unsigned long long)(p + 1) * Xi / (unsigned int)a.W) - (unsigned int)((unsigned long long)p * Xi / (unsigned int)a.W);
+    const unsigned int cells = wpx * (unsigned int)(yhi - ylo + 1);
+    euler_overview_px* o = a.out + (size_t)py * a.W + p;
+    if (a.nsplit == 1) {
+      euler_overview_px r;
+      r.cells = cells; r.solid = tab.w[0][k]; r.sink = tab.w[1][k]; r.water = tab.w[2][k]; r.marks = tab.w[3][k];
+      r.max_speed2 = __uint_as_float(tab.w[4][k]);
+      r.dye[0] = tab.dye[0][k]; r.dye[1] = tab.dye[1][k]; r.dye[2] = tab.dye[2][k];
+      *o = r;
+    } else {      // a slice of the box's rows: added to the record the host zeroed (integers and a maximum: exact in any order)
+      if (cells) atomicAdd(&o->cells, cells);
+      if (tab.w[0][k]) atomicAdd(&o->solid, tab.w[0][k]);
+      if (tab.w[1][k]) atomicAdd(&o->sink, tab.w[1][k]);
+      if (tab.w[2][k]) {
+        atomicAdd(&o->water, tab.w[2][k]);
+        atomicAdd(&o->marks, tab.w[3][k]);
+        if (tab.w[4][k]) atomicMax(reinterpret_cast<unsigned int*>(&o->max_speed2), tab.w[4][k]);
+        for (int c = 0; c < 3; ++c) if (tab.dye[c][k]) atomicAdd(reinterpret_cast<unsigned long long*>(&o->dye[c]), tab.dye[c][k]);
+      }
+    }
+  }
+}
+
+// the device buffer of the records: allocated by the first call, grown when W * H grows (a failure leaves the handle as it was)
+static int ov_reserve(euler_sim* S, size_t n) {
+  if (n <= S->ov_cap) return EULER_OK;
+  euler_overview_px* nb = nullptr;
+  if (hipMalloc((void**)&nb, n * sizeof(euler_overview_px)) != hipSuccess) {
+    (void)hipGetLastError();
+    eu_set_error("euler_overview: %zu bytes of device memory for the records", n * sizeof(euler_overview_px));
+    return EULER_ENOMEM;
+  }
+  if (S->ov_buf) {
+    HIPCHK(hipStreamSynchronize(S->stream));
+    (void)hipFree(S->ov_buf);
+    S->hbm_bytes -= S->ov_cap * sizeof(euler_overview_px);
+  }
+  S->ov_buf = nb; S->ov_cap = n;
+  S->hbm_bytes += n * sizeof(euler_overview_px);
+  return EULER_OK;
+}
+
+// the reduction alone, on the handle's stream, into S->ov_buf (tools/overview_cost.py times it through the KC_MISC class)
+static int ov_launch(euler_sim* S, int W, int H) {
+  const int Xi = S->X - 2, Yi = S->Y - 2;
+  OvArgs a;
+  a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
+  for (int c = 0; c < 3; ++c) a.dye[c] = S->dye[c];
+  a.tmap = eu_tile_map_on(S) ? S->tmap : nullptr; a.tnx = S->tmap_nx;
+  a.X = S->X; a.Y = S->Y; a.W = W; a.H = H; a.out = S->ov_buf;
+  long long npc = (long long)OV_SPAN * W / Xi;      // pixel columns per workgroup: about OV_SPAN cells wide, at least one box, at most the table
+  a.npc = (int)(npc < 1 ? 1 : (npc > OV_NPC ? OV_NPC : npc));
+  const long long span = ((long long)a.npc * Xi + W - 1) / W, rows_max = (Yi + H - 1) / H, rows_min = Yi / H;
+  long long ns = (span * rows_max + OV_WG_CELLS - 1) / OV_WG_CELLS;      // slices of a box's rows
+  a.nsplit = (int)(ns < 1 ? 1 : (ns > rows_min ? rows_min : ns));
+  if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->ov_buf, 0, (size_t)W * H * sizeof(euler_overview_px), S->stream));
+  const long long nwg = (long long)((W + a.npc - 1) / a.npc) * H * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
+  const dim3 grid((unsigned)nwg);
+  const bool vec = S->X % 4 == 0, dye = S->dye[0] != nullptr;
+  if (vec && dye) LAUNCH(S, KC_MISC, (k_overview<4, true>), grid, dim3(OV_T), a);
+  else if (vec) LAUNCH(S, KC_MISC, (k_overview<4, false>), grid, dim3(OV_T), a);
+  else if (dye) LAUNCH(S, KC_MISC, (k_overview<1, true>), grid, dim3(OV_T), a);
+  else LAUNCH(S, KC_MISC, (k_overview<1, false>), grid, dim3(OV_T), a);
+  HIPCHK(hipGetLastError());
+  return EULER_OK;
+}
+
+extern "C" int euler_overview(euler_sim* S, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes) {
+  if (!S || !out) { eu_set_error("euler_overview: null argument"); return EULER_EINVAL; }
+  if (S->slab_on) { eu_set_error("euler_overview: not on a row-slab handle (a box of cells straddles slabs)"); return EULER_ESTATE; }
+  if (!S->loaded) { eu_set_error("euler_overview: no scenario loaded"); return EULER_ESTATE; }
+  if (W < 1 || H < 1 || W > S->X - 2 || H > S->Y - 2) { eu_set_error("euler_overview: a raster of %d x %d for an interior of %d x %d cells", (int)W, (int)H, S->X - 2, S->Y - 2); return EULER_EINVAL; }
+  const size_t n = (size_t)W * (size_t)H;
+  if (out_bytes != n * sizeof(euler_overview_px)) { eu_set_error("euler_overview: %zu bytes given, %zu expected", out_bytes, n * sizeof(euler_overview_px)); return EULER_EINVAL; }
+  int rc = ov_reserve(S, n);
+  if (!rc) rc = ov_launch(S, W, H);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(out, S->ov_buf, out_bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return EULER_OK;
+}
+
+extern "C" int euler_render_fit(euler_sim* S, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {
+  if (!S || !len || wx < 1 || wy < 1) { eu_set_error("euler_render_fit: bad argument"); return EULER_EINVAL; }
+  const int W = wx < S->X - 2 ? wx : S->X - 2, H = wy < S->Y - 2 ? wy : S->Y - 2;
+  const size_t bytes = (size_t)W * H * sizeof(euler_overview_px);
+  euler_overview_px* px = (euler_overview_px*)malloc(bytes);
+  if (!px) return EULER_ENOMEM;
+  int rc = euler_overview(S, W, H, px, bytes);
+  if (!rc) rc = euler_overview_text(px, W, H, S->cfg.rainbow, out, cap, len);
+  free(px);
+  return rc;
+}
+
+void eu_overview_release(euler_sim* S) {
+  if (S->ov_buf) (void)hipFree(S->ov_buf);
+  S->ov_buf = nullptr; S->ov_cap = 0;
+}

@@ -304,6 +304,51 @@ int euler_render_grids_rgb(const uint8_t* solid, const uint8_t* sink, const uint
 /* colorize() (main.c:187-201), the reference's 'r' key (main.c:970-973): recolour the current fluid. */
 int euler_colorize(euler_sim* sim);
 
+/* ---- whole-domain overview (docs/overview.md) ---------------------------------------------- */
+/* euler_render shows one glyph per CELL: at 4096^2 a 98 x 38 corner under the ceiling.  The overview reduces the whole interior
+ * ON THE DEVICE to a W x H raster of boxes of cells; only the W * H records cross to the host.  Everything in a record is an
+ * integer sum or a maximum of non-negative floats, so the result does not depend on the order of the reduction (tests compare bits). */
+typedef struct euler_overview_px {   /* one output pixel = one box of interior cells; 48 bytes */
+  uint32_t cells;       /* cells in the box */
+  uint32_t solid;       /* cells with solid != 0 */
+  uint32_t sink;        /* cells with solid == 0 && sink != 0 */
+  uint32_t water;       /* cells with solid == 0 && sink == 0 && count > 0 */
+  uint32_t marks;       /* sum over the water cells of min(count, 3): the reference's glyph index (draw_rows) */
+  float    max_speed2;  /* max over the water cells of dx*dx + dy*dy, dx = (u[i] + u[i-1]) / 2, dy = (v[i] + v[i-X]) / 2
+                           (the cell-centre velocity k_advect_dye starts from); 0 without water; a NaN term is skipped */
+  uint64_t dye[3];      /* sum over the water cells of q(r), q(g), q(b), q(x) = (uint32_t)(clamp(x, 0, 1) * 16777216.f) and q(NaN) = 0;
+                           0 on handles without euler_config.rainbow */
+} euler_overview_px;
+/* The boxes: only the interior is shown, Xi = X - 2 columns and Yi = Y - 2 rows; 1 <= W <= Xi and 1 <= H <= Yi (else EULER_EINVAL), so no box
+ * is empty.  Pixel column px covers the cells x = 1 + floor(px * Xi / W) ... floor((px + 1) * Xi / W); pixel row py = 0 is the TOP of the
+ * picture: row py covers y = Y - 2 - floor(py * Yi / H) down to y = Y - 1 - floor((py + 1) * Yi / H).  out holds W * H records, row py at
+ * out + py * W; out_bytes must be exactly W * H * sizeof(euler_overview_px).  One launch on the handle's stream that only READS the state
+ * (the arrays euler_get_field returns for U, V, COUNT, SOLID, SINK, DYE_*): stepping afterwards gives the bits of a run that never called it.
+ * The device buffer of the records comes with the first call and grows with W * H (EULER_ENOMEM: the handle unchanged).  Row-slab handles
+ * refuse (EULER_ESTATE); a handle without a loaded state: EULER_ESTATE. */
+int euler_overview(euler_sim* sim, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes);
+/* Host formatters over such records (no GPU needed).  The class of a pixel, in this order: 2 * solid >= cells: solid ('X'); else, with
+ * open = cells - solid - sink: sink > 0 && sink >= open: sink ('='); else k = min(3, (marks + open - 1) / open) is the glyph index of
+ * draw_rows (rounded up: a thin sheet still shows as 'o'; 0 is air).
+ * euler_overview_text: those classes through the frame formatter of euler_render (its colour runs, escapes and line ends), W x H glyphs; rainbow != 0:
+ * every water glyph carries the colour of the box's mean dye, dye[c] / (water * 2^24).  With one cell per pixel (W = X - 2, H = Y - 2) the
+ * text is euler_render(sim, X - 2, Y - 2) byte for byte; with the dye each colour byte is within 1 of it (q truncates to 24 bits).
+ * Same sizing protocol as euler_render. */
+int euler_overview_text(const euler_overview_px* px, int32_t W, int32_t H, int32_t rainbow,
+                        char* out, int32_t cap, int32_t* len);
+enum {
+  EULER_IMAGE_COVERAGE = 0,   /* water = (64, 128, 255) */
+  EULER_IMAGE_DYE = 1,        /* water = the sRGB bytes of the box's mean dye (the formula of the coloured frame); records without dye: black water */
+  EULER_IMAGE_SPEED = 2       /* water = ((int)(255 t + 0.5), 128, (int)(255 (1 - t) + 0.5)), t = min(1, sqrtf(max_speed2) / speed_scale) */
+};
+/* W * H * 3 bytes, row 0 = top.  Per channel (solid * S + sink * K + water * Wc + cells / 2) / cells in integers, air = 0, S = 128, K = 64,
+ * Wc by mode (above).  EULER_IMAGE_SPEED needs speed_scale > 0; another mode, rgb_bytes != W * H * 3: EULER_EINVAL. */
+int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_t mode, float speed_scale,
+                       uint8_t* rgb, size_t rgb_bytes);
+/* The fit-to-window frame: euler_overview with W = min(wx, X - 2), H = min(wy, Y - 2), then euler_overview_text (coloured on a handle created
+ * with euler_config.rainbow).  Sizing protocol of euler_render; wx < 1 or wy < 1: EULER_EINVAL. */
+int euler_render_fit(euler_sim* sim, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
