@@ -7,6 +7,7 @@ import pytest
 import euler_amd as ea
 from golden_util import load, scenario_text
 from oracle_lib import Oracle
+from resident_ref import random_scene_text
 from test_gpu_parity import assert_bits, compare_all
 
 pytestmark = pytest.mark.gpu
@@ -506,15 +507,7 @@ def test_coarse_modes_on_random_scenes(seed, mg):
     """Random walls, pools and air pockets (a 44 x 36 character scene upscaled to 300 x 260: aggregates without fluid, aggregates cut by walls,
     fluid in single cells): two-level and multilevel modes against the oracle's restatements - iterates capped at 5 to 1e-10 of max |p| for
     three substeps of moving water, then a frame solved to tolerance with the same cell grid and iteration counts within 5 %."""
-    rng = np.random.default_rng(seed)
-    H, W = 36, 44
-    rows = []
-    for y in range(H):
-        r = rng.random(W)
-        row = "".join("X" if v < 0.10 else ("0" if v < 0.62 else " ") for v in r)
-        rows.append("X" + row[1:-1] + "X")
-    rows[0] = rows[-1] = "X" * W
-    text = "\n".join(rows) + "\n"
+    text = random_scene_text(seed)
     o, sim = _two_level_pair(300, 260, 5, text, mg=mg)
     for k in range(3):
         dt = sim.timestep(0.1)
