@@ -27,6 +27,12 @@ IMAGE_COVERAGE, IMAGE_DYE, IMAGE_SPEED = 0, 1, 2      # EULER_IMAGE_*: euler_ove
 OVERVIEW_DTYPE = np.dtype({"names": ["cells", "solid", "sink", "water", "marks", "max_speed2", "dye"],
                            "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.uint32, np.float32, (np.uint64, 3)],
                            "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 48})
+# euler_diag (include/euler.h): the record of the flow diagnostics, and the doubles euler_diag_derive forms from it
+DIAG_CROWDED = 8      # EULER_DIAG_CROWDED
+DIAG_DTYPE = np.dtype({"names": ["cells", "fluid", "markers", "crowded", "mass_x", "mass_y", "div_l1", "ke_hi", "ke_lo", "count_max", "nonfinite", "max_div", "max_speed2"],
+                       "formats": [np.uint64] * 9 + [np.uint32, np.uint32, np.float32, np.float32],
+                       "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 84], "itemsize": 88})
+DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
  F_PRESSURE, F_PCG_B, F_PCG_R, F_PCG_Z, F_PCG_S, F_PCG_Q, F_CELLMASK,
  F_DYE_R, F_DYE_G, F_DYE_B, F_DYE_RTMP, F_DYE_GTMP, F_DYE_BTMP, F_MARKER_KEYS) = range(25)
@@ -86,6 +92,7 @@ EXPORTS = [
     "euler_p2p_export", "euler_p2p_connect", "euler_p2p_disconnect", "euler_p2p_calls", "euler_resident_info",
     "euler_set_option", "euler_get_option",
     "euler_overview", "euler_overview_text", "euler_overview_rgb", "euler_render_fit",
+    "euler_diagnostics", "euler_diag_derive",
 ]
 
 
@@ -160,6 +167,8 @@ def load_library():
         "euler_overview_text": (C.c_int, [vp, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
         "euler_overview_rgb": (C.c_int, [vp, i32, i32, i32, f32, vp, C.c_size_t]),
         "euler_render_fit": (C.c_int, [vp, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
+        "euler_diagnostics": (C.c_int, [vp, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_diag_derive": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -248,6 +257,14 @@ def write_ppm(path, rgb):
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
         f.write(rgb.tobytes())
+
+
+def diag_derive(rec):
+    """An euler_diag record (DIAG_DTYPE) -> the dict of euler_diag_derive's doubles (host only)."""
+    rec = np.ascontiguousarray(rec, DIAG_DTYPE).reshape(1)
+    out = np.zeros(len(DIAG_VALUES), np.float64)
+    _check(load_library().euler_diag_derive(rec.ctypes.data, out.ctypes.data))
+    return dict(zip(DIAG_VALUES, (float(x) for x in out)))
 
 
 SNAPSHOT_F32 = ("u", "v", "utmp", "vtmp")
@@ -396,6 +413,21 @@ class Simulation:
         buf = C.create_string_buffer(max(n.value, 1))
         _check(self.L.euler_render_fit(self.h, wx, wy, buf, n.value, C.byref(n)))
         return buf.raw[: n.value]
+
+    def diagnostics_record(self, box=None):
+        """euler_diagnostics over box = (x0, y0, x1, y1), inclusive (None: the whole interior): one record of DIAG_DTYPE, shape ()."""
+        x0, y0, x1, y1 = (1, 1, self.X - 2, self.Y - 2) if box is None else box
+        rec = np.zeros((), DIAG_DTYPE)
+        _check(self.L.euler_diagnostics(self.h, int(x0), int(y0), int(x1), int(y1), rec.ctypes.data, rec.nbytes))
+        return rec
+
+    def diagnostics(self, box=None):
+        """Residual divergence, kinetic energy, mass and marker crowding of a box of cells, reduced on the device (docs/diagnostics.md):
+        a dict of the record's fields (include/euler.h euler_diag) plus the derived values of euler_diag_derive."""
+        rec = self.diagnostics_record(box)
+        out = {n: (float(rec[n]) if n in ("max_div", "max_speed2") else int(rec[n])) for n in DIAG_DTYPE.names}
+        out.update(diag_derive(rec))
+        return out
 
     def colorize(self):
         """The reference's 'r' key (main.c:970-973): colour the current fluid afresh."""

@@ -11,13 +11,15 @@
  *
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit]
- *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] <scenario>
+ *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
  * one glyph per cell of the window's corner.  --ppm writes PREFIX%06d.ppm (binary P6) of the whole interior after every N-th frame (default 1;
  * frame 0 included), WxH boxes (default: the interior divided by the smallest integer that brings both sides to <= 1024), coloured by
  * coverage, by the dye (the default with --rainbow) or by speed (blue = 0 ... red = SCALE cells per second and above).
+ * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
+ * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
  */
 #include <errno.h>
 #include <signal.h>
@@ -34,7 +36,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] <scenario>\n", argv0);
+                  "[--fit] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -100,6 +102,23 @@ static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, int W,
   return ok ? 0 : -1;
 }
 
+/* ---- --stats: one CSV line per frame (euler_get_stats + euler_diagnostics of the whole interior + euler_diag_derive) ---------------- */
+static const char k_stats_header[] = "frame,substeps,pcg_iterations,residual,fluid,markers,count_max,crowded,max_div,mean_abs_div,kinetic_energy,com_x,com_y,nonfinite\n";
+static int write_stats_line(euler_sim* sim, FILE* out, const char* path, int frame, int X, int Y) {
+  euler_stats st;
+  euler_diag d;
+  euler_diag_values v;
+  if (euler_get_stats(sim, &st) != EULER_OK || euler_diagnostics(sim, 1, 1, X - 2, Y - 2, &d, sizeof d) != EULER_OK || euler_diag_derive(&d, &v) != EULER_OK) {
+    fprintf(stderr, "%s\n", euler_last_error());
+    return -1;
+  }
+  const int ok = fprintf(out, "%d,%d,%d,%.9g,%llu,%llu,%u,%llu,%.9g,%.9g,%.9g,%.9g,%.9g,%u\n", frame, (int)st.last_substeps, (int)st.last_pcg_iterations, st.last_residual,
+                         (unsigned long long)d.fluid, (unsigned long long)d.markers, (unsigned)d.count_max, (unsigned long long)d.crowded, (double)d.max_div, v.mean_abs_div,
+                         v.kinetic_energy, v.com_x, v.com_y, (unsigned)d.nonfinite) > 0 && fflush(out) == 0;
+  if (!ok) fprintf(stderr, "--stats: cannot write %s: %s\n", path, strerror(errno));
+  return ok ? 0 : -1;
+}
+
 /* ---- the reference's loop state (main.c:85-88) ----------------------------------------------- */
 typedef struct app {
   euler_sim* sim;
@@ -136,6 +155,8 @@ int main(int argc, char** argv) {
   int fit = 0, ppm_w = 0, ppm_h = 0, ppm_every = 1, ppm_mode = -1;
   float ppm_scale = 1.f;
   const char* ppm = NULL;
+  const char* stats = NULL;
+  int stats_every = 1;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -182,6 +203,9 @@ int main(int argc, char** argv) {
       else if (sscanf(v, "speed:%f%c", &ppm_scale, &tail) == 1 && ppm_scale > 0.f) ppm_mode = EULER_IMAGE_SPEED;
       else { usage(argv[0]); return 1; }
     }
+    /* the flow diagnostics as CSV (docs/diagnostics.md) */
+    else if (!strcmp(argv[i], "--stats") && i + 1 < argc) stats = argv[++i];
+    else if (!strcmp(argv[i], "--stats-every") && i + 1 < argc) { stats_every = atoi(argv[++i]); if (stats_every < 1) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
@@ -223,13 +247,18 @@ int main(int argc, char** argv) {
     if (enable_raw_mode() == -1) { perror("failed to enable raw mode"); return 1; }
     write_all("\x1b[2J\x1b[H", 7);      /* clear_screen_now */
   }
+  FILE* stats_file = NULL;
+  int rc_exit = 0;
+  if (stats) {
+    stats_file = fopen(stats, "w");
+    if (!stats_file || fputs(k_stats_header, stats_file) < 0 || fflush(stats_file) != 0) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
+  }
   int32_t cap = 0;
   char* buf = NULL;
   struct timespec next;
   clock_gettime(CLOCK_MONOTONIC, &next);
   size_t key_pos = 0;
-  int rc_exit = 0;
-  for (int f = 0; frames < 0 || f <= frames; ++f) {
+  for (int f = 0; !rc_exit && (frames < 0 || f <= frames); ++f) {
     if (f > 0) {
       /* one key per frame: a scripted one (--keys) or whatever the terminal has (non-blocking read) */
       char c = '\0';
@@ -270,8 +299,10 @@ int main(int argc, char** argv) {
       write_all("\x1b[?25l", 6);           /* hide cursor */
     }
     if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, ppm_w, ppm_h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
+    if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }
+  if (stats_file && fclose(stats_file) != 0 && !rc_exit) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }
   euler_stats st;
   if (euler_get_stats(app.sim, &st) == EULER_OK)

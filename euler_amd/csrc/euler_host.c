@@ -1,7 +1,7 @@
 /*
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
  * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
- * whole-domain overview's records (text through the same frame formatter, RGB).
+ * whole-domain overview's records (text through the same frame formatter, RGB), and the values derived from a diagnostics record.
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -357,5 +357,21 @@ int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_
       rgb[3 * i + c] = (uint8_t)(((uint64_t)r->solid * 128 + (uint64_t)r->sink * 64 + (uint64_t)r->water * (uint64_t)wc[c] + cells / 2) / cells);
     }
   }
+  return EULER_OK;
+}
+
+/* ---- flow diagnostics: what a user reads off an euler_diag record (include/euler.h, docs/diagnostics.md) ---- */
+
+int euler_diag_derive(const euler_diag* rec, euler_diag_values* out) {
+  if (!rec || !out) return EULER_EINVAL;
+  memset(out, 0, sizeof *out);
+  if (!rec->fluid) return EULER_OK;
+  const double fluid = (double)rec->fluid, markers = (double)rec->markers;      /* (markers >= fluid > 0) */
+  out->mean_abs_div = (double)rec->div_l1 / 16777216.0 / fluid;
+  out->kinetic_energy = 0.5 * ((double)rec->ke_hi + (double)rec->ke_lo / 4294967296.0);
+  out->com_x = (double)rec->mass_x / markers;
+  out->com_y = (double)rec->mass_y / markers;
+  out->markers_per_cell = markers / fluid;
+  out->crowded_fraction = (double)rec->crowded / fluid;
   return EULER_OK;
 }

@@ -349,6 +349,48 @@ int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_
  * with euler_config.rainbow).  Sizing protocol of euler_render; wx < 1 or wy < 1: EULER_EINVAL. */
 int euler_render_fit(euler_sim* sim, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len);
 
+/* ---- flow diagnostics (docs/diagnostics.md) ------------------------------------------------------ */
+/* How good is a frame?  One pass ON THE DEVICE over a box of interior cells [x0, x1] x [y0, y1] (inclusive) reduces u, v, count and solid to the
+ * record below; only its 88 bytes cross to the host.  A FLUID cell is the reference's is_fluid on a non-solid cell: count > 0 && !solid.  Per fluid
+ * cell i = y * X + x, in float32 without contraction:
+ *   d  = ((u[i] - u[i-1]) + v[i]) - v[i-X]            the divergence the velocity update left behind (main.c:720 in its order, h = 1)
+ *   s2 = dx*dx + dy*dy, dx = (u[i] + u[i-1]) / 2, dy = (v[i] + v[i-X]) / 2      the cell-centre speed squared (euler_overview_px.max_speed2)
+ *   qd(a) = (uint64_t)((a < 256 ? a : 256) * 16777216.f)              2^-24 units, saturating at 256
+ *   qk(s) = (uint64_t)((s < 16777216.f ? s : 16777216.f) * 4294967296.f)    2^-32 units, saturating at 2^24
+ * Both scales are powers of two: the multiply is exact, the conversion truncates - the same on host and device.  d and s2 are judged separately:
+ * a NaN d adds nothing to div_l1 / max_div, a NaN s2 nothing to ke_* / max_speed2, and a cell with either counts ONCE in nonfinite; an infinity
+ * saturates its sum and shows in its maximum.  The maxima are taken on the unsigned bit patterns of the non-negative floats.  Every field is an
+ * integer sum or such a maximum, so the record does not depend on the launch geometry (tests compare bits).  No sum can wrap: a whole-grid handle
+ * has at most 2^28 cells, a term is at most 2^32 (qd, the low half of qk), 2^24 (the high half) or 255 * 2^25 (count * x): every sum stays below 2^61. */
+enum { EULER_DIAG_CROWDED = 8 };   /* a cell counts as crowded from this many markers on: twice the seeding density of 4 (main.c:255-266); the uint8 count wraps at 256 */
+typedef struct euler_diag {      /* 88 bytes, no padding */
+  uint64_t cells;      /* cells of the box */
+  uint64_t fluid;      /* cells with count > 0 && !solid */
+  uint64_t markers;    /* sum of count over the fluid cells */
+  uint64_t crowded;    /* fluid cells with count >= EULER_DIAG_CROWDED */
+  uint64_t mass_x;     /* sum of count * x over the fluid cells */
+  uint64_t mass_y;     /* sum of count * y */
+  uint64_t div_l1;     /* sum of qd(|d|) */
+  uint64_t ke_hi, ke_lo; /* sums of qk(s2) >> 32 and qk(s2) & 0xffffffff */
+  uint32_t count_max;  /* max count over the fluid cells */
+  uint32_t nonfinite;  /* fluid cells whose d or s2 is a NaN (counted once) */
+  float    max_div;    /* max |d| */
+  float    max_speed2; /* max s2 */
+} euler_diag;
+typedef struct euler_diag_values {   /* what a user reads off a record; all 0 when fluid == 0 */
+  double mean_abs_div;      /* div_l1 / 2^24 / fluid */
+  double kinetic_energy;    /* 0.5 * (ke_hi + ke_lo / 2^32): density 1, cell volume 1 */
+  double com_x, com_y;      /* mass_x / markers, mass_y / markers: the markers' centre of mass in cell indices */
+  double markers_per_cell;  /* markers / fluid */
+  double crowded_fraction;  /* crowded / fluid */
+} euler_diag_values;
+/* The box must lie in the interior, 1 <= x0 <= x1 <= X - 2 and 1 <= y0 <= y1 <= Y - 2, and out_bytes must be sizeof(euler_diag): else EULER_EINVAL.
+ * EULER_ESTATE without a loaded state and on a row-slab handle (summing the records across ranks is a follow-up).  One launch on the handle's stream
+ * that only READS u, v, count, solid and the tile map: stepping afterwards gives the bits of a run that never called it.  The 88-byte device record
+ * comes with the first call (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy. */
+int euler_diagnostics(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, euler_diag* out, size_t out_bytes);
+int euler_diag_derive(const euler_diag* rec, euler_diag_values* out);   /* host only, no GPU */
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
