@@ -93,6 +93,7 @@ EXPORTS = [
     "euler_set_option", "euler_get_option",
     "euler_overview", "euler_overview_text", "euler_overview_rgb", "euler_render_fit",
     "euler_diagnostics", "euler_diag_derive",
+    "euler_overview_box", "euler_marker_raster", "euler_view_text", "euler_render_view",
 ]
 
 
@@ -169,6 +170,10 @@ def load_library():
         "euler_render_fit": (C.c_int, [vp, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
         "euler_diagnostics": (C.c_int, [vp, i32, i32, i32, i32, vp, C.c_size_t]),
         "euler_diag_derive": (C.c_int, [vp, vp]),
+        "euler_overview_box": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_marker_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_view_text": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
+        "euler_render_view": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -247,6 +252,22 @@ def overview_rgb(px, mode=IMAGE_COVERAGE, speed_scale=1.0):
     rgb = np.empty((h, w, 3), np.uint8)
     _check(load_library().euler_overview_rgb(px.ctypes.data, w, h, int(mode), float(speed_scale), rgb.ctypes.data, rgb.nbytes))
     return rgb
+
+
+def view_text(cells, raster, scale, rainbow=False):
+    """The magnified frame of a box (euler_view_text): cells = its overview at one cell per record, shape (bh, bw); raster = the marker counts of
+    euler_marker_raster over the same box, shape (bh * scale, bw * scale); every cell becomes scale x scale glyphs."""
+    cells = _overview_records(cells)
+    bh, bw = cells.shape
+    raster = np.ascontiguousarray(raster, np.uint32)
+    if raster.shape != (bh * int(scale), bw * int(scale)):
+        raise ValueError("view_text: a raster of shape (%d, %d)" % (bh * int(scale), bw * int(scale)))
+    L = load_library()
+    n = C.c_int32(0)
+    _check(L.euler_view_text(cells.ctypes.data, raster.ctypes.data, bw, bh, int(scale), int(rainbow), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    _check(L.euler_view_text(cells.ctypes.data, raster.ctypes.data, bw, bh, int(scale), int(rainbow), buf, n.value, C.byref(n)))
+    return buf.raw[: n.value]
 
 
 def write_ppm(path, rgb):
@@ -400,11 +421,34 @@ class Simulation:
         _check(self.L.euler_render(self.h, wx, wy, buf, n.value, C.byref(n)))
         return buf.raw[: n.value]
 
-    def overview(self, w, h):
-        """The whole interior reduced on the device to h x w boxes of cells (euler_overview): an array of OVERVIEW_DTYPE, shape (h, w), row 0 = top."""
+    def overview(self, w, h, box=None):
+        """The whole interior, or box = (x0, y0, x1, y1) inclusive (euler_overview_box), reduced on the device to h x w boxes of cells
+        (euler_overview): an array of OVERVIEW_DTYPE, shape (h, w), row 0 = top."""
         px = np.zeros((max(int(h), 0), max(int(w), 0)), OVERVIEW_DTYPE)
-        _check(self.L.euler_overview(self.h, w, h, px.ctypes.data if px.size else np.zeros(1, OVERVIEW_DTYPE).ctypes.data, px.nbytes))
+        dst = px.ctypes.data if px.size else np.zeros(1, OVERVIEW_DTYPE).ctypes.data
+        if box is None:
+            _check(self.L.euler_overview(self.h, w, h, dst, px.nbytes))
+        else:
+            _check(self.L.euler_overview_box(self.h, *(int(t) for t in box), w, h, dst, px.nbytes))
         return px
+
+    def marker_raster(self, box, scale):
+        """The markers of box = (x0, y0, x1, y1) counted on the device into scale x scale sub-pixels per cell (euler_marker_raster):
+        uint32, shape (bh * scale, bw * scale), row 0 = top."""
+        x0, y0, x1, y1 = (int(t) for t in box)
+        out = np.zeros((max(y1 - y0 + 1, 0) * max(int(scale), 0), max(x1 - x0 + 1, 0) * max(int(scale), 0)), np.uint32)
+        _check(self.L.euler_marker_raster(self.h, x0, y0, x1, y1, int(scale), out.ctypes.data if out.size else np.zeros(1, np.uint32).ctypes.data, out.nbytes))
+        return out
+
+    def render_view(self, box, wx, wy):
+        """The frame of box = (x0, y0, x1, y1) in a window of wx x wy glyphs (euler_render_view): boxes of cells below one cell per glyph,
+        the markers' raster above."""
+        b = [int(t) for t in box]
+        n = C.c_int32(0)
+        _check(self.L.euler_render_view(self.h, *b, wx, wy, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        _check(self.L.euler_render_view(self.h, *b, wx, wy, buf, n.value, C.byref(n)))
+        return buf.raw[: n.value]
 
     def render_fit(self, wx, wy):
         """draw() of the WHOLE interior fitted into wx x wy glyphs (euler_render_fit)."""

@@ -10,7 +10,7 @@
  * handler one character per frame ('.' = no key) so that the gate is testable without a tty.
  *
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
- *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit]
+ *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1]
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
@@ -18,6 +18,11 @@
  * one glyph per cell of the window's corner.  --ppm writes PREFIX%06d.ppm (binary P6) of the whole interior after every N-th frame (default 1;
  * frame 0 included), WxH boxes (default: the interior divided by the smallest integer that brings both sides to <= 1024), coloured by
  * coverage, by the dye (the default with --rainbow) or by speed (blue = 0 ... red = SCALE cells per second and above).
+ * --view draws the box of interior cells [X0, X1] x [Y0, Y1] fitted into the window (euler_render_view, docs/viewport.md): boxes of cells where the box is
+ * larger than the window, the markers' raster at 2 ... 16 glyphs per cell where the window holds it at least twice.  With it, and only with it, the keys
+ * h j k l pan left / down / up / right by a quarter of the box (clamped to the interior), + halves the box about its centre (never below 4 x 4 cells),
+ * - doubles it (clamped) and 0 shows the whole interior; --ppm then shows the box (--ppm-size clamped to it, the default divisor rule applied to it).
+ * --fit --view is a usage error.
  * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
  * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
  */
@@ -36,7 +41,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -79,15 +84,15 @@ static int window_size(int* wx, int* wy) {
   return 0;
 }
 
-/* ---- --ppm: the whole interior as a binary PPM (euler_overview + euler_overview_rgb) ---------------- */
-static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, int W, int H, int mode, float scale) {
+/* ---- --ppm: the whole interior, or the box of --view, as a binary PPM (euler_overview / euler_overview_box + euler_overview_rgb) ---------------- */
+static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const int* box, int W, int H, int mode, float scale) {
   const size_t n = (size_t)W * (size_t)H;
   euler_overview_px* px = (euler_overview_px*)malloc(n * sizeof *px);
   uint8_t* rgb = (uint8_t*)malloc(n * 3);
   char* path = (char*)malloc(strlen(prefix) + 32);
   int ok = px && rgb && path;
   if (!ok) fprintf(stderr, "--ppm: out of memory\n");
-  if (ok && (euler_overview(sim, W, H, px, n * sizeof *px) != EULER_OK || euler_overview_rgb(px, W, H, mode, scale, rgb, n * 3) != EULER_OK)) {
+  if (ok && ((box ? euler_overview_box(sim, box[0], box[1], box[2], box[3], W, H, px, n * sizeof *px) : euler_overview(sim, W, H, px, n * sizeof *px)) != EULER_OK || euler_overview_rgb(px, W, H, mode, scale, rgb, n * 3) != EULER_OK)) {
     fprintf(stderr, "%s\n", euler_last_error());
     ok = 0;
   }
@@ -125,7 +130,36 @@ typedef struct app {
   int pause;                    /* g_pause */
   unsigned temp_unpause;        /* g_temp_unpause_counter */
   int rainbow;
+  int view;                     /* --view: the box below is drawn and the pan / zoom keys act on it */
+  int box[4];                   /* x0, y0, x1, y1, inclusive, inside the interior */
+  int xi, yi;                   /* the interior: X - 2, Y - 2 */
 } app_t;
+
+/* --view's keys: pan by a quarter of the box, halve / double it about its centre, all clamped to the interior [1, xi] x [1, yi] */
+static void zoom_axis(int* lo, int* hi, int limit, int nw) {
+  const int w = *hi - *lo + 1;
+  int l = nw < w ? *lo + (w - nw) / 2 : *lo - (nw - w) / 2;
+  if (l < 1) l = 1;
+  if (l + nw - 1 > limit) l = limit - nw + 1;
+  *lo = l; *hi = l + nw - 1;
+}
+static void view_key(app_t* a, char c) {
+  int* b = a->box;
+  const int bw = b[2] - b[0] + 1, bh = b[3] - b[1] + 1;
+  const int dx = bw / 4 > 1 ? bw / 4 : 1, dy = bh / 4 > 1 ? bh / 4 : 1;
+  int s;
+  if (c == 'h') { s = dx < b[0] - 1 ? dx : b[0] - 1; b[0] -= s; b[2] -= s; }
+  else if (c == 'l') { s = dx < a->xi - b[2] ? dx : a->xi - b[2]; b[0] += s; b[2] += s; }
+  else if (c == 'j') { s = dy < b[1] - 1 ? dy : b[1] - 1; b[1] -= s; b[3] -= s; }
+  else if (c == 'k') { s = dy < a->yi - b[3] ? dy : a->yi - b[3]; b[1] += s; b[3] += s; }
+  else if (c == '+') {
+    zoom_axis(&b[0], &b[2], a->xi, bw / 2 >= 4 ? bw / 2 : (bw < 4 ? bw : 4));
+    zoom_axis(&b[1], &b[3], a->yi, bh / 2 >= 4 ? bh / 2 : (bh < 4 ? bh : 4));
+  } else if (c == '-') {
+    zoom_axis(&b[0], &b[2], a->xi, 2 * bw < a->xi ? 2 * bw : a->xi);
+    zoom_axis(&b[1], &b[3], a->yi, 2 * bh < a->yi ? 2 * bh : a->yi);
+  } else if (c == '0') { b[0] = 1; b[1] = 1; b[2] = a->xi; b[3] = a->yi; }
+}
 
 /* process_keypress (main.c:961-980); returns 0 on 'q' */
 static int handle_key(app_t* a, char c) {
@@ -133,6 +167,7 @@ static int handle_key(app_t* a, char c) {
   else if (c == 'f') a->temp_unpause++;
   else if (c == 'r') { if (a->rainbow && euler_colorize(a->sim) != EULER_OK) fprintf(stderr, "%s\n", euler_last_error()); }
   else if (c == 'q') return 0;
+  else if (a->view) view_key(a, c);
   return 1;
 }
 
@@ -157,6 +192,7 @@ int main(int argc, char** argv) {
   const char* ppm = NULL;
   const char* stats = NULL;
   int stats_every = 1;
+  int view = 0, vbox[4] = {0, 0, 0, 0};
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -192,6 +228,12 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--maccormack")) maccormack = 1;
     /* the whole-domain overview (docs/overview.md) */
     else if (!strcmp(argv[i], "--fit")) fit = 1;
+    /* the pan-and-zoom viewport (docs/viewport.md) */
+    else if (!strcmp(argv[i], "--view") && i + 1 < argc) {
+      char tail;
+      if (sscanf(argv[++i], "%d,%d,%d,%d%c", &vbox[0], &vbox[1], &vbox[2], &vbox[3], &tail) != 4) { usage(argv[0]); return 1; }
+      view = 1;
+    }
     else if (!strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
     else if (!strcmp(argv[i], "--ppm-size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &ppm_w, &ppm_h) != 2 || ppm_w < 1 || ppm_h < 1) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--ppm-every") && i + 1 < argc) { ppm_every = atoi(argv[++i]); if (ppm_every < 1) { usage(argv[0]); return 1; } }
@@ -212,7 +254,11 @@ int main(int argc, char** argv) {
   }
   if (!scenario && !resume) { usage(argv[0]); return 1; }                                                       /* main.c:986-989 */
 
-  if (ppm) {
+  if (view && (fit || vbox[0] < 1 || vbox[1] < 1 || vbox[2] > cfg.X - 2 || vbox[3] > cfg.Y - 2 || vbox[0] > vbox[2] || vbox[1] > vbox[3])) { usage(argv[0]); return 1; }
+  const int ppm_size_given = ppm_w > 0;
+  if (ppm && view) {      /* the size follows the box frame by frame (below) */
+    if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
+  } else if (ppm) {
     const int xi = cfg.X - 2, yi = cfg.Y - 2;
     if (!ppm_w) {      /* the interior divided by the smallest integer that brings both sides to <= 1024 */
       int d = 1;
@@ -237,6 +283,8 @@ int main(int argc, char** argv) {
   app_t app;
   memset(&app, 0, sizeof app);
   app.rainbow = cfg.rainbow;
+  app.view = view; app.xi = cfg.X - 2; app.yi = cfg.Y - 2;
+  memcpy(app.box, vbox, sizeof vbox);
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK) {
@@ -280,14 +328,16 @@ int main(int argc, char** argv) {
       if (window_size(&wx, &wy) == 0) write_all("\x1b[2J\x1b[H", 7);
     }
     int32_t len = 0;
-    if (render(app.sim, wx, wy, NULL, 0, &len) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    const int* b = app.box;
+#define RENDER(out, cap) (view ? euler_render_view(app.sim, b[0], b[1], b[2], b[3], wx, wy, (out), (cap), &len) : render(app.sim, wx, wy, (out), (cap), &len))
+    if (RENDER(NULL, 0) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
     if (len > cap) {
       cap = len + 4096;
       char* nb = (char*)realloc(buf, (size_t)cap);
       if (!nb) { rc_exit = 1; break; }
       buf = nb;
     }
-    if (render(app.sim, wx, wy, buf, cap, &len) != EULER_OK || len > cap) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    if (RENDER(buf, cap) != EULER_OK || len > cap) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
     if (dump) {
       printf("--- frame %d (%d bytes)\n", f, (int)len);
       fwrite(buf, 1, (size_t)len, stdout);
@@ -298,7 +348,17 @@ int main(int argc, char** argv) {
       write_all(buf, (size_t)len);
       write_all("\x1b[?25l", 6);           /* hide cursor */
     }
-    if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, ppm_w, ppm_h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
+#undef RENDER
+    if (ppm && view && f % ppm_every == 0) {      /* the box as it stands: --ppm-size clamped to it, else the divisor rule of the whole interior applied to it */
+      const int bw = b[2] - b[0] + 1, bh = b[3] - b[1] + 1;
+      int w = ppm_w < bw ? ppm_w : bw, h = ppm_h < bh ? ppm_h : bh;
+      if (!ppm_size_given) {
+        int d = 1;
+        while (bw / d > 1024 || bh / d > 1024) ++d;
+        w = bw / d > 1 ? bw / d : 1; h = bh / d > 1 ? bh / d : 1;
+      }
+      if (write_ppm_frame(app.sim, ppm, f, b, w, h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
+    } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, ppm_w, ppm_h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
     if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }

@@ -163,6 +163,7 @@ struct euler_sim {
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
   euler_overview_px* ov_buf; size_t ov_cap;   // euler_overview (k_overview.hip): the records on the device, room for ov_cap of them; allocated by the first call, grown on demand
   euler_diag* diag_buf;   // euler_diagnostics (k_diagnostics.hip): the record on the device; allocated by the first call
+  unsigned int* vr_buf; size_t vr_cap;   // euler_marker_raster (k_viewport.hip): the raster on the device, room for vr_cap pixels; allocated by the first call, grown on demand
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -401,6 +402,7 @@ int eu_ordered_select(euler_sim* S, const unsigned long long* mask, size_t nword
 int eu_sync_marker_state(euler_sim* S);
 void eu_overview_release(euler_sim* S);   // k_overview.hip
 void eu_diagnostics_release(euler_sim* S);   // k_diagnostics.hip
+void eu_viewport_release(euler_sim* S);   // k_viewport.hip
 void eu_rccl_release(euler_sim* S);   // comm_rccl.hip
 void eu_p2p_release(euler_sim* S);    // comm_p2p.hip
 int eu_p2p_halo_skewed(euler_sim* S, double* s_skewed);   // ghost rows of a band-skewed vector, straight from / into the array

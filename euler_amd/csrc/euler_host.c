@@ -1,7 +1,7 @@
 /*
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
  * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
- * whole-domain overview's records (text through the same frame formatter, RGB), and the values derived from a diagnostics record.
+ * whole-domain overview's records (text through the same frame formatter, RGB), the magnified frame of the viewport, and the values derived from a diagnostics record.
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -329,6 +329,41 @@ int euler_overview_text(const euler_overview_px* px, int32_t W, int32_t H, int32
       else if (k == OV_SINK) g[C + i] = 1;
       else g[2 * C + i] = (uint8_t)k;
       if (col) for (int c = 0; c < 3; ++c) col[c * C + i] = overview_mean_dye(r, c);
+    }
+  int rc = render_rows(g, g + C, g + 2 * C, col, col ? col + C : NULL, col ? col + 2 * C : NULL, X, Y, W, H, out, cap, len);
+  free(g);
+  free(col);
+  return rc;
+}
+
+/* ---- pan-and-zoom viewport: the magnified frame (include/euler.h, docs/viewport.md) ---- */
+
+int euler_view_text(const euler_overview_px* cells, const uint32_t* raster, int32_t Bw, int32_t Bh,
+                    int32_t scale, int32_t rainbow, char* out, int32_t cap, int32_t* len) {
+  if (!cells || !raster || !len || Bw < 1 || Bh < 1) return EULER_EINVAL;
+  if (scale != 1 && scale != 2 && scale != 4 && scale != 8 && scale != 16) return EULER_EINVAL;
+  if ((int64_t)Bw * scale * ((int64_t)Bh * scale) > (1 << 24)) return EULER_EINVAL;
+  /* as euler_overview_text: a (W + 2) x (H + 2) grid with a border ring that is never drawn, scale x scale sub-pixels per cell */
+  const int32_t W = Bw * scale, H = Bh * scale, X = W + 2, Y = H + 2;
+  const size_t C = (size_t)X * (size_t)Y;
+  uint8_t* g = (uint8_t*)calloc(3, C);
+  float* col = rainbow ? (float*)calloc(3 * C, sizeof(float)) : NULL;
+  if (!g || (rainbow && !col)) { free(g); free(col); return EULER_ENOMEM; }
+  for (int32_t cy = 0; cy < Bh; ++cy)
+    for (int32_t cx = 0; cx < Bw; ++cx) {
+      const euler_overview_px* r = cells + (size_t)cy * Bw + cx;
+      const int k = overview_class(r);
+      float dye[3] = {0.f, 0.f, 0.f};
+      if (col) for (int c = 0; c < 3; ++c) dye[c] = overview_mean_dye(r, c);
+      for (int32_t sy = 0; sy < scale; ++sy)
+        for (int32_t sx = 0; sx < scale; ++sx) {
+          const int32_t py = cy * scale + sy, p = cx * scale + sx;
+          const size_t i = (size_t)(H - py) * X + (size_t)(p + 1);      /* raster row 0 is the top: grid row Y - 2 */
+          if (k == OV_SOLID) g[i] = 1;
+          else if (k == OV_SINK) g[C + i] = 1;
+          else { const uint32_t n = raster[(size_t)py * W + p]; g[2 * C + i] = (uint8_t)(n < 3 ? n : 3); }
+          if (col) for (int c = 0; c < 3; ++c) col[c * C + i] = dye[c];
+        }
     }
   int rc = render_rows(g, g + C, g + 2 * C, col, col ? col + C : NULL, col ? col + 2 * C : NULL, X, Y, W, H, out, cap, len);
   free(g);

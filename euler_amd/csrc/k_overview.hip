@@ -1,5 +1,5 @@
-// k_overview.hip — euler_overview (include/euler.h, docs/overview.md): the whole interior reduced on the device to a W x H raster of
-// euler_overview_px records, one box of cells per record.  Every field of a record is an integer sum or a maximum of non-negative
+// k_overview.hip — euler_overview / euler_overview_box (include/euler.h, docs/overview.md, docs/viewport.md): a box of interior cells - the whole
+// interior for euler_overview - reduced on the device to a W x H raster of euler_overview_px records, one box of cells per record.  Every field of a record is an integer sum or a maximum of non-negative
 // floats (compared as unsigned bit patterns): whatever order the cells arrive in, the record is the same.
 //
 // One launch.  A workgroup owns a run of WHOLE pixel boxes of one pixel row - npc <= OV_NPC pixel columns, about OV_SPAN cells wide -
@@ -25,6 +25,7 @@ struct OvArgs {
   const uint8_t* tmap;      // null: every tile is read whole
   int tnx;
   int X, Y, W, H, npc, nsplit;
+  int bx0, by1, Bw, Bh;     // the box: its left column, its top row, its extent in cells (the whole interior: 1, Y - 2, X - 2, Y - 2)
   euler_overview_px* out;
 };
 
@@ -85,12 +86,12 @@ template <int VEC, bool DYE>
 __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   __shared__ OvTable tab;
   const int tid = threadIdx.x;
-  const unsigned int Xi = (unsigned int)(a.X - 2), Yi = (unsigned int)(a.Y - 2);
+  const unsigned int Xi = (unsigned int)a.Bw, Yi = (unsigned int)a.Bh;
   const unsigned int groups = (unsigned int)((a.W + a.npc - 1) / a.npc), slice = blockIdx.x / groups;      // (neighbouring workgroups lie along a row)
   const int p0 = (int)(blockIdx.x % groups) * a.npc, p1 = p0 + a.npc < a.W ? p0 + a.npc : a.W;      // this workgroup's pixel columns [p0, p1)
   const int py = (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
-  const int xa = 1 + (int)((unsigned long long)p0 * Xi / (unsigned int)a.W), xb = (int)((unsigned long long)p1 * Xi / (unsigned int)a.W);      // its columns [xa, xb]
-  const int ytop = a.Y - 2 - (int)((unsigned long long)py * Yi / (unsigned int)a.H), ybot = a.Y - 1 - (int)((unsigned long long)(py + 1) * Yi / (unsigned int)a.H);
+  const int xa = a.bx0 + (int)((unsigned long long)p0 * Xi / (unsigned int)a.W), xb = a.bx0 - 1 + (int)((unsigned long long)p1 * Xi / (unsigned int)a.W);      // its columns [xa, xb]
+  const int ytop = a.by1 - (int)((unsigned long long)py * Yi / (unsigned int)a.H), ybot = a.by1 + 1 - (int)((unsigned long long)(py + 1) * Yi / (unsigned int)a.H);
   const int nrows = ytop - ybot + 1;
   const int yhi = ytop - (int)((long long)sp * nrows / a.nsplit), ylo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows yhi down to ylo
   for (int k = tid; k < OV_NPC; k += OV_T) {
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   }
   __syncthreads();
   const size_t X = (size_t)a.X;
-  const int xbase = VEC == 4 ? (xa & ~3) : xa;
+  const int xbase = VEC == 4 ? (xa & ~3) : xa;      // (lane groups stay aligned to ABSOLUTE x & ~3 whatever the box: the cells an edge cuts are masked below)
   // (the trip count is the same for the lanes of a wave up to the last pass: the shuffles below run behind a wave-uniform test)
   for (int xc = xbase; xc <= xb; xc += OV_T * VEC) {
     const int x0 = xc + tid * VEC;
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       const int x = x0 + k;
-      pk[k] = x >= xa && x <= xb ? (int)(((unsigned long long)x * (unsigned int)a.W - 1ull) / Xi) - p0 : -1;      // the column px whose range holds x
+      pk[k] = x >= xa && x <= xb ? (int)(((unsigned long long)(x - a.bx0 + 1) * (unsigned int)a.W - 1ull) / Xi) - p0 : -1;      // the column px whose range holds x
       if (pk[k] >= 0) { pmin = pk[k] < pmin ? pk[k] : pmin; pmax = pk[k] > pmax ? pk[k] : pmax; }
     }
     const int wmin = ov_wave_min(pmin), wmax = -ov_wave_min(-pmax);
@@ -239,13 +240,14 @@ static int ov_reserve(euler_sim* S, size_t n) {
 }
 
 // the reduction alone, on the handle's stream, into S->ov_buf (tools/overview_cost.py times it through the KC_MISC class)
-static int ov_launch(euler_sim* S, int W, int H) {
-  const int Xi = S->X - 2, Yi = S->Y - 2;
+static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H) {
+  const int Xi = x1 - x0 + 1, Yi = y1 - y0 + 1;      // (the box's extent: npc and nsplit follow it)
   OvArgs a;
   a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
   for (int c = 0; c < 3; ++c) a.dye[c] = S->dye[c];
   a.tmap = eu_tile_map_on(S) ? S->tmap : nullptr; a.tnx = S->tmap_nx;
   a.X = S->X; a.Y = S->Y; a.W = W; a.H = H; a.out = S->ov_buf;
+  a.bx0 = x0; a.by1 = y1; a.Bw = Xi; a.Bh = Yi;
   long long npc = (long long)OV_SPAN * W / Xi;      // pixel columns per workgroup: about OV_SPAN cells wide, at least one box, at most the table
   a.npc = (int)(npc < 1 ? 1 : (npc > OV_NPC ? OV_NPC : npc));
   const long long span = ((long long)a.npc * Xi + W - 1) / W, rows_max = (Yi + H - 1) / H, rows_min = Yi / H;
@@ -263,19 +265,33 @@ static int ov_launch(euler_sim* S, int W, int H) {
   return EULER_OK;
 }
 
-extern "C" int euler_overview(euler_sim* S, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes) {
-  if (!S || !out) { eu_set_error("euler_overview: null argument"); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("euler_overview: not on a row-slab handle (a box of cells straddles slabs)"); return EULER_ESTATE; }
-  if (!S->loaded) { eu_set_error("euler_overview: no scenario loaded"); return EULER_ESTATE; }
-  if (W < 1 || H < 1 || W > S->X - 2 || H > S->Y - 2) { eu_set_error("euler_overview: a raster of %d x %d for an interior of %d x %d cells", (int)W, (int)H, S->X - 2, S->Y - 2); return EULER_EINVAL; }
+// the call behind euler_overview (the whole interior) and euler_overview_box
+static int ov_call(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes) {
+  if (!S || !out) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
+  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (a box of cells straddles slabs)", who); return EULER_ESTATE; }
+  if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
+  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
+    eu_set_error("%s: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", who, x0, x1, y0, y1, S->X - 2, S->Y - 2);
+    return EULER_EINVAL;
+  }
+  if (W < 1 || H < 1 || W > x1 - x0 + 1 || H > y1 - y0 + 1) { eu_set_error("%s: a raster of %d x %d for a box of %d x %d cells", who, W, H, x1 - x0 + 1, y1 - y0 + 1); return EULER_EINVAL; }
   const size_t n = (size_t)W * (size_t)H;
-  if (out_bytes != n * sizeof(euler_overview_px)) { eu_set_error("euler_overview: %zu bytes given, %zu expected", out_bytes, n * sizeof(euler_overview_px)); return EULER_EINVAL; }
+  if (out_bytes != n * sizeof(euler_overview_px)) { eu_set_error("%s: %zu bytes given, %zu expected", who, out_bytes, n * sizeof(euler_overview_px)); return EULER_EINVAL; }
   int rc = ov_reserve(S, n);
-  if (!rc) rc = ov_launch(S, W, H);
+  if (!rc) rc = ov_launch(S, x0, y0, x1, y1, W, H);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, S->ov_buf, out_bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;
+}
+
+extern "C" int euler_overview(euler_sim* S, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes) {
+  if (!S) { eu_set_error("euler_overview: null argument"); return EULER_EINVAL; }
+  return ov_call(S, "euler_overview", 1, 1, S->X - 2, S->Y - 2, W, H, out, out_bytes);
+}
+
+extern "C" int euler_overview_box(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes) {
+  return ov_call(S, "euler_overview_box", x0, y0, x1, y1, W, H, out, out_bytes);
 }
 
 extern "C" int euler_render_fit(euler_sim* S, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {

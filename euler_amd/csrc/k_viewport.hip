@@ -1,0 +1,153 @@
+// k_viewport.hip — euler_marker_raster and euler_render_view (include/euler.h, docs/viewport.md): the markers of a box of cells counted on the
+// device into a raster of scale x scale sub-pixels per cell, and the frame of a box in a window (below one cell per glyph: the box overview of
+// k_overview.hip; above: the raster through euler_view_text).
+//
+// One pass over the marker array, 8 bytes per marker, two markers (one 16-byte load) per lane.  A marker's sub-pixel is
+//   c = floor((m.x - x0) * scale), r = H - 1 - floor((m.y - y0) * scale):
+// inside the box the subtraction is exact (positions below 2^24, x0 an integer <= m.x) and so is the multiplication by a power of two; outside
+// it the rounded difference lies on the same side of 0 and of Bw as the exact one.  The counts are therefore integers of exact arithmetic,
+// whatever the launch geometry.  A wave without a marker in the box leaves after its load; in the others, a lane whose two markers share a
+// sub-pixel carries a weight of 2, and a RUN of lanes on one sub-pixel (the array keeps neighbours in space neighbours in memory) folds to its first
+// lane, which issues one 32-bit integer add whose result nobody reads.
+//
+// The pass only reads the marker array and touches none of the handle's validity flags.
+#include "euler_dev.h"
+
+#include <stdlib.h>
+
+#define VR_T 256              // threads per workgroup: 512 markers
+#define VR_MAX_PIXELS (1 << 24)
+
+struct VrArgs {
+  const float4* m2;           // the marker array, two markers per element
+  unsigned long long n;       // markers
+  float fx0, fy0, fs, fW, fH; // the box origin, the scale and the raster's extent as floats (all exact: integers <= 2^24)
+  int W, H;
+  unsigned int* out;
+};
+
+// the sub-pixel of a position; false: outside the box (a NaN fails every comparison, an infinity the upper ones)
+__device__ __forceinline__ bool vr_pixel(const VrArgs& a, float x, float y, unsigned int& pix) {
+  const float sx = (x - a.fx0) * a.fs, sy = (y - a.fy0) * a.fs;
+  const bool in = sx >= 0.f && sx < a.fW && sy >= 0.f && sy < a.fH;
+  pix = in ? (unsigned int)(a.H - 1 - (int)sy) * (unsigned int)a.W + (unsigned int)(int)sx : 0u;      // (W * H <= 2^24: no wrap)
+  return in;
+}
+
+// bin_aggregated (euler_dev.h) for row-major pixels with a weight of 1 or 2 per lane: the first lane of a run of live lanes on one pixel adds the run's weights
+__device__ __forceinline__ void vr_add_runs(unsigned int* out, bool live, unsigned int pix, unsigned int w) {
+  const int lane = threadIdx.x & 63;
+  const unsigned int ppix = __shfl_up(pix, 1, 64);
+  const bool plive = __shfl_up((int)live, 1, 64) != 0;
+  const bool head = live && (lane == 0 || !plive || ppix != pix);
+  const unsigned long long heads = __ballot(head), lives = __ballot(live), twos = __ballot(live && w == 2u);
+  if (!head) return;      // (no cross-lane operation below)
+  // the run ends before the next head or the next dead lane
+  const unsigned long long above = lane == 63 ? 0ull : ((heads | ~lives) >> (lane + 1));
+  const int run = above ? __ffsll((long long)above) : 64 - lane;
+  const unsigned long long span = (run == 64 ? ~0ull : ((1ull << run) - 1ull)) << lane;
+  atomicAdd(&out[pix], (unsigned int)run + (unsigned int)__popcll(twos & span));
+}
+
+__global__ __launch_bounds__(VR_T) void k_marker_raster(const VrArgs a) {
+  const unsigned long long j = (unsigned long long)blockIdx.x * VR_T + threadIdx.x, i0 = 2ull * j;      // this lane's markers: i0, i0 + 1
+  bool in0 = false, in1 = false;
+  unsigned int pix0 = 0u, pix1 = 0u;
+  if (i0 + 1ull < a.n) {
+    const float4 p = a.m2[j];
+    in0 = vr_pixel(a, p.x, p.y, pix0);
+    in1 = vr_pixel(a, p.z, p.w, pix1);
+  } else if (i0 < a.n) {      // an odd count: the last marker alone
+    const float2 p = reinterpret_cast<const float2*>(a.m2)[i0];
+    in0 = vr_pixel(a, p.x, p.y, pix0);
+  }
+  if (!__any(in0 || in1)) return;      // nothing of this wave lies in the box: no memory traffic beyond the load
+  const bool same = in0 && in1 && pix0 == pix1, second = in0 && in1 && !same;
+  vr_add_runs(a.out, in0 || in1, in0 ? pix0 : pix1, same ? 2u : 1u);
+  if (__any(second)) vr_add_runs(a.out, second, pix1, 1u);
+}
+
+// the device buffer of the raster: allocated by the first call, grown when W * H grows (a failure leaves the handle as it was)
+static int vr_reserve(euler_sim* S, size_t n) {
+  if (n <= S->vr_cap) return EULER_OK;
+  unsigned int* nb = nullptr;
+  if (hipMalloc((void**)&nb, n * sizeof(unsigned int)) != hipSuccess) {
+    (void)hipGetLastError();
+    eu_set_error("euler_marker_raster: %zu bytes of device memory for the raster", n * sizeof(unsigned int));
+    return EULER_ENOMEM;
+  }
+  if (S->vr_buf) {
+    HIPCHK(hipStreamSynchronize(S->stream));
+    (void)hipFree(S->vr_buf);
+    S->hbm_bytes -= S->vr_cap * sizeof(unsigned int);
+  }
+  S->vr_buf = nb; S->vr_cap = n;
+  S->hbm_bytes += n * sizeof(unsigned int);
+  return EULER_OK;
+}
+
+// the clear and the pass alone, on the handle's stream, into S->vr_buf (tools/viewport_cost.py times the pass through the KC_MISC class)
+static int vr_launch(euler_sim* S, int x0, int y0, int scale, int W, int H) {
+  HIPCHK(hipMemsetAsync(S->vr_buf, 0, (size_t)W * H * sizeof(unsigned int), S->stream));
+  const unsigned long long n = S->n_markers_host;
+  if (!n) return EULER_OK;
+  VrArgs a;
+  a.m2 = reinterpret_cast<const float4*>(S->markers[S->cur]); a.n = n;
+  a.fx0 = (float)x0; a.fy0 = (float)y0; a.fs = (float)scale; a.fW = (float)W; a.fH = (float)H;
+  a.W = W; a.H = H; a.out = S->vr_buf;
+  const unsigned long long nwg = (n + 2ull * VR_T - 1ull) / (2ull * VR_T);      // (at most max_markers / 512: far below 2^31 on any grid euler_create accepts)
+  LAUNCH(S, KC_MISC, k_marker_raster, dim3((unsigned)nwg), dim3(VR_T), a);
+  HIPCHK(hipGetLastError());
+  return EULER_OK;
+}
+
+extern "C" int euler_marker_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t scale, uint32_t* out, size_t out_bytes) {
+  if (!S || !out) { eu_set_error("euler_marker_raster: null argument"); return EULER_EINVAL; }
+  if (S->slab_on) { eu_set_error("euler_marker_raster: not on a row-slab handle (a slab holds the markers of its own rows only)"); return EULER_ESTATE; }
+  if (!S->loaded) { eu_set_error("euler_marker_raster: no scenario loaded"); return EULER_ESTATE; }
+  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
+    eu_set_error("euler_marker_raster: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", (int)x0, (int)x1, (int)y0, (int)y1, S->X - 2, S->Y - 2);
+    return EULER_EINVAL;
+  }
+  if (scale != 1 && scale != 2 && scale != 4 && scale != 8 && scale != 16) { eu_set_error("euler_marker_raster: scale %d: 1, 2, 4, 8 or 16", (int)scale); return EULER_EINVAL; }
+  const long long W = (long long)(x1 - x0 + 1) * scale, H = (long long)(y1 - y0 + 1) * scale;
+  if (W * H > VR_MAX_PIXELS) { eu_set_error("euler_marker_raster: a raster of %lld x %lld pixels (at most 2^24)", W, H); return EULER_EINVAL; }
+  const size_t n = (size_t)(W * H);
+  if (out_bytes != n * sizeof(uint32_t)) { eu_set_error("euler_marker_raster: %zu bytes given, %zu expected", out_bytes, n * sizeof(uint32_t)); return EULER_EINVAL; }
+  int rc = vr_reserve(S, n);
+  if (!rc) rc = vr_launch(S, x0, y0, scale, (int)W, (int)H);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(out, S->vr_buf, out_bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return EULER_OK;
+}
+
+extern "C" int euler_render_view(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {
+  if (!S || !len || wx < 1 || wy < 1) { eu_set_error("euler_render_view: bad argument"); return EULER_EINVAL; }
+  if (S->slab_on) { eu_set_error("euler_render_view: not on a row-slab handle (a box of cells straddles slabs)"); return EULER_ESTATE; }
+  if (!S->loaded) { eu_set_error("euler_render_view: no scenario loaded"); return EULER_ESTATE; }
+  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
+    eu_set_error("euler_render_view: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", (int)x0, (int)x1, (int)y0, (int)y1, S->X - 2, S->Y - 2);
+    return EULER_EINVAL;
+  }
+  const int Bw = x1 - x0 + 1, Bh = y1 - y0 + 1;
+  int scale = 0;      // 0: at or below one cell per glyph
+  if ((long long)Bw * 2 <= wx && (long long)Bh * 2 <= wy)
+    for (scale = 16; (long long)Bw * scale > wx || (long long)Bh * scale > wy; scale >>= 1) {}
+  const int W = scale ? Bw : (wx < Bw ? wx : Bw), H = scale ? Bh : (wy < Bh ? wy : Bh);
+  const size_t bytes = (size_t)W * H * sizeof(euler_overview_px), rbytes = scale ? (size_t)Bw * scale * Bh * scale * sizeof(uint32_t) : 0;
+  euler_overview_px* px = (euler_overview_px*)malloc(bytes);
+  uint32_t* ras = scale ? (uint32_t*)malloc(rbytes) : nullptr;
+  int rc = px && (!scale || ras) ? EULER_OK : EULER_ENOMEM;
+  if (rc) eu_set_error("euler_render_view: %zu bytes of host memory", bytes + rbytes);
+  if (!rc) rc = euler_overview_box(S, x0, y0, x1, y1, W, H, px, bytes);
+  if (!rc && scale) rc = euler_marker_raster(S, x0, y0, x1, y1, scale, ras, rbytes);
+  if (!rc) rc = scale ? euler_view_text(px, ras, Bw, Bh, scale, S->cfg.rainbow, out, cap, len) : euler_overview_text(px, W, H, S->cfg.rainbow, out, cap, len);
+  free(px); free(ras);
+  return rc;
+}
+
+void eu_viewport_release(euler_sim* S) {
+  if (S->vr_buf) (void)hipFree(S->vr_buf);
+  S->vr_buf = nullptr; S->vr_cap = 0;
+}

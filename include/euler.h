@@ -349,6 +349,40 @@ int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_
  * with euler_config.rainbow).  Sizing protocol of euler_render; wx < 1 or wy < 1: EULER_EINVAL. */
 int euler_render_fit(euler_sim* sim, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len);
 
+/* ---- pan-and-zoom viewport (docs/viewport.md) ------------------------------------------------ */
+/* The overview of a BOX of interior cells [x0, x1] x [y0, y1] (inclusive, as for euler_diagnostics below): 1 <= x0 <= x1 <= X - 2 and
+ * 1 <= y0 <= y1 <= Y - 2, Bw = x1 - x0 + 1, Bh = y1 - y0 + 1, 1 <= W <= Bw, 1 <= H <= Bh, out_bytes exactly W * H * sizeof(euler_overview_px): else
+ * EULER_EINVAL.  Pixel column px covers x = x0 + floor(px * Bw / W) ... x0 + floor((px + 1) * Bw / W) - 1; pixel row py = 0 is the top and covers
+ * y = y1 - floor(py * Bh / H) down to y1 + 1 - floor((py + 1) * Bh / H).  The records are euler_overview_px as above; with the whole interior as the
+ * box they are euler_overview's, which is this call on (1, 1, X - 2, Y - 2): the same launch, the same device buffer and its growth (EULER_ENOMEM: the
+ * handle unchanged), the same EULER_ESTATE refusals.  Reads the state only. */
+int euler_overview_box(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                       int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes);
+/* Above one cell per pixel: the MARKERS of the box (EULER_F_MARKERS, sub-cell positions) counted on the device into a raster of scale x scale
+ * sub-pixels per cell.  scale is 1, 2, 4, 8 or 16; W = Bw * scale, H = Bh * scale, W * H <= 2^24 and out_bytes == W * H * 4: else EULER_EINVAL.
+ * out[r * W + c] is the number of markers m with c = floor((m.x - x0) * scale) and r = H - 1 - floor((m.y - y0) * scale), counted only where
+ * 0 <= c < W and 0 <= H - 1 - r < H (cell x is [x, x + 1), row 0 = top); a marker with a non-finite coordinate counts nowhere.  Positions are
+ * below 2^24 and x0 is an integer no larger than an in-box m.x: the float subtraction is exact, the multiplication by a power of two is exact,
+ * and the counts are integers that do not depend on the launch geometry (tests compare them exactly).  One pass over the marker array behind a
+ * clear of the raster, on the handle's stream; it only READS the markers: stepping afterwards gives the bits of a run that never called it.
+ * The raster's device buffer comes with the first call, grows on demand (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy.
+ * EULER_ESTATE without a loaded state and on a row-slab handle (a slab holds its own markers only). */
+int euler_marker_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                        int32_t scale, uint32_t* out, size_t out_bytes);
+/* Host formatter of a magnified view (no GPU needed).  cells: the box at ONE cell per record (Bw x Bh records, row 0 = top); raster: the
+ * (Bh * scale) x (Bw * scale) counts of euler_marker_raster over the same box.  Every cell becomes scale x scale glyphs through the frame formatter
+ * of euler_render: a solid cell (the class of euler_overview_text) 'X', a sink cell '=', else the glyph index min(3, count of the sub-pixel), 0 = air;
+ * rainbow != 0: a water glyph carries its cell's mean-dye colour.  Bw, Bh < 1, a scale other than 1, 2, 4, 8, 16 or more than 2^24 glyphs:
+ * EULER_EINVAL.  Same sizing protocol as euler_render. */
+int euler_view_text(const euler_overview_px* cells, const uint32_t* raster, int32_t Bw, int32_t Bh,
+                    int32_t scale, int32_t rainbow, char* out, int32_t cap, int32_t* len);
+/* The frame of a box in a window of wx x wy glyphs (wx < 1 or wy < 1: EULER_EINVAL).  Where the window holds the box at least twice in both
+ * directions (Bw * 2 <= wx and Bh * 2 <= wy): the largest scale <= 16 with Bw * scale <= wx and Bh * scale <= wy, euler_overview_box at one cell per
+ * pixel, euler_marker_raster, euler_view_text.  Otherwise euler_overview_box with W = min(wx, Bw), H = min(wy, Bh), then euler_overview_text.  Coloured
+ * on a handle created with euler_config.rainbow.  Sizing protocol of euler_render. */
+int euler_render_view(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                      int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len);
+
 /* ---- flow diagnostics (docs/diagnostics.md) ------------------------------------------------------ */
 /* How good is a frame?  One pass ON THE DEVICE over a box of interior cells [x0, x1] x [y0, y1] (inclusive) reduces u, v, count and solid to the
  * record below; only its 88 bytes cross to the host.  A FLUID cell is the reference's is_fluid on a non-solid cell: count > 0 && !solid.  Per fluid
