@@ -126,6 +126,8 @@ struct SelectScratch {
   size_t capacity_blocks;
 };
 
+struct eu_devbuf { void* p; size_t bytes; };   // a grow-only device buffer of a handle (eu_devbuf_reserve), counted in hbm_bytes
+
 struct euler_sim {
   euler_config cfg;
   int X, Y;
@@ -161,9 +163,8 @@ struct euler_sim {
   float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when blocked_dirty): whole-grid handles only
   int solidT_dirty;
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
-  euler_overview_px* ov_buf; size_t ov_cap;   // euler_overview (k_overview.hip): the records on the device, room for ov_cap of them; allocated by the first call, grown on demand
-  euler_diag* diag_buf;   // euler_diagnostics (k_diagnostics.hip): the record on the device; allocated by the first call
-  unsigned int* vr_buf; size_t vr_cap;   // euler_marker_raster (k_viewport.hip): the raster on the device, room for vr_cap pixels; allocated by the first call, grown on demand
+  eu_devbuf ov_buf, diag_buf, vr_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
+                          // raster; each allocated by its pass's first call and grown on demand
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -400,9 +401,13 @@ int eu_launch_pcg_op(euler_sim* S, int op, float dt, double a, double* out);
 int eu_ordered_select(euler_sim* S, const unsigned long long* mask, size_t nwords, unsigned int* out_idx,
                       unsigned int* out_total);
 int eu_sync_marker_state(euler_sim* S);
-void eu_overview_release(euler_sim* S);   // k_overview.hip
-void eu_diagnostics_release(euler_sim* S);   // k_diagnostics.hip
-void eu_viewport_release(euler_sim* S);   // k_viewport.hip
+// the host side of a read-only observer pass (k_observe.hip, docs/observer_passes.md): enter, reserve, launch, read back
+int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reason, const void* out, int x0, int y0, int x1, int y1);   // null argument, row-slab handle, nothing loaded, box inside the interior
+int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes);   // grow-only; a failure leaves the handle as it was
+void eu_devbuf_release(euler_sim* S, eu_devbuf* b);
+int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t bytes);   // copy to the caller and wait for it
+// k_overview.hip: euler_overview_box behind eu_observe_enter (euler_render_view, which has entered already)
+int eu_overview_entered(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes);
 void eu_rccl_release(euler_sim* S);   // comm_rccl.hip
 void eu_p2p_release(euler_sim* S);    // comm_p2p.hip
 int eu_p2p_halo_skewed(euler_sim* S, double* s_skewed);   // ghost rows of a band-skewed vector, straight from / into the array

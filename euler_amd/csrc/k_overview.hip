@@ -10,7 +10,7 @@
 // atomics into records the host zeroed.  With the tile map, a 64 x 64 tile without water is read for its solid / sink bytes only.
 //
 // The pass only reads the state and touches none of the handle's validity flags.
-#include "euler_dev.h"
+#include "k_observe.h"
 
 #include <stdlib.h>
 
@@ -22,8 +22,7 @@
 struct OvArgs {
   const uint8_t *solid, *sink, *count;
   const float *u, *v, *dye[3];
-  const uint8_t* tmap;      // null: every tile is read whole
-  int tnx;
+  ObTiles tiles;
   int X, Y, W, H, npc, nsplit;
   int bx0, by1, Bw, Bh;     // the box: its left column, its top row, its extent in cells (the whole interior: 1, Y - 2, X - 2, Y - 2)
   euler_overview_px* out;
@@ -39,12 +38,6 @@ __device__ __forceinline__ void ov_merge(OvAcc& a, const OvAcc& b) {
   a.max_bits = b.max_bits > a.max_bits ? b.max_bits : a.max_bits;
   a.dye[0] += b.dye[0]; a.dye[1] += b.dye[1]; a.dye[2] += b.dye[2];
 }
-// q(x) of include/euler.h: clamp to [0, 1] (a NaN: 0), times 2^24 (exact), truncated
-__device__ __forceinline__ unsigned int ov_q(float x) {
-  const float c = x > 0.f ? (x > 1.f ? 1.f : x) : 0.f;
-  return (unsigned int)(c * 16777216.f);
-}
-
 struct OvTable {
   unsigned int w[5][OV_NPC];          // solid, sink, water, marks, max_speed2 bits
   unsigned long long dye[3][OV_NPC];
@@ -60,28 +53,8 @@ __device__ __forceinline__ void ov_to_table(OvTable& t, int p, const OvAcc& a) {
     if (DYE) for (int c = 0; c < 3; ++c) if (a.dye[c]) atomicAdd(&t.dye[c][p], a.dye[c]);
   }
 }
-__device__ __forceinline__ unsigned int ov_wave_sum(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long ov_wave_sum64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned int ov_wave_max(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const unsigned int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ int ov_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-  return v;
-}
 
-// VEC: cells per lane - 4 where X % 4 == 0 (every row starts 16-byte aligned: one dword of each mask, one float4 of each field), else 1
+// VEC: cells per lane (k_observe.h)
 template <int VEC, bool DYE>
 __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   __shared__ OvTable tab;
@@ -100,7 +73,7 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   }
   __syncthreads();
   const size_t X = (size_t)a.X;
-  const int xbase = VEC == 4 ? (xa & ~3) : xa;      // (lane groups stay aligned to ABSOLUTE x & ~3 whatever the box: the cells an edge cuts are masked below)
+  const int xbase = ob_xbase(VEC, xa);      // (the cells an edge cuts are masked below)
   // (the trip count is the same for the lanes of a wave up to the last pass: the shuffles below run behind a wave-uniform test)
   for (int xc = xbase; xc <= xb; xc += OV_T * VEC) {
     const int x0 = xc + tid * VEC;
@@ -112,52 +85,20 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
       for (int y = yhi; y >= ylo;) {
         const int ty = y >> 6;
         const int yend = (ty << 6) > ylo ? (ty << 6) : ylo;
-        const bool wet = !a.tmap || a.tmap[ty * a.tnx + tx] != 0;      // the tile map is a superset: a cleared flag means no cell of the tile holds markers
+        const bool wet = a.tiles.wet(tx, ty);
         for (; y >= yend; --y) {
-          const size_t i = (size_t)y * X + (size_t)x0;
-          unsigned int so, si, cn = 0u;
-          float uu[VEC + 1], vv[VEC], vd[VEC], dr[VEC], dg[VEC], db[VEC];
-          if constexpr (VEC == 4) {
-            so = *reinterpret_cast<const unsigned int*>(a.solid + i);
-            si = *reinterpret_cast<const unsigned int*>(a.sink + i);
-          } else { so = a.solid[i]; si = a.sink[i]; }
-          if (wet) {
-            if constexpr (VEC == 4) {
-              cn = *reinterpret_cast<const unsigned int*>(a.count + i);
-              const float4 u4 = *reinterpret_cast<const float4*>(a.u + i);
-              const float4 v4 = *reinterpret_cast<const float4*>(a.v + i);
-              const float4 w4 = *reinterpret_cast<const float4*>(a.v + i - X);
-              uu[0] = a.u[i - 1]; uu[1] = u4.x; uu[2] = u4.y; uu[3] = u4.z; uu[4] = u4.w;
-              vv[0] = v4.x; vv[1] = v4.y; vv[2] = v4.z; vv[3] = v4.w;
-              vd[0] = w4.x; vd[1] = w4.y; vd[2] = w4.z; vd[3] = w4.w;
-              if (DYE) {
-                const float4 r4 = *reinterpret_cast<const float4*>(a.dye[0] + i);
-                const float4 g4 = *reinterpret_cast<const float4*>(a.dye[1] + i);
-                const float4 b4 = *reinterpret_cast<const float4*>(a.dye[2] + i);
-                dr[0] = r4.x; dr[1] = r4.y; dr[2] = r4.z; dr[3] = r4.w;
-                dg[0] = g4.x; dg[1] = g4.y; dg[2] = g4.z; dg[3] = g4.w;
-                db[0] = b4.x; db[1] = b4.y; db[2] = b4.z; db[3] = b4.w;
-              }
-            } else {
-              cn = a.count[i];
-              uu[0] = a.u[i - 1]; uu[1] = a.u[i];
-              vv[0] = a.v[i]; vd[0] = a.v[i - X];
-              if (DYE) { dr[0] = a.dye[0][i]; dg[0] = a.dye[1][i]; db[0] = a.dye[2][i]; }
-            }
-          }
+          ObRow<VEC, true, DYE> row;
+          row.load(a.solid, a.sink, a.count, a.u, a.v, a.dye, X, (size_t)y * X + (size_t)x0, wet);
 #pragma unroll
           for (int k = 0; k < VEC; ++k) {
-            const unsigned int s = (so >> (8 * k)) & 0xffu, n = (si >> (8 * k)) & 0xffu, c = (cn >> (8 * k)) & 0xffu;
+            const unsigned int s = row.solid(k), n = row.sink(k), c = row.count(k);
             if (s) acc[k].solid += 1u;
             else if (n) acc[k].sink += 1u;
             else if (wet && c) {
               acc[k].water += 1u;
               acc[k].marks += c < 3u ? c : 3u;
-              const float dx = (uu[k + 1] + uu[k]) / 2.f, dy = (vv[k] + vd[k]) / 2.f;
-              const float s2 = dx * dx + dy * dy;
-              const unsigned int bits = __float_as_uint(s2);
-              if (s2 == s2 && bits > acc[k].max_bits) acc[k].max_bits = bits;      // (s2 >= +0 unless it is a NaN: unsigned order = float order)
-              if (DYE) { acc[k].dye[0] += ov_q(dr[k]); acc[k].dye[1] += ov_q(dg[k]); acc[k].dye[2] += ov_q(db[k]); }
+              ob_max_bits(acc[k].max_bits, row.speed2(k));
+              if (DYE) for (int ch = 0; ch < 3; ++ch) acc[k].dye[ch] += ob_q24(row.dye[ch][k]);
             }
           }
         }
@@ -171,15 +112,15 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
       pk[k] = x >= xa && x <= xb ? (int)(((unsigned long long)(x - a.bx0 + 1) * (unsigned int)a.W - 1ull) / Xi) - p0 : -1;      // the column px whose range holds x
       if (pk[k] >= 0) { pmin = pk[k] < pmin ? pk[k] : pmin; pmax = pk[k] > pmax ? pk[k] : pmax; }
     }
-    const int wmin = ov_wave_min(pmin), wmax = -ov_wave_min(-pmax);
+    const int wmin = ob_wave<ObMin>(pmin), wmax = ob_wave<ObMax>(pmax);
     if (wmin == wmax) {      // the whole wave sits in one pixel (wide boxes): fold across the lanes, one lane goes to the table
       OvAcc t;
       ov_clear(t);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) if (pk[k] >= 0) ov_merge(t, acc[k]);
-      t.solid = ov_wave_sum(t.solid); t.sink = ov_wave_sum(t.sink); t.water = ov_wave_sum(t.water); t.marks = ov_wave_sum(t.marks);
-      t.max_bits = ov_wave_max(t.max_bits);
-      if (DYE) for (int c = 0; c < 3; ++c) t.dye[c] = ov_wave_sum64(t.dye[c]);
+      t.solid = ob_wave<ObSum>(t.solid); t.sink = ob_wave<ObSum>(t.sink); t.water = ob_wave<ObSum>(t.water); t.marks = ob_wave<ObSum>(t.marks);
+      t.max_bits = ob_wave<ObMax>(t.max_bits);
+      if (DYE) for (int c = 0; c < 3; ++c) t.dye[c] = ob_wave<ObSum>(t.dye[c]);
       if ((tid & 63) == 0) ov_to_table<DYE>(tab, wmin, t);
     } else {
       OvAcc t;
@@ -220,40 +161,21 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   }
 }
 
-// the device buffer of the records: allocated by the first call, grown when W * H grows (a failure leaves the handle as it was)
-static int ov_reserve(euler_sim* S, size_t n) {
-  if (n <= S->ov_cap) return EULER_OK;
-  euler_overview_px* nb = nullptr;
-  if (hipMalloc((void**)&nb, n * sizeof(euler_overview_px)) != hipSuccess) {
-    (void)hipGetLastError();
-    eu_set_error("euler_overview: %zu bytes of device memory for the records", n * sizeof(euler_overview_px));
-    return EULER_ENOMEM;
-  }
-  if (S->ov_buf) {
-    HIPCHK(hipStreamSynchronize(S->stream));
-    (void)hipFree(S->ov_buf);
-    S->hbm_bytes -= S->ov_cap * sizeof(euler_overview_px);
-  }
-  S->ov_buf = nb; S->ov_cap = n;
-  S->hbm_bytes += n * sizeof(euler_overview_px);
-  return EULER_OK;
-}
-
-// the reduction alone, on the handle's stream, into S->ov_buf (tools/overview_cost.py times it through the KC_MISC class)
+// the reduction alone, on the handle's stream, into the records of S->ov_buf (tools/overview_cost.py times it through the KC_MISC class)
 static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H) {
   const int Xi = x1 - x0 + 1, Yi = y1 - y0 + 1;      // (the box's extent: npc and nsplit follow it)
   OvArgs a;
   a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
   for (int c = 0; c < 3; ++c) a.dye[c] = S->dye[c];
-  a.tmap = eu_tile_map_on(S) ? S->tmap : nullptr; a.tnx = S->tmap_nx;
-  a.X = S->X; a.Y = S->Y; a.W = W; a.H = H; a.out = S->ov_buf;
+  a.tiles = eu_observe_tiles(S);
+  a.X = S->X; a.Y = S->Y; a.W = W; a.H = H; a.out = (euler_overview_px*)S->ov_buf.p;
   a.bx0 = x0; a.by1 = y1; a.Bw = Xi; a.Bh = Yi;
   long long npc = (long long)OV_SPAN * W / Xi;      // pixel columns per workgroup: about OV_SPAN cells wide, at least one box, at most the table
   a.npc = (int)(npc < 1 ? 1 : (npc > OV_NPC ? OV_NPC : npc));
   const long long span = ((long long)a.npc * Xi + W - 1) / W, rows_max = (Yi + H - 1) / H, rows_min = Yi / H;
   long long ns = (span * rows_max + OV_WG_CELLS - 1) / OV_WG_CELLS;      // slices of a box's rows
   a.nsplit = (int)(ns < 1 ? 1 : (ns > rows_min ? rows_min : ns));
-  if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->ov_buf, 0, (size_t)W * H * sizeof(euler_overview_px), S->stream));
+  if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->ov_buf.p, 0, (size_t)W * H * sizeof(euler_overview_px), S->stream));
   const long long nwg = (long long)((W + a.npc - 1) / a.npc) * H * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
   const dim3 grid((unsigned)nwg);
   const bool vec = S->X % 4 == 0, dye = S->dye[0] != nullptr;
@@ -265,24 +187,20 @@ static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H)
   return EULER_OK;
 }
 
-// the call behind euler_overview (the whole interior) and euler_overview_box
-static int ov_call(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes) {
-  if (!S || !out) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (a box of cells straddles slabs)", who); return EULER_ESTATE; }
-  if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
-  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
-    eu_set_error("%s: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", who, x0, x1, y0, y1, S->X - 2, S->Y - 2);
-    return EULER_EINVAL;
-  }
+// euler_overview_box behind the entry checks (euler_render_view enters once for both of its passes)
+int eu_overview_entered(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes) {
   if (W < 1 || H < 1 || W > x1 - x0 + 1 || H > y1 - y0 + 1) { eu_set_error("%s: a raster of %d x %d for a box of %d x %d cells", who, W, H, x1 - x0 + 1, y1 - y0 + 1); return EULER_EINVAL; }
   const size_t n = (size_t)W * (size_t)H;
   if (out_bytes != n * sizeof(euler_overview_px)) { eu_set_error("%s: %zu bytes given, %zu expected", who, out_bytes, n * sizeof(euler_overview_px)); return EULER_EINVAL; }
-  int rc = ov_reserve(S, n);
+  int rc = eu_devbuf_reserve(S, "euler_overview", "the records", &S->ov_buf, out_bytes);
   if (!rc) rc = ov_launch(S, x0, y0, x1, y1, W, H);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, S->ov_buf, out_bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));
-  return EULER_OK;
+  return rc ? rc : eu_observe_readback(S, out, &S->ov_buf, out_bytes);
+}
+
+// the call behind euler_overview (the whole interior) and euler_overview_box
+static int ov_call(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes) {
+  const int rc = eu_observe_enter(S, who, "a box of cells straddles slabs", out, x0, y0, x1, y1);
+  return rc ? rc : eu_overview_entered(S, who, x0, y0, x1, y1, W, H, out, out_bytes);
 }
 
 extern "C" int euler_overview(euler_sim* S, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes) {
@@ -304,9 +222,4 @@ extern "C" int euler_render_fit(euler_sim* S, int32_t wx, int32_t wy, char* out,
   if (!rc) rc = euler_overview_text(px, W, H, S->cfg.rainbow, out, cap, len);
   free(px);
   return rc;
-}
-
-void eu_overview_release(euler_sim* S) {
-  if (S->ov_buf) (void)hipFree(S->ov_buf);
-  S->ov_buf = nullptr; S->ov_cap = 0;
 }

@@ -67,69 +67,42 @@ __global__ __launch_bounds__(VR_T) void k_marker_raster(const VrArgs a) {
   if (__any(second)) vr_add_runs(a.out, second, pix1, 1u);
 }
 
-// the device buffer of the raster: allocated by the first call, grown when W * H grows (a failure leaves the handle as it was)
-static int vr_reserve(euler_sim* S, size_t n) {
-  if (n <= S->vr_cap) return EULER_OK;
-  unsigned int* nb = nullptr;
-  if (hipMalloc((void**)&nb, n * sizeof(unsigned int)) != hipSuccess) {
-    (void)hipGetLastError();
-    eu_set_error("euler_marker_raster: %zu bytes of device memory for the raster", n * sizeof(unsigned int));
-    return EULER_ENOMEM;
-  }
-  if (S->vr_buf) {
-    HIPCHK(hipStreamSynchronize(S->stream));
-    (void)hipFree(S->vr_buf);
-    S->hbm_bytes -= S->vr_cap * sizeof(unsigned int);
-  }
-  S->vr_buf = nb; S->vr_cap = n;
-  S->hbm_bytes += n * sizeof(unsigned int);
-  return EULER_OK;
-}
-
-// the clear and the pass alone, on the handle's stream, into S->vr_buf (tools/viewport_cost.py times the pass through the KC_MISC class)
+// the clear and the pass alone, on the handle's stream, into the raster of S->vr_buf (tools/viewport_cost.py times the pass through the KC_MISC class)
 static int vr_launch(euler_sim* S, int x0, int y0, int scale, int W, int H) {
-  HIPCHK(hipMemsetAsync(S->vr_buf, 0, (size_t)W * H * sizeof(unsigned int), S->stream));
+  HIPCHK(hipMemsetAsync(S->vr_buf.p, 0, (size_t)W * H * sizeof(unsigned int), S->stream));
   const unsigned long long n = S->n_markers_host;
   if (!n) return EULER_OK;
   VrArgs a;
   a.m2 = reinterpret_cast<const float4*>(S->markers[S->cur]); a.n = n;
   a.fx0 = (float)x0; a.fy0 = (float)y0; a.fs = (float)scale; a.fW = (float)W; a.fH = (float)H;
-  a.W = W; a.H = H; a.out = S->vr_buf;
+  a.W = W; a.H = H; a.out = (unsigned int*)S->vr_buf.p;
   const unsigned long long nwg = (n + 2ull * VR_T - 1ull) / (2ull * VR_T);      // (at most max_markers / 512: far below 2^31 on any grid euler_create accepts)
   LAUNCH(S, KC_MISC, k_marker_raster, dim3((unsigned)nwg), dim3(VR_T), a);
   HIPCHK(hipGetLastError());
   return EULER_OK;
 }
 
-extern "C" int euler_marker_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t scale, uint32_t* out, size_t out_bytes) {
-  if (!S || !out) { eu_set_error("euler_marker_raster: null argument"); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("euler_marker_raster: not on a row-slab handle (a slab holds the markers of its own rows only)"); return EULER_ESTATE; }
-  if (!S->loaded) { eu_set_error("euler_marker_raster: no scenario loaded"); return EULER_ESTATE; }
-  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
-    eu_set_error("euler_marker_raster: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", (int)x0, (int)x1, (int)y0, (int)y1, S->X - 2, S->Y - 2);
-    return EULER_EINVAL;
-  }
-  if (scale != 1 && scale != 2 && scale != 4 && scale != 8 && scale != 16) { eu_set_error("euler_marker_raster: scale %d: 1, 2, 4, 8 or 16", (int)scale); return EULER_EINVAL; }
+// euler_marker_raster behind the entry checks (euler_render_view enters once for both of its passes)
+static int vr_entered(euler_sim* S, int x0, int y0, int x1, int y1, int scale, uint32_t* out, size_t out_bytes) {
+  if (scale != 1 && scale != 2 && scale != 4 && scale != 8 && scale != 16) { eu_set_error("euler_marker_raster: scale %d: 1, 2, 4, 8 or 16", scale); return EULER_EINVAL; }
   const long long W = (long long)(x1 - x0 + 1) * scale, H = (long long)(y1 - y0 + 1) * scale;
   if (W * H > VR_MAX_PIXELS) { eu_set_error("euler_marker_raster: a raster of %lld x %lld pixels (at most 2^24)", W, H); return EULER_EINVAL; }
   const size_t n = (size_t)(W * H);
   if (out_bytes != n * sizeof(uint32_t)) { eu_set_error("euler_marker_raster: %zu bytes given, %zu expected", out_bytes, n * sizeof(uint32_t)); return EULER_EINVAL; }
-  int rc = vr_reserve(S, n);
+  int rc = eu_devbuf_reserve(S, "euler_marker_raster", "the raster", &S->vr_buf, out_bytes);
   if (!rc) rc = vr_launch(S, x0, y0, scale, (int)W, (int)H);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, S->vr_buf, out_bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));
-  return EULER_OK;
+  return rc ? rc : eu_observe_readback(S, out, &S->vr_buf, out_bytes);
+}
+
+extern "C" int euler_marker_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t scale, uint32_t* out, size_t out_bytes) {
+  const int rc = eu_observe_enter(S, "euler_marker_raster", "a slab holds the markers of its own rows only", out, x0, y0, x1, y1);
+  return rc ? rc : vr_entered(S, x0, y0, x1, y1, scale, out, out_bytes);
 }
 
 extern "C" int euler_render_view(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {
   if (!S || !len || wx < 1 || wy < 1) { eu_set_error("euler_render_view: bad argument"); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("euler_render_view: not on a row-slab handle (a box of cells straddles slabs)"); return EULER_ESTATE; }
-  if (!S->loaded) { eu_set_error("euler_render_view: no scenario loaded"); return EULER_ESTATE; }
-  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
-    eu_set_error("euler_render_view: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", (int)x0, (int)x1, (int)y0, (int)y1, S->X - 2, S->Y - 2);
-    return EULER_EINVAL;
-  }
+  int rc = eu_observe_enter(S, "euler_render_view", "a box of cells straddles slabs", len, x0, y0, x1, y1);
+  if (rc) return rc;
   const int Bw = x1 - x0 + 1, Bh = y1 - y0 + 1;
   int scale = 0;      // 0: at or below one cell per glyph
   if ((long long)Bw * 2 <= wx && (long long)Bh * 2 <= wy)
@@ -138,16 +111,11 @@ extern "C" int euler_render_view(euler_sim* S, int32_t x0, int32_t y0, int32_t x
   const size_t bytes = (size_t)W * H * sizeof(euler_overview_px), rbytes = scale ? (size_t)Bw * scale * Bh * scale * sizeof(uint32_t) : 0;
   euler_overview_px* px = (euler_overview_px*)malloc(bytes);
   uint32_t* ras = scale ? (uint32_t*)malloc(rbytes) : nullptr;
-  int rc = px && (!scale || ras) ? EULER_OK : EULER_ENOMEM;
+  rc = px && (!scale || ras) ? EULER_OK : EULER_ENOMEM;
   if (rc) eu_set_error("euler_render_view: %zu bytes of host memory", bytes + rbytes);
-  if (!rc) rc = euler_overview_box(S, x0, y0, x1, y1, W, H, px, bytes);
-  if (!rc && scale) rc = euler_marker_raster(S, x0, y0, x1, y1, scale, ras, rbytes);
+  if (!rc) rc = eu_overview_entered(S, "euler_overview_box", x0, y0, x1, y1, W, H, px, bytes);
+  if (!rc && scale) rc = vr_entered(S, x0, y0, x1, y1, scale, ras, rbytes);
   if (!rc) rc = scale ? euler_view_text(px, ras, Bw, Bh, scale, S->cfg.rainbow, out, cap, len) : euler_overview_text(px, W, H, S->cfg.rainbow, out, cap, len);
   free(px); free(ras);
   return rc;
-}
-
-void eu_viewport_release(euler_sim* S) {
-  if (S->vr_buf) (void)hipFree(S->vr_buf);
-  S->vr_buf = nullptr; S->vr_cap = 0;
 }

@@ -2,7 +2,6 @@
 the fields read back through euler_get_field - every field exactly equal, max_div and max_speed2 bit for bit - over the five scenarios, grids that
 take the four-cells-per-lane and the one-cell-per-lane path, boxes that cut a lane's group at either edge, sit inside one tile or span idle tiles,
 with and without the tile map; planted non-finite values and counts; that the pass leaves no trace in the state; `euler --stats`."""
-import os
 import subprocess
 
 import numpy as np
@@ -12,12 +11,9 @@ import diagnostics_ref as ref
 import euler_amd as ea
 from euler_amd import scenarios
 from golden_util import SCENARIOS, X, Y, load, scenario_text
-from test_gpu_parity import assert_bits
+from observer_util import EULER_EINVAL, EULER_ESTATE, EXE, no_trace_pair
 
 pytestmark = pytest.mark.gpu
-
-EULER_EINVAL, EULER_ESTATE = -1, -5      # include/euler.h
-EXE = os.path.join(os.path.dirname(ea.LIB_PATH), "..", "bin", "euler")
 
 
 def terms_of(sim):
@@ -164,26 +160,17 @@ def test_1024_dam_break_with_and_without_the_tile_map():
 
 # ----------------------------------------------------------------------------- no lasting state
 def _pair(options=(), **kw):
-    a = ea.Simulation(256, 256, **kw).load_text(scenarios.dam_break(), upscale=True)
-    b = ea.Simulation(256, 256, **kw).load_text(scenarios.dam_break(), upscale=True)
-    for s in (a, b):
+    def make():
+        s = ea.Simulation(256, 256, **kw).load_text(scenarios.dam_break(), upscale=True)
         for k, v in options:
             s.set_option(k, v)
-    for f in range(20):
-        b.diagnostics()
-        a.step(); b.step()
-        b.diagnostics((5, 3, 250, 130))
-        if f == 10:      # once between the stages of a substep
-            dt = a.timestep(0.1)
-            assert b.timestep(0.1) == dt
-            for st in range(6):
-                a.stage(st, dt); b.stage(st, dt)
-                check(b, [None, (70, 2, 77, 9), (5, 3, 250, 130)], "between the stages, after stage %d" % st)      # (the count grid moves ahead of the tile map's next refresh here)
-    for fld in (ea.F_U, ea.F_V, ea.F_UTMP, ea.F_VTMP, ea.F_COUNT, ea.F_PREV_COUNT, ea.F_MARKERS, ea.F_PRESSURE):
-        assert_bits(b.get(fld), a.get(fld), "field %d" % fld)
-    sa, sb = a.stats(), b.stats()
-    assert (sa.total_substeps, sa.total_pcg_iterations, sa.n_markers, sa.rng_state) == (sb.total_substeps, sb.total_pcg_iterations, sb.n_markers, sb.rng_state)
-    assert sa.total_substeps >= 20
+        return s
+
+    def between_stages(s, st):      # (the count grid moves ahead of the tile map's next refresh here)
+        check(s, [None, (70, 2, 77, 9), (5, 3, 250, 130)], "between the stages, after stage %d" % st)
+
+    a, b = no_trace_pair(make, lambda s, stepped: s.diagnostics((5, 3, 250, 130)) if stepped else s.diagnostics(), between_stages, frames=20, compare_every=20)
+    assert a.stats().total_substeps >= 20
     check(b, [None], "after the pair")
     a.close(); b.close()
 

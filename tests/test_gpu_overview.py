@@ -2,7 +2,6 @@
 of the fields read back through euler_get_field - every field exactly equal, max_speed2 bit for bit - over the five scenarios, shapes that
 divide nothing, large grids with and without the tile map; that the pass leaves no trace in the state; the fit-to-window frame and the
 `euler` front end's --fit / --ppm."""
-import os
 import subprocess
 
 import numpy as np
@@ -12,18 +11,10 @@ import euler_amd as ea
 import overview_ref as ref
 from euler_amd import scenarios
 from golden_util import SCENARIOS, X, Y, load, scenario_text
+from observer_util import DYE, EULER_EINVAL, EULER_ESTATE, EXE, STATE_FIELDS, dumped_frames, no_trace_pair, read_back
 from test_gpu_parity import assert_bits
 
 pytestmark = pytest.mark.gpu
-
-EULER_EINVAL, EULER_ESTATE = -1, -5      # include/euler.h
-DYE = (ea.F_DYE_R, ea.F_DYE_G, ea.F_DYE_B)
-EXE = os.path.join(os.path.dirname(ea.LIB_PATH), "..", "bin", "euler")
-
-
-def read_back(sim, dye):
-    g = [sim.get(f) for f in (ea.F_SOLID, ea.F_SINK, ea.F_COUNT, ea.F_U, ea.F_V)]
-    return g + [tuple(sim.get(f) for f in DYE) if dye else None]
 
 
 def check(sim, dye, shapes, what, state=None):
@@ -153,29 +144,20 @@ def test_8192_half_tank():
 # ----------------------------------------------------------------------------- no lasting state
 def _pair(scn, frames=40, options=(), **kw):
     text = scenario_text(load(scn + "_frames.npz"))
-    a = ea.Simulation(X, Y, **kw).load_text(text)
-    b = ea.Simulation(X, Y, **kw).load_text(text)
-    for s in (a, b):
+
+    def make():
+        s = ea.Simulation(X, Y, **kw).load_text(text)
         for k, v in options:
             s.set_option(k, v)
-    dye = bool(kw.get("rainbow"))
-    fields = (ea.F_U, ea.F_V, ea.F_UTMP, ea.F_VTMP, ea.F_COUNT, ea.F_PREV_COUNT, ea.F_MARKERS, ea.F_PRESSURE) + (DYE if dye else ())
-    for f in range(frames):
-        b.overview(33, 13)
-        a.step(); b.step()
-        b.overview(98, 38)
-        if f == frames // 2:      # once between the stages of a substep
-            dt = a.timestep(0.1)
-            assert b.timestep(0.1) == dt
-            for st in range(6):
-                a.stage(st, dt); b.stage(st, dt)
-                b.overview(49, 19)
-                b.render_fit(20, 10)
-        for fld in fields:
-            assert_bits(b.get(fld), a.get(fld), "%s frame %d field %d" % (scn, f, fld))
-    sa, sb = a.stats(), b.stats()
-    assert (sa.total_substeps, sa.total_pcg_iterations, sa.n_markers, sa.rng_state) == (sb.total_substeps, sb.total_pcg_iterations, sb.n_markers, sb.rng_state)
-    a.close(); b.close()
+        return s
+
+    def between_stages(s, st):
+        s.overview(49, 19)
+        s.render_fit(20, 10)
+
+    fields = STATE_FIELDS + (DYE if kw.get("rainbow") else ())
+    for s in no_trace_pair(make, lambda s, stepped: s.overview(98, 38) if stepped else s.overview(33, 13), between_stages, fields, frames, compare_every=1):
+        s.close()
 
 
 @pytest.mark.parametrize("scn", SCENARIOS)
@@ -230,14 +212,6 @@ def test_render_fit_is_the_text_of_the_records():
 
 
 # ----------------------------------------------------------------------------- the front end
-def _frames(stdout):
-    out = []
-    for chunk in stdout.split(b"--- frame ")[1:]:
-        header, body = chunk.split(b"\n", 1)
-        out.append(body[: int(header.split(b"(")[1].split()[0])])
-    return out
-
-
 def test_cli_fit_and_ppm(tmp_path):
     g = load("basic_frames.npz")
     scn = tmp_path / "basic.txt"
@@ -255,15 +229,15 @@ def test_cli_fit_and_ppm(tmp_path):
     base = [EXE, "--dump", "--window", "49x19", "--frames", "5"]
     run = subprocess.run(base + ["--fit", str(scn)], capture_output=True, timeout=120)
     assert run.returncode == 0, run.stderr.decode()
-    assert _frames(run.stdout) == fit
+    assert dumped_frames(run.stdout) == fit
     # without the new flags: the frames of draw, as before
     run = subprocess.run(base + [str(scn)], capture_output=True, timeout=120)
-    assert run.returncode == 0 and _frames(run.stdout) == plain and plain != fit
+    assert run.returncode == 0 and dumped_frames(run.stdout) == plain and plain != fit
     # --ppm: frames / every + 1 files, the bytes of write_ppm(overview_rgb(...)) of the same state; the dumped frames unchanged
     prefix = str(tmp_path / "img_")
     run = subprocess.run(base + ["--ppm", prefix, "--ppm-size", "40x16", "--ppm-every", "2", "--ppm-mode", "speed:2.5", str(scn)], capture_output=True, timeout=120)
     assert run.returncode == 0, run.stderr.decode()
-    assert _frames(run.stdout) == plain
+    assert dumped_frames(run.stdout) == plain
     assert sorted(p.name for p in tmp_path.glob("img_*.ppm")) == ["img_%06d.ppm" % f for f in (0, 2, 4)]
     for f, px in images.items():
         want = tmp_path / "want.ppm"

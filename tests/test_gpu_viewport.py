@@ -2,7 +2,6 @@
 restatement (tests/viewport_ref.py) of the fields and markers read back - every field exactly equal, max_speed2 bit for bit - over the five
 scenarios, aligned and ragged large grids with and without the tile map, thin grids; the refusals; that the calls leave no trace in the state;
 euler_render_view and the `euler` front end's --view."""
-import os
 import subprocess
 
 import numpy as np
@@ -13,18 +12,9 @@ import overview_ref as ref
 import viewport_ref as vref
 from euler_amd import scenarios
 from golden_util import SCENARIOS, X, Y, load, scenario_text
-from test_gpu_parity import assert_bits
+from observer_util import DYE, EULER_EINVAL, EULER_ESTATE, EXE, STATE_FIELDS, dumped_frames, no_trace_pair, read_back
 
 pytestmark = pytest.mark.gpu
-
-EULER_EINVAL, EULER_ESTATE = -1, -5      # include/euler.h
-DYE = (ea.F_DYE_R, ea.F_DYE_G, ea.F_DYE_B)
-EXE = os.path.join(os.path.dirname(ea.LIB_PATH), "..", "bin", "euler")
-
-
-def read_back(sim, dye):
-    g = [sim.get(f) for f in (ea.F_SOLID, ea.F_SINK, ea.F_COUNT, ea.F_U, ea.F_V)]
-    return g + [tuple(sim.get(f) for f in DYE) if dye else None]
 
 
 def cases(Xg, Yg, seed, extra=()):
@@ -259,37 +249,27 @@ def test_render_view_of_the_whole_interior_is_draw():
 
 # ----------------------------------------------------------------------------- no lasting state
 def _pair(options=(), frames=20):
-    kw = dict(dot_mode=ea.DOT_TREE, precond=ea.PRECOND_IC0_TILE, max_iterations=30, rainbow=True)
-    a = ea.Simulation(256, 256, **kw).load_text(scenarios.dam_break(), upscale=True)
-    b = ea.Simulation(256, 256, **kw).load_text(scenarios.dam_break(), upscale=True)
-    for s in (a, b):
+    def make():
+        s = ea.Simulation(256, 256, dot_mode=ea.DOT_TREE, precond=ea.PRECOND_IC0_TILE, max_iterations=30, rainbow=True).load_text(scenarios.dam_break(), upscale=True)
         for k, v in options:
             s.set_option(k, v)
+        return s
 
-    def look(s):
+    def look(s, stepped):
+        if stepped:
+            return
         s.overview(40, 20, box=(5, 3, 250, 130))
         s.marker_raster((20, 100, 68, 118), 4)
         s.render_view((20, 100, 43, 108), 98, 38)
         s.render_view((1, 1, 254, 254), 98, 38)
 
-    fields = (ea.F_U, ea.F_V, ea.F_UTMP, ea.F_VTMP, ea.F_COUNT, ea.F_PREV_COUNT, ea.F_MARKERS, ea.F_PRESSURE) + DYE
-    for f in range(frames):
-        look(b)
-        a.step(); b.step()
-        if f == frames // 2:      # once between the stages of a substep
-            dt = a.timestep(0.1)
-            assert b.timestep(0.1) == dt
-            for st in range(6):
-                a.stage(st, dt); b.stage(st, dt)
-                look(b)
-                check_rasters(b, [((1, 1, 254, 254), 1), ((20, 100, 68, 118), 8)], "after stage %d" % st)
-                check_boxes(b, True, [((5, 3, 250, 130), 40, 20)], "after stage %d" % st)
-        if f % 5 == 4 or f == frames // 2:
-            for fld in fields:
-                assert_bits(b.get(fld), a.get(fld), "frame %d field %d" % (f, fld))
-    sa, sb = a.stats(), b.stats()
-    assert (sa.total_substeps, sa.total_pcg_iterations, sa.n_markers, sa.rng_state) == (sb.total_substeps, sb.total_pcg_iterations, sb.n_markers, sb.rng_state)
-    a.close(); b.close()
+    def between_stages(s, st):
+        look(s, False)
+        check_rasters(s, [((1, 1, 254, 254), 1), ((20, 100, 68, 118), 8)], "after stage %d" % st)
+        check_boxes(s, True, [((5, 3, 250, 130), 40, 20)], "after stage %d" % st)
+
+    for s in no_trace_pair(make, look, between_stages, STATE_FIELDS + DYE, frames, compare_every=5):
+        s.close()
 
 
 def test_the_calls_leave_no_trace():
@@ -301,14 +281,6 @@ def test_no_trace_with_maccormack_and_rk2():
 
 
 # ----------------------------------------------------------------------------- the front end
-def _frames(stdout):
-    out = []
-    for chunk in stdout.split(b"--- frame ")[1:]:
-        header, body = chunk.split(b"\n", 1)
-        out.append(body[: int(header.split(b"(")[1].split()[0])])
-    return out
-
-
 def test_cli_view(tmp_path):
     g = load("block_frames.npz")
     scn = tmp_path / "block.txt"
@@ -333,21 +305,21 @@ def test_cli_view(tmp_path):
         assert len(set(boxes)) >= 5 and len(set(view)) >= 5
         run = subprocess.run(base + view_flags + ["--keys", keys, str(scn)], capture_output=True, timeout=120)
         assert run.returncode == 0, run.stderr.decode()
-        got = _frames(run.stdout)
+        got = dumped_frames(run.stdout)
         assert len(got) == 9
         for f in range(9):
             assert got[f] == view[f], (keys, f, boxes[f])
         # without --view the keys do nothing: the frames of a run without them
         run = subprocess.run(base + ["--keys", keys, str(scn)], capture_output=True, timeout=120)
-        assert run.returncode == 0 and _frames(run.stdout) == plain
+        assert run.returncode == 0 and dumped_frames(run.stdout) == plain
     run = subprocess.run(base + [str(scn)], capture_output=True, timeout=120)
-    assert run.returncode == 0 and _frames(run.stdout) == plain
+    assert run.returncode == 0 and dumped_frames(run.stdout) == plain
     # --ppm with --view (the last key string): the box as it stands, --ppm-size clamped to it; by default the box at one cell per pixel (both sides <= 1024)
     for flags, pick in ((["--ppm-size", "20x8"], 1), ([], 2)):
         prefix = str(tmp_path / ("v%d_" % pick))
         run = subprocess.run(base + view_flags + ["--keys", keys, "--ppm", prefix] + flags + [str(scn)], capture_output=True, timeout=120)
         assert run.returncode == 0, run.stderr.decode()
-        assert _frames(run.stdout) == view
+        assert dumped_frames(run.stdout) == view
         for f in range(9):
             want = tmp_path / "want.ppm"
             ea.write_ppm(str(want), ea.overview_rgb(images[f][pick], ea.IMAGE_COVERAGE))

@@ -13,30 +13,9 @@ and the box's copy figure from the same run.  Prints a markdown table and one JS
 import argparse
 import json
 import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-import euler_amd as ea  # noqa: E402
-from euler_amd import scenarios  # noqa: E402
-
-
-def timed(s, call, calls):
-    for _ in range(3):
-        call()
-    s.profile_enable(["misc"])
-    kern, whole = [], []
-    for _ in range(calls):
-        s.profile_reset()
-        t0 = time.perf_counter()
-        call()
-        whole.append((time.perf_counter() - t0) * 1e3)
-        kern.append(s.profile()["misc"][0])
-    s.L.euler_profile_enable(s.h, 0)
-    return kern, whole
+import numpy as np
+from cost_common import ea, kernel_ms, make
 
 
 def main():
@@ -49,11 +28,7 @@ def main():
     ap.add_argument("--raster", default="200x50", help="the overview raster of the yardstick")
     args = ap.parse_args()
     w, h = (int(t) for t in args.raster.split("x"))
-    s = ea.Simulation(args.size, args.size, dot_mode=ea.DOT_TREE, precond=ea.PRECOND_IC0_TILE, max_iterations=args.max_iterations)
-    if args.workload == "half_tank":
-        s.load_half_tank()
-    else:
-        s.load_text(getattr(scenarios, args.workload)(), upscale=True)
+    s = make(args.size, args.workload, args.max_iterations)
     for _ in range(args.warmup):
         s.step()
     res = {"size": args.size, "workload": args.workload, "warmup": args.warmup, "calls": args.calls, "raster": [w, h], "device": s.device_name(),
@@ -76,13 +51,11 @@ def main():
     for no_map in (0, 1):
         s.set_option(ea.OPT_NO_TILE_MAP, no_map)
         for name, call, per_cell_all, per_cell_wet in (("overview %d x %d" % (w, h), lambda: s.overview(w, h), 3, 8), ("diagnostics", lambda: s.diagnostics_record(), 0, 10)):
-            kern, whole = timed(s, call, args.calls)
+            k, lo, hi, wh = kernel_ms(s, call, args.calls)
             need = (per_cell_all + per_cell_wet) * (n - 2) ** 2 if no_map else per_cell_all * (n - 2) ** 2 + per_cell_wet * cells_wet
-            k = statistics.median(kern)
-            row = {"pass": name, "no_tile_map": no_map, "kernel_ms": k, "kernel_ms_min": min(kern), "kernel_ms_max": max(kern), "must_read_bytes": need,
-                   "tbps": need / (k * 1e-3) / 1e12, "call_ms": statistics.median(whole)}
+            row = {"pass": name, "no_tile_map": no_map, "kernel_ms": k, "kernel_ms_min": lo, "kernel_ms_max": hi, "must_read_bytes": need, "tbps": need / (k * 1e-3) / 1e12, "call_ms": wh}
             res["rows"].append(row)
-            print("| %s | %s | %.4f (%.4f - %.4f) | %.1f | %.2f | %.3f |" % (name, "off" if no_map else "on", k, min(kern), max(kern), need / 1e6, row["tbps"], row["call_ms"]))
+            print("| %s | %s | %.4f (%.4f - %.4f) | %.1f | %.2f | %.3f |" % (name, "off" if no_map else "on", k, lo, hi, need / 1e6, row["tbps"], row["call_ms"]))
     s.set_option(ea.OPT_NO_TILE_MAP, 0)
     s.close()
     r = res["rows"]

@@ -20,23 +20,11 @@ import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import numpy as np
+from cost_common import ROOT, ea, kernel_ms, make
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-import euler_amd as ea  # noqa: E402
-from euler_amd import scenarios  # noqa: E402
-
 DYE = (ea.F_DYE_R, ea.F_DYE_G, ea.F_DYE_B)
-
-
-def make(args, rainbow):
-    s = ea.Simulation(args.size, args.size, dot_mode=ea.DOT_TREE, precond=ea.PRECOND_IC0_TILE, max_iterations=args.max_iterations, rainbow=rainbow)
-    if args.workload == "half_tank":
-        s.load_half_tank()
-    else:
-        s.load_text(getattr(scenarios, args.workload)(), upscale=True)
-    return s
 
 
 def must_read(count, dye):
@@ -68,7 +56,7 @@ def main():
     print("| %d^2 %s | dye | tile map | kernel ms (median) | must read MB | TB/s | of the copy figure | whole call ms |" % (args.size, args.workload))
     print("|---|---|---|---|---|---|---|---|")
     for rainbow in (False, True):
-        s = make(args, rainbow)
+        s = make(args.size, args.workload, args.max_iterations, rainbow)
         res["device"] = s.device_name()
         for _ in range(args.warmup):
             s.step()
@@ -79,23 +67,12 @@ def main():
             for no_map in (0, 1):
                 s.set_option(ea.OPT_NO_TILE_MAP, no_map)
                 need = nbytes if not no_map else (23 if rainbow else 11) * (args.size - 2) ** 2
-                for _ in range(3):
-                    s.overview(w, h)
-                s.profile_enable(["misc"])
-                kern, whole = [], []
-                for _ in range(args.calls):
-                    s.profile_reset()
-                    t0 = time.perf_counter()
-                    s.overview(w, h)
-                    whole.append((time.perf_counter() - t0) * 1e3)
-                    kern.append(s.profile()["misc"][0])
-                s.L.euler_profile_enable(s.h, 0)
-                k, wh = statistics.median(kern), statistics.median(whole)
+                k, lo, hi, wh = kernel_ms(s, lambda: s.overview(w, h), args.calls)
                 tbps = need / (k * 1e-3) / 1e12
-                row = {"raster": [w, h], "dye": rainbow, "no_tile_map": no_map, "kernel_ms": k, "kernel_ms_min": min(kern), "kernel_ms_max": max(kern), "must_read_bytes": need,
+                row = {"raster": [w, h], "dye": rainbow, "no_tile_map": no_map, "kernel_ms": k, "kernel_ms_min": lo, "kernel_ms_max": hi, "must_read_bytes": need,
                        "tbps": tbps, "copy_gbps": copy_gbps, "call_ms": wh}
                 res["rows"].append(row)
-                print("| %d x %d | %s | %s | %.3f (%.3f - %.3f) | %.1f | %.2f | %.2f | %.2f |" % (w, h, "yes" if rainbow else "no", "off" if no_map else "on", k, min(kern), max(kern), need / 1e6, tbps,
+                print("| %d x %d | %s | %s | %.3f (%.3f - %.3f) | %.1f | %.2f | %.2f | %.2f |" % (w, h, "yes" if rainbow else "no", "off" if no_map else "on", k, lo, hi, need / 1e6, tbps,
                                                                                             tbps * 1e3 / copy_gbps, wh))
             s.set_option(ea.OPT_NO_TILE_MAP, 0)
         if rainbow:

@@ -16,30 +16,9 @@ Prints markdown tables and one JSON line.
 """
 import argparse
 import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import euler_amd as ea  # noqa: E402
-
-
-def make(size, max_iterations):
-    return ea.Simulation(size, size, dot_mode=ea.DOT_TREE, precond=ea.PRECOND_IC0_TILE, max_iterations=max_iterations).load_half_tank()
-
-
-def kernel_ms(s, call, calls):
-    for _ in range(3):
-        call()
-    s.profile_enable(["misc"])
-    t = []
-    for _ in range(calls):
-        s.profile_reset()
-        call()
-        t.append(s.profile()["misc"][0])
-    s.L.euler_profile_enable(s.h, 0)
-    return statistics.median(t), min(t), max(t)
+from cost_common import ea, kernel_ms, make
 
 
 def main():
@@ -54,7 +33,7 @@ def main():
     res = {"size": args.size, "whole_size": args.whole_size, "calls": args.calls}
 
     if not args.trace_leg:
-        s = make(args.size, args.max_iterations)
+        s = make(args.size, "half_tank", args.max_iterations)
         res["device"] = s.device_name()
         for _ in range(args.warmup):
             s.step()
@@ -62,7 +41,7 @@ def main():
         copy_gbps = s.copy_bandwidth(1 << 30, 10)
         mid = args.size // 2
         box = (mid - 32, args.size // 4 - 16, mid + 31, args.size // 4 + 15)      # 64 x 32 cells inside the water
-        k, lo, hi = kernel_ms(s, lambda: s.marker_raster(box, 4), args.calls)
+        k, lo, hi, _ = kernel_ms(s, lambda: s.marker_raster(box, 4), args.calls)
         inbox = int(s.marker_raster(box, 4).sum())
         yard = n * 8 / (copy_gbps * 1e9) * 1e3
         res["zoomed"] = {"box": box, "scale": 4, "n_markers": n, "in_box": inbox, "kernel_ms": k, "kernel_ms_min": lo, "kernel_ms_max": hi, "copy_gbps": copy_gbps,
@@ -76,12 +55,12 @@ def main():
         res["overview_box"] = []
         big = (mid - 1024, 2, mid + 1023, 1025)
         for b, w, h in ((box, 64, 32), (big, 200, 50), ((1, 1, args.size - 2, args.size - 2), 200, 50)):
-            k, lo, hi = kernel_ms(s, lambda: s.overview(w, h, box=b), args.calls)
+            k, lo, hi, _ = kernel_ms(s, lambda: s.overview(w, h, box=b), args.calls)
             res["overview_box"].append({"box": b, "raster": [w, h], "kernel_ms": k, "kernel_ms_min": lo, "kernel_ms_max": hi})
             print("| %s | %d x %d | %.3f (%.3f - %.3f) |" % (b, w, h, k, lo, hi))
         s.close()
 
-    s = make(args.whole_size, args.max_iterations)
+    s = make(args.whole_size, "half_tank", args.max_iterations)
     s.set_option(ea.OPT_MARKERS_TWO_PASS, 1)
     for _ in range(args.warmup):
         s.step()
@@ -94,7 +73,7 @@ def main():
         s.close()
         return
     n = s.stats().n_markers
-    k, lo, hi = kernel_ms(s, lambda: s.marker_raster(whole, 1), args.calls)
+    k, lo, hi, _ = kernel_ms(s, lambda: s.marker_raster(whole, 1), args.calls)
     s.profile_enable(["marker_bin"])
     per = []
     for _ in range(5):
