@@ -23,6 +23,7 @@ SWEEP_AUTO, SWEEP_BAND, SWEEP_SIMPLE = 0, 1, 2
 PCG_F64, PCG_F32 = 0, 1
 RESIDENT_AUTO, RESIDENT_OFF = 0, 1
 IMAGE_COVERAGE, IMAGE_DYE, IMAGE_SPEED = 0, 1, 2      # EULER_IMAGE_*: euler_overview_rgb's modes
+EDIT_SOLID, EDIT_CLEAR, EDIT_SINK, EDIT_SOURCE, EDIT_FILL, EDIT_DRAIN = range(6)      # EULER_EDIT_*: euler_edit_box's ops
 # euler_overview_px (include/euler.h): one pixel of the whole-domain overview = one box of interior cells
 OVERVIEW_DTYPE = np.dtype({"names": ["cells", "solid", "sink", "water", "marks", "max_speed2", "dye"],
                            "formats": [np.uint32, np.uint32, np.uint32, np.uint32, np.uint32, np.float32, (np.uint64, 3)],
@@ -94,6 +95,7 @@ EXPORTS = [
     "euler_overview", "euler_overview_text", "euler_overview_rgb", "euler_render_fit",
     "euler_diagnostics", "euler_diag_derive",
     "euler_overview_box", "euler_marker_raster", "euler_view_text", "euler_render_view",
+    "euler_edit_box",
 ]
 
 
@@ -174,6 +176,7 @@ def load_library():
         "euler_marker_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, C.c_size_t]),
         "euler_view_text": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
         "euler_render_view": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
+        "euler_edit_box": (C.c_int, [vp, i32, i32, i32, i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -472,6 +475,12 @@ class Simulation:
         out = {n: (float(rec[n]) if n in ("max_div", "max_speed2") else int(rec[n])) for n in DIAG_DTYPE.names}
         out.update(diag_derive(rec))
         return out
+
+    def edit_box(self, op, box):
+        """Edit box = (x0, y0, x1, y1), inclusive, and the markers in it on the device (euler_edit_box, docs/editing.md): op is one of EDIT_SOLID,
+        EDIT_CLEAR, EDIT_SINK, EDIT_SOURCE, EDIT_FILL, EDIT_DRAIN."""
+        _check(self.L.euler_edit_box(self.h, int(op), *(int(t) for t in box)))
+        return self
 
     def colorize(self):
         """The reference's 'r' key (main.c:970-973): colour the current fluid afresh."""

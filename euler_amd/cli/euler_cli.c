@@ -10,7 +10,7 @@
  * handler one character per frame ('.' = no key) so that the gate is testable without a tty.
  *
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
- *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1]
+ *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
@@ -23,6 +23,11 @@
  * h j k l pan left / down / up / right by a quarter of the box (clamped to the interior), + halves the box about its centre (never below 4 x 4 cells),
  * - doubles it (clamped) and 0 shows the whole interior; --ppm then shows the box (--ppm-size clamped to it, the default divisor rule applied to it).
  * --fit --view is a usage error.
+ * --edit (up to 64 times) edits the box of interior cells [X0, X1] x [Y0, Y1] and the markers in it on the device (euler_edit_box, docs/editing.md) right
+ * before the step that produces frame F, in command-line order (F = 0: before frame 0 is drawn); OP is one of solid clear sink source fill drain.  A
+ * malformed edit or a box outside the interior is a usage error.  With --view, and only with it, the keys X (solid) C (clear) S (sink) O (source) W (fill)
+ * D (drain) edit the BRUSH: the viewed box shrunk about its centre to a quarter of its sides - with Bw = X1 - X0 + 1: w = max(1, Bw / 4), from
+ * X0 + (Bw - w) / 2 on; the same in y.
  * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
  * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
  */
@@ -41,7 +46,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -133,7 +138,24 @@ typedef struct app {
   int view;                     /* --view: the box below is drawn and the pan / zoom keys act on it */
   int box[4];                   /* x0, y0, x1, y1, inclusive, inside the interior */
   int xi, yi;                   /* the interior: X - 2, Y - 2 */
+  int failed;                   /* a brush key's edit was refused */
 } app_t;
+
+/* ---- --edit and the brush keys: euler_edit_box (docs/editing.md) ------------------------------------------------------------------------ */
+#define MAX_EDITS 64
+typedef struct edit { int frame, op, box[4]; } edit_t;
+static const char* const k_edit_ops[6] = {"solid", "clear", "sink", "source", "fill", "drain"};      /* EULER_EDIT_* in their order */
+static int parse_edit(const char* arg, edit_t* e) {
+  char op[8], tail;
+  if (sscanf(arg, "%d:%7[a-z]:%d,%d,%d,%d%c", &e->frame, op, &e->box[0], &e->box[1], &e->box[2], &e->box[3], &tail) != 6 || e->frame < 0) return -1;
+  for (e->op = 0; e->op < 6; ++e->op) if (!strcmp(op, k_edit_ops[e->op])) return 0;
+  return -1;
+}
+static int apply_edit(euler_sim* sim, int op, const int* b) {
+  if (euler_edit_box(sim, op, b[0], b[1], b[2], b[3]) == EULER_OK) return 0;
+  fprintf(stderr, "%s\n", euler_last_error());
+  return -1;
+}
 
 /* --view's keys: pan by a quarter of the box, halve / double it about its centre, all clamped to the interior [1, xi] x [1, yi] */
 static void zoom_axis(int* lo, int* hi, int limit, int nw) {
@@ -159,6 +181,12 @@ static void view_key(app_t* a, char c) {
     zoom_axis(&b[0], &b[2], a->xi, 2 * bw < a->xi ? 2 * bw : a->xi);
     zoom_axis(&b[1], &b[3], a->yi, 2 * bh < a->yi ? 2 * bh : a->yi);
   } else if (c == '0') { b[0] = 1; b[1] = 1; b[2] = a->xi; b[3] = a->yi; }
+  else if (c && strchr("XCSOWD", c)) {      /* the brush: the box shrunk about its centre to a quarter of its sides */
+    static const int ops[6] = {EULER_EDIT_SOLID, EULER_EDIT_CLEAR, EULER_EDIT_SINK, EULER_EDIT_SOURCE, EULER_EDIT_FILL, EULER_EDIT_DRAIN};
+    const int w = bw / 4 > 1 ? bw / 4 : 1, h = bh / 4 > 1 ? bh / 4 : 1;
+    const int brush[4] = {b[0] + (bw - w) / 2, b[1] + (bh - h) / 2, b[0] + (bw - w) / 2 + w - 1, b[1] + (bh - h) / 2 + h - 1};
+    if (apply_edit(a->sim, ops[strchr("XCSOWD", c) - "XCSOWD"], brush) != 0) a->failed = 1;
+  }
 }
 
 /* process_keypress (main.c:961-980); returns 0 on 'q' */
@@ -193,6 +221,8 @@ int main(int argc, char** argv) {
   const char* stats = NULL;
   int stats_every = 1;
   int view = 0, vbox[4] = {0, 0, 0, 0};
+  edit_t edits[MAX_EDITS];
+  int n_edits = 0;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -234,6 +264,8 @@ int main(int argc, char** argv) {
       if (sscanf(argv[++i], "%d,%d,%d,%d%c", &vbox[0], &vbox[1], &vbox[2], &vbox[3], &tail) != 4) { usage(argv[0]); return 1; }
       view = 1;
     }
+    /* scripted edits of the running scene (docs/editing.md) */
+    else if (!strcmp(argv[i], "--edit") && i + 1 < argc) { if (n_edits == MAX_EDITS || parse_edit(argv[++i], &edits[n_edits++]) != 0) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
     else if (!strcmp(argv[i], "--ppm-size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &ppm_w, &ppm_h) != 2 || ppm_w < 1 || ppm_h < 1) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--ppm-every") && i + 1 < argc) { ppm_every = atoi(argv[++i]); if (ppm_every < 1) { usage(argv[0]); return 1; } }
@@ -255,6 +287,10 @@ int main(int argc, char** argv) {
   if (!scenario && !resume) { usage(argv[0]); return 1; }                                                       /* main.c:986-989 */
 
   if (view && (fit || vbox[0] < 1 || vbox[1] < 1 || vbox[2] > cfg.X - 2 || vbox[3] > cfg.Y - 2 || vbox[0] > vbox[2] || vbox[1] > vbox[3])) { usage(argv[0]); return 1; }
+  for (int k = 0; k < n_edits; ++k) {
+    const int* eb = edits[k].box;
+    if (eb[0] < 1 || eb[1] < 1 || eb[2] > cfg.X - 2 || eb[3] > cfg.Y - 2 || eb[0] > eb[2] || eb[1] > eb[3]) { usage(argv[0]); return 1; }
+  }
   const int ppm_size_given = ppm_w > 0;
   if (ppm && view) {      /* the size follows the box frame by frame (below) */
     if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
@@ -313,6 +349,9 @@ int main(int argc, char** argv) {
       if (keys) { if (keys[key_pos]) c = keys[key_pos++]; }
       else if (interactive) { if (read(STDIN_FILENO, &c, 1) == -1 && errno != EAGAIN && errno != EINTR) { perror("read"); rc_exit = 1; break; } }
       if (!handle_key(&app, c)) break;
+      if (app.failed) { rc_exit = 1; break; }
+      for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == f && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;
+      if (rc_exit) break;
       if (gated_step(&app) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
       if (pace && !dump) {                  /* 10 frames per second (main.c:1036, misc/time.c:17-32) */
         next.tv_nsec += 100000000L;
@@ -323,6 +362,8 @@ int main(int argc, char** argv) {
         else clock_nanosleep(CLOCK_MONOTONIC, TIMER_ABSTIME, &next, NULL);
       }
     }
+    else for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == 0 && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;      /* before frame 0 is drawn */
+    if (rc_exit) break;
     if (g_resized) {                        /* handle_window_size_changed (main.c:1010-1014) */
       g_resized = 0;
       if (window_size(&wx, &wy) == 0) write_all("\x1b[2J\x1b[H", 7);

@@ -764,12 +764,6 @@ extern "C" int euler_timestep(euler_sim* S, float frame_time_left, float* dt) {
   return EULER_OK;
 }
 
-// somebody other than the substep's own sequence is about to write the state: what one stage prepared for the next no longer describes it
-static void eu_state_edited(euler_sim* S) {
-  S->prebin_valid = 0;                               // (k_advect_bin_a2's counts and delete ballot)
-  if (S->maxsq_state == 2) S->maxsq_state = 1;       // (k_velocity_update_para's maxima of u, v: stale, cleared before the next accumulation)
-  S->uv_clean = 0; S->uv_zb = 0; S->tmap_valid = 0; S->utmp_clean = 0; S->countT_clean = 0;                     // (what the lean zero_bounds / the velocity update's skipped zero stores rely on)
-}
 static int run_stage(euler_sim* S, int stage, float dt) {
   if (stage != EULER_STAGE_REFRESH_COUNTS) S->prebin_valid = 0;      // (what k_advect_bin_a2 binned belongs to the refresh that follows it DIRECTLY)
   if (stage == EULER_STAGE_EXTRAPOLATE && S->maxsq_state == 2) S->maxsq_state = 1;      // (writes u, v; inside a substep the timestep has consumed the maxima long before)

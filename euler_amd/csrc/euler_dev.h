@@ -379,6 +379,12 @@ static inline void eu_state_replaced(euler_sim* S) {
   S->uv_clean = 0; S->uv_zb = 0;
   S->tmap_valid = 0; S->utmp_clean = 0; S->countT_clean = 0;
 }
+// somebody other than the substep's own sequence is about to write the state: what one stage prepared for the next no longer describes it
+static inline void eu_state_edited(euler_sim* S) {
+  S->prebin_valid = 0;                               // (k_advect_bin_a2's counts and delete ballot)
+  if (S->maxsq_state == 2) S->maxsq_state = 1;       // (k_velocity_update_para's maxima of u, v: stale, cleared before the next accumulation)
+  S->uv_clean = 0; S->uv_zb = 0; S->tmap_valid = 0; S->utmp_clean = 0; S->countT_clean = 0;                     // (what the lean zero_bounds / the velocity update's skipped zero stores rely on)
+}
 // the tile map describes both count grids and this handle's passes may use it (EULER_OPT_NO_TILE_MAP: rounds 1-5's forms)
 static inline bool eu_tile_map_on(const euler_sim* S) { return S->tmap && S->tmap_valid && !S->slab_on && S->opt[EULER_OPT_NO_TILE_MAP] == 0; }
 // launch groups implemented in the kernel files
@@ -401,6 +407,7 @@ int eu_launch_pcg_op(euler_sim* S, int op, float dt, double a, double* out);
 int eu_ordered_select(euler_sim* S, const unsigned long long* mask, size_t nwords, unsigned int* out_idx,
                       unsigned int* out_total);
 int eu_sync_marker_state(euler_sim* S);
+int eu_marker_compact(euler_sim* S, const unsigned long long* delmask);   // k_markers.hip: swap-with-last removal of the selected deletions (S->sel_idx, ms->n_deleted); ms->n is the caller's to lower
 // the host side of a read-only observer pass (k_observe.hip, docs/observer_passes.md): enter, reserve, launch, read back
 int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reason, const void* out, int x0, int y0, int x1, int y1);   // null argument, row-slab handle, nothing loaded, box inside the interior
 int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes);   // grow-only; a failure leaves the handle as it was

@@ -783,6 +783,11 @@ int eu_marker_advect_b(euler_sim* S, unsigned long long n, const unsigned int* k
   return EULER_OK;
 }
 
+int eu_marker_compact(euler_sim* S, const unsigned long long* delmask) {      // (k_edit.hip shares it)
+  LAUNCH(S, KC_MARKER_COMPACT, k_compact_markers, dim3(256), dim3(256), S->markers[S->cur], S->sel_idx, delmask, S->ms);
+  return EULER_OK;
+}
+
 int eu_launch_refresh_counts(euler_sim* S) {      // (whole-grid handles; row slabs: k_slab.hip)
   const unsigned long long n = S->n_markers_host;
   unsigned long long* delmask = S->evmask;
@@ -797,7 +802,7 @@ int eu_launch_refresh_counts(euler_sim* S) {      // (whole-grid handles; row sl
   S->prebin_valid = 0;
   rc = eu_ordered_select(S, delmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_deleted);
   if (rc) return rc;
-  LAUNCH(S, KC_MARKER_COMPACT, k_compact_markers, dim3(256), dim3(256), S->markers[S->cur], S->sel_idx, delmask, S->ms);
+  eu_marker_compact(S, delmask);
   // prev <- cur, cur <- the counters, the counters <- 0
   LAUNCH(S, KC_MARKER_BIN, k_narrow_counts<true>, dim3((S->X + 63) / 64, (S->win_hi - S->win_lo + 63) / 64), dim3(256), S->count, S->count32, S->X,
          S->win_lo, S->win_hi, S->ms, 0, S->prev_count, S->tmap, S->tmap_nx, S->tmap_n, S->tmap_valid, touch_known);

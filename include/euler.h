@@ -425,6 +425,33 @@ typedef struct euler_diag_values {   /* what a user reads off a record; all 0 wh
 int euler_diagnostics(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, euler_diag* out, size_t out_bytes);
 int euler_diag_derive(const euler_diag* rec, euler_diag_values* out);   /* host only, no GPU */
 
+/* ---- device-side scene editing (docs/editing.md) -------------------------------------------------- */
+/* Open a gate, drop a block of water, raise a wall, drain a pool while the run goes on: a box of interior cells [x0, x1] x [y0, y1] (inclusive, as for
+ * euler_diagnostics) and the markers in it are edited ON THE DEVICE; nothing but a few counters crosses to the host.  A marker is "in the box" when
+ * (floorf(m.x), floorf(m.y)) is a cell of the box.
+ *   op       masks of the box's cells                 markers                       count of the box's cells
+ *   SOLID    solid = 1, source = sink = 0             those in the box deleted      0
+ *   SINK     sink = 1, solid = source = 0             those in the box deleted      0
+ *   DRAIN    unchanged                                those in the box deleted      0
+ *   CLEAR    solid = source = sink = 0                unchanged                     unchanged
+ *   SOURCE   source = 1, solid = sink = 0, then seeded as by FILL (the parser's '?', main.c:230-232)
+ *   FILL     unchanged                                appended                      4 where seeded
+ * DELETING is refresh_marker_counts' removal (main.c:105-116) with "in the box" as its condition: the array is walked in order, a deleted marker is
+ * replaced by the current last one, which is examined next.  SEEDING is sim_init's (main.c:255-266): the eligible cells - those of the box with
+ * !solid && !sink && count == 0 after the op's mask change - are taken x outer, y inner; each appends four markers at the end of the array, marker k at
+ * x = i + (k < 2 ? 0 : 0.5f) + randf() / 2, y = j + (k % 2 ? 0 : 0.5f) + randf() / 2, the x draw first, off the handle's one xorshift stream (the
+ * sources' stream: euler_set_rng / euler_stats.rng_state), 8 draws per cell: euler_seed_markers over the eligible mask from the current state.  A draw
+ * of exactly 1.0 puts a marker on its cell's far edge; the next refresh counts it where it lies.
+ * With E eligible cells and n markers, n + 4 E > 4 X Y - 1: EULER_EINVAL, the state unchanged.  Not touched: u, v, utmp, vtmp, prev_count, precon, the
+ * dye (euler_colorize recolours), the frame and solver counters, the exhausted latch; the next substep's stages meet the new masks as the reference's
+ * would.  A continuation is therefore the reference's from the edited state, bit for bit, and equals loading the host-edited snapshot.
+ * Refusals, in this order: a null handle EULER_EINVAL; a row-slab handle EULER_ESTATE (solid and source cells are facts a slab only gets from a load);
+ * nothing loaded EULER_ESTATE; a box outside the interior (1 <= x0 <= x1 <= X - 2, 1 <= y0 <= y1 <= Y - 2) or an unknown op EULER_EINVAL.  A refused
+ * call changes and allocates nothing.  The call works in the marker stage's scratch: no new device buffer (the source stage's draw buffer follows the number of source cells,
+ * as after euler_set_field(EULER_F_SOURCE)); it waits for the device twice. */
+enum { EULER_EDIT_SOLID = 0, EULER_EDIT_CLEAR = 1, EULER_EDIT_SINK = 2, EULER_EDIT_SOURCE = 3, EULER_EDIT_FILL = 4, EULER_EDIT_DRAIN = 5 };
+int euler_edit_box(euler_sim* sim, int32_t op, int32_t x0, int32_t y0, int32_t x1, int32_t y1);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
