@@ -11,7 +11,7 @@
 //                  mailbox is polled for the neighbour's row.
 // Every datum travels as a self-validating 16-byte granule {lo32, tag, hi32, tag} written with one
 // system-scope write-through store and read with system-scope loads - the same hand-off the IC(0) band
-// pipeline uses inside a GPU (k_pcg.hip; MI355X_MICROARCH "granule" hand-off) - so no fence, no
+// pipeline uses inside a GPU (k_sweep.hip; MI355X_MICROARCH "granule" hand-off) - so no fence, no
 // write-back of the L2 (which holds the solver's dirty vectors) and no assumption about the order in
 // which stores to a peer arrive.  The tag is the exchange's sequence number; two slot parities are enough
 // because an exchange k+2 cannot begin before every rank has finished reading exchange k (it needs their
@@ -48,7 +48,7 @@ struct P2PState {
 #define P2P_NHANDLES 4                 // mailbox, z, s, s2
 
 // stand-alone in-place all-reduce of one double (the all_zero(r) flag, euler_comm_ops.allreduce, the self-test);
-// the reductions of the PCG loop do the same inside their own last block (k_pcg.hip block_finish)
+// the reductions of the PCG loop do the same inside their own last block (k_pcg.h block_finish)
 __global__ __launch_bounds__(64) void k_p2p_allreduce(PcgScalars* sc, double* val, int is_max) {
   const double v = threadIdx.x == 0 ? *val : 0.0;
   const double t = is_max ? p2p_allreduce_block<true>(sc, v) : p2p_allreduce_block<false>(sc, v);

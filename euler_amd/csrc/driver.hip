@@ -531,7 +531,7 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
     if (rc) { euler_destroy(S); return rc; }
   }
   S->hbm_bytes = g_alloc_bytes + (S->slab_on ? eu_slab_bytes(S) : 0);
-  eu_launch_tile_table(S);      // E^-1 of an interior tile (k_pcg.hip), once per handle
+  eu_launch_tile_table(S);      // E^-1 of an interior tile (k_tile.hip), once per handle
   if (S->cfg.pcg_precision != EULER_PCG_F64 && S->cfg.pcg_precision != EULER_PCG_F32) { eu_set_error("euler_create: pcg_precision %d", S->cfg.pcg_precision); euler_destroy(S); return EULER_EINVAL; }
   if (S->cfg.pcg_precision == EULER_PCG_F32 && !eu_resident_eligible(S)) {
     eu_set_error("euler_create: EULER_PCG_F32 runs in the resident solver: one GPU, EULER_PRECOND_IC0_TILE with tiles of 16 records, EULER_DOT_TREE, "

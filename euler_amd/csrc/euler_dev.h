@@ -50,7 +50,7 @@ struct PcgScalars {
   int iters;     // apply_a calls so far (main.c:750)
   int max_iters;
   unsigned int n_chunks;        // active 16-record chunks of this solve (euler_sim.chunk_list)
-  unsigned int zfix;            // S->z holds only the halo of the solve's last z (k_pcg.hip TileArgs::zform): the pass at the end of the solve forms it whole
+  unsigned int zfix;            // S->z holds only the halo of the solve's last z (k_pcg.h TileArgs::zform): the pass at the end of the solve forms it whole
   // peer-to-peer mailboxes (comm_p2p.hip), set once by euler_p2p_connect and never reset: the mapped mailboxes of all
   // ranks, this rank, and the DEVICE-side exchange counters (only exchanges that really run count, so that the tags of
   // all ranks stay in step although launches after convergence return at once)
@@ -87,7 +87,7 @@ struct MarkerState {
   unsigned long long rng0;    // sources: the generator's state at the start of the substep's draws (the parallel draw kernel jumps from it)
 };
 
-// Band-skewed layout of the solver's private arrays (k_pcg.hip header): element (x,y) lives at
+// Band-skewed layout of the solver's private arrays (k_pcg.h): element (x,y) lives at
 // record t = x + y%64 of band y/64, lane y%64; RECORDS COME IN PAIRS: the two elements (t even, t+1) of a lane
 // are adjacent, index = ((y/64)*TS + (t & ~1))*64 + 2*(y%64) + (t & 1), so that one 16-byte access per lane
 // serves two steps of the IC(0) sweeps (a lone wave pays per memory INSTRUCTION: tools/micro/step_bench2).  A band has X + 63 live records,
@@ -250,7 +250,7 @@ struct euler_sim {
   uint8_t* chunk_part;    // this solve: some cell of the chunk is not CM_INTERIOR (the listed entry of an interior chunk carries EU_CHUNK_INTERIOR)
   size_t hbm_bytes;       // device memory this handle allocated: at creation, plus the search directions' ring when the first multi-kernel solve needs it (euler_hbm_bytes)
   int lean_ok;            // the solver arrays have only been written by solves since chunk_prev was current (else k_build_system writes them whole)
-  double* zhalo;          // tile-local mode on one GPU (k_pcg.hip tile_z_recompute): [band][T / 16][2][64] - records 0 and 15 of every tile's z; allocated by the first solve that needs them
+  double* zhalo;          // tile-local mode on one GPU (k_pcg.h tile_z_recompute): [band][T / 16][2][64] - records 0 and 15 of every tile's z; allocated by the first solve that needs them
   double* zrows;          // [band][2][X]: lane 0's / lane 63's z by column (with zhalo)
   int z_halo_last;        // the solve's last k_precond_tile left z as its halo only: the next k_search_apply forms z again (ZR)
   double* tile_table;     // [8][64][2]: E^-1 of an interior tile of 16 records (k_tile_table) - the same for every interior tile, so k_precond_tile never streams it

@@ -4,7 +4,7 @@
 //     z = M_tile^-1 r + P_0 V(P_0^T r)                  (multilevel: "Multilevel mode" below - a V-cycle over bilinear node grids 8, 16, 32, ... cells apart (k_mg.hip) whose top level is the
 //                                                        dense level of the two-level mode; also on row slabs)
 //
-// M_tile = the tile-local IC(0) of k_pcg.hip (64-row x 16-record blocks, one pass over memory); P = piecewise constants over coarse
+// M_tile = the tile-local IC(0) of k_tile.hip (64-row x 16-record blocks, one pass over memory); P = piecewise constants over coarse
 // cells of g x g grid cells (g = 64 m, a power of two; at most 256 coarse cells, 16 x 16 on a square grid) restricted to the fluid.
 // No reference counterpart (the reference has ONE preconditioner, main.c:580-627): this is an extension of the roofline mode, restated
 // in the oracle (eo_sim.coarse_m, coarse_correction) and compared with it to rounding.  Why: a block-local factor has no coupling
@@ -17,12 +17,11 @@
 //                  k_coarse_factor    its dense Cholesky factor, banded (half-bandwidth nx), one workgroup
 //                  k_coarse_inverse   the explicit inverse, one thread per column, columns in LDS (n <= 256: 0.5 MB) - applying the
 //                                     preconditioner is then a 256 x 256 matrix-vector product instead of two triangular solves on the critical path
-//   per iteration  k_precond_tile     (k_pcg.hip) leaves, per tile, the sums of the new r over its fluid cells by coarse column: 3 doubles
+//   per iteration  k_precond_tile     (k_tile.hip) leaves, per tile, the sums of the new r over its fluid cells by coarse column: 3 doubles
 //                  k_coarse_solve     a workgroup per coarse cell: r_c = sums of those partials in a fixed order; the last one to finish:
 //                                     y = (P^T A P)^-1 r_c, dot(z, r) += y . r_c, and the scalar epilogue (sigma / beta) k_precond_tile leaves to it
-//                  k_search_apply     (k_pcg.hip, COARSE) adds y of a cell's coarse cell to z wherever it forms s' = z + beta s
-#include "euler_dev.h"
-#include "k_mg.h"
+//                  k_search_apply     (k_search.hip, COARSE) adds y of a cell's coarse cell to z wherever it forms s' = z + beta s
+#include "k_pcg.h"
 
 #include <stdlib.h>
 
@@ -30,12 +29,7 @@
 #define CC_THREADS 1024
 #define CC_NULL_MAX 4       // fluid regions cut off from the air whose indicators are kept (k_coarse_nullfix)
 #define CC_NULL_TOTAL (CC_NULL_MAX * CC_MAX + 1 + 2 * CC_NULL_MAX + 512 * 2 * CC_NULL_MAX + 1)      // = NS_TOTAL below
-#define COMM_CALL(expr) do { if ((expr) != 0) { eu_set_error("communicator callback failed: %s", #expr); return EULER_ECOMM; } } while (0)
 
-// the scalar epilogues of k_pcg.hip (same codes)
-enum { CFIN_SIGMA_INIT = 0, CFIN_BETA = 3 };
-
-void eu_coarse_release(euler_sim* S);
 int eu_coarse_alloc(euler_sim* S, bool mg) {
   if (S->cc_null) return mg ? eu_mg_alloc(S) : EULER_OK;      // (the last allocation below: everything of the dense level is there)
   eu_coarse_release(S);                // (a failed earlier attempt may have left some of it)
@@ -486,7 +480,7 @@ int eu_launch_coarse_setup(euler_sim* S) {
 // sums of its cell (the bands of the coarse row x the tiles whose 79 columns touch the coarse column: ~300 entries for 16 x 16 coarse
 // cells on 8192^2, 1.5 MB over all - one workgroup alone took 99 us for that) in a fixed assignment of entries to threads and a fixed
 // fold, publishes r_c[c] and takes a ticket; the workgroup that draws the last ticket forms y = inv r_c (four threads per row, 0.5 MB
-// out of L2), dot(z, r) += y . r_c and the scalar epilogue.  The hand-off is the one of block_finish (k_pcg.hip): 8-byte agent-scope
+// out of L2), dot(z, r) += y . r_c and the scalar epilogue.  The hand-off is the one of block_finish (k_pcg.h): 8-byte agent-scope
 // atomics on both sides.  Nothing depends on which workgroup is last.
 __device__ __forceinline__ double cc_block_sum(double v, double* s_red) {      // valid in thread 0; fixed order
   v = eu_wave_sum(v);
@@ -501,7 +495,7 @@ __device__ __forceinline__ double cc_block_sum(double v, double* s_red) {      /
 __global__ __launch_bounds__(CC_THREADS) void k_coarse_solve(const double* __restrict__ part, const double* __restrict__ inv, double* __restrict__ y,
                                                              double* rc, unsigned int* counter, PcgScalars* sc, int fin_op, int force, int n, int nx,
                                                              int m, int shift, int ntb, int band_lo, int band_hi) {
-  if (!force && (sc->done || !sc->nonzero)) return;      // (`done` may have been raised by this very iteration's max |r|)
+  if (!force && pcg_idle(sc)) return;      // (`done` may have been raised by this very iteration's max |r|)
   __shared__ double s_rc[CC_MAX], s_q[4][CC_MAX], s_red[CC_THREADS / 64];
   __shared__ int am_last;
   const int tid = threadIdx.x, c = blockIdx.x;
@@ -553,8 +547,8 @@ __global__ __launch_bounds__(CC_THREADS) void k_coarse_solve(const double* __res
   const double t = cc_block_sum(dv, s_red);
   if (tid == 0) {
     const double v = sc->sigma_new + t;      // k_precond_tile left dot(z_tile, r) there (FIN_STORE_ONLY)
-    if (fin_op == CFIN_SIGMA_INIT) sc->sigma = v;                                                     // main.c:748
-    else if (fin_op == CFIN_BETA) { sc->sigma_new = v; sc->beta = v / sc->sigma; sc->sigma = v; }     // main.c:762-765
+    if (fin_op == FIN_SIGMA_INIT) sc->sigma = v;                                                     // main.c:748
+    else if (fin_op == FIN_BETA) { sc->sigma_new = v; sc->beta = v / sc->sigma; sc->sigma = v; }     // main.c:762-765
     else sc->sigma_new = v;
     __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next iteration
   }
@@ -571,7 +565,7 @@ int eu_launch_coarse_solve(euler_sim* S, int fin_op, int force) {
 // ---- the first search direction of a solve: s = z + P y (the memcpy at main.c:746, with the coarse part of z added on fluid cells), this rank's bands
 __global__ __launch_bounds__(256) void k_coarse_search_init(double* __restrict__ s, const double* __restrict__ z, const uint8_t* __restrict__ mask,
                                                             const double* __restrict__ y, SkewGeom g, int shift, int nx, size_t e_lo, size_t e_cnt, const PcgScalars* sc) {
-  if (sc->done || !sc->nonzero) return;
+  if (pcg_idle(sc)) return;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < e_cnt; k += (size_t)gridDim.x * blockDim.x) {
     const size_t e = e_lo + k;
     double v = z[e];
@@ -593,7 +587,7 @@ int eu_launch_coarse_search_init(euler_sim* S) {
 
 // ---- row slabs: a neighbour's edge row of z_0 (a compact row, one value per column) becomes a ghost row of the first search direction: + P y of its cells
 __global__ __launch_bounds__(256) void k_coarse_add_row(double* __restrict__ row, const double* __restrict__ y, int X, int yrow, int shift, int nx, const PcgScalars* sc) {
-  if (sc->done || !sc->nonzero) return;
+  if (pcg_idle(sc)) return;
   const int x = blockIdx.x * 256 + threadIdx.x;
   if (x < X) row[x] = row[x] + y[(size_t)(yrow >> shift) * nx + (x >> shift)];
 }

@@ -2,7 +2,7 @@
 // boundary zeroing, semi-Lagrangian velocity advection (+ gravity + bounds), pressure-system
 // assembly and the post-solve velocity update.  All are embarrassingly parallel gathers with
 // coalesced row-major access; none has a floating-point reduction except the exact max.
-#include "euler_dev.h"
+#include "k_pcg.h"
 
 #include <stdlib.h>
 
@@ -404,7 +404,6 @@ __global__ __launch_bounds__(256) void k_copy_typed(const float* __restrict__ u,
   if (y < Y - 1) vo[i] = v[i];
 }
 
-int eu_launch_diffuse(euler_sim* S, float dt);
 int eu_launch_advect_velocity(euler_sim* S, float dt) {
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
   dim3 grid((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4);
@@ -931,8 +930,6 @@ __global__ __launch_bounds__(256) void k_clamp_p(double* __restrict__ p, const u
     if ((mask[i] & CM_FLUID) && p[i] < 0.0) p[i] = 0.0;
 }
 
-int eu_launch_band_ranges(euler_sim* S);
-
 // the top bit of a listed chunk says INTERIOR (k_search_apply / k_precond_tile: no mask loads, constant coefficients, E^-1 from the table)
 __global__ __launch_bounds__(256) void k_mark_interior(unsigned int* __restrict__ list, const PcgScalars* sc, const uint8_t* __restrict__ part) {
   const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -985,7 +982,6 @@ int eu_launch_build_system(euler_sim* S, float dt) {
   return eu_launch_band_ranges(S);
 }
 
-int eu_launch_finish_p(euler_sim* S);      // k_pcg.hip: the p += alpha s still due, in memory
 // The finished, clamped pressure in memory: k_velocity_update_para forms it in LDS only.  Whoever reads S->p between two solves comes through here first.
 int eu_pressure_current(euler_sim* S) {
   if (!S->p_pending) return EULER_OK;

@@ -1,4 +1,4 @@
-// k_mg.h — internal: what the multilevel preconditioner's coarse part (k_mg.hip) shares with the fine-grid passes of k_pcg.hip and with k_coarse.hip.
+// k_mg.h — internal: what the multilevel preconditioner's coarse part (k_mg.hip) shares with the fine-grid passes (k_tile.hip, k_search.hip) and with k_coarse.hip.
 #pragma once
 
 #include "euler_dev.h"

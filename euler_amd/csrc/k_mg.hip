@@ -2,7 +2,7 @@
 //
 //     z = M_tile^-1 r + P_0 V(P_0^T r)
 //
-// M_tile = the tile-local IC(0) of k_pcg.hip.  Level 0 = a grid of NODES, node (I, J) at the centre of grid cell (8 J + 4, 8 I + 4) (MG_G0 = 8, k_mg.h: two node columns per
+// M_tile = the tile-local IC(0) of k_tile.hip.  Level 0 = a grid of NODES, node (I, J) at the centre of grid cell (8 J + 4, 8 I + 4) (MG_G0 = 8, k_mg.h: two node columns per
 // tile width, eight node rows per band); P_0 = bilinear interpolation from the four nodes around a cell (weights in eighths), restricted to the fluid, constant beyond the
 // outermost nodes.  Level l + 1 = every other node of level l in both directions (its node J sits ON node 2 J), bilinear again: weights 1, 1/2 - full weighting.  Because nodes
 // sit AT cell centres / on finer nodes, a hat is 0 at the neighbouring nodes and the Galerkin operators A_0 = P_0^T A P_0, A_(l+1) = P^T A_l P are exact NINE-POINT
@@ -25,12 +25,7 @@
 //
 // The CPU restatement the tests check all of this against: the test oracle's mg_build / mg_vcycle (same formulas; sums in another order: agreement to rounding).
 // No reference counterpart (the reference has ONE preconditioner, main.c:580-627).
-#include "euler_dev.h"
-#include "k_mg.h"
-
-#define COMM_CALL(expr) do { if ((expr) != 0) { eu_set_error("communicator callback failed: %s", #expr); return EULER_ECOMM; } } while (0)
-
-enum { MFIN_SIGMA_INIT = 0, MFIN_BETA = 3 };      // the scalar epilogues of k_pcg.hip (same codes)
+#include "k_pcg.h"
 
 // ------------------------------------------------------------------------------------------ hierarchy
 struct MgHier {
@@ -63,7 +58,6 @@ static MgHier mg_hier(const euler_sim* S) {
 }
 __device__ __forceinline__ const double* mg_sten(const MgHier& H, int l) { return H.a + 9 * (size_t)H.off[l]; }
 
-void eu_mg_release(euler_sim* S);
 // (a failed allocation gives back what the attempt already holds: the next attempt starts from nothing - ADVICE r5)
 #define MGCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { eu_mg_release(S); return eu_hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
 int eu_mg_alloc(euler_sim* S) {
@@ -579,7 +573,7 @@ template <bool GATHER>
 __global__ __launch_bounds__(MG_DOWN_THREADS) void k_mg_down(MgDownArgs A) {
   extern __shared__ double lds[];
   __shared__ int s_last;
-  if (!A.force && (A.sc->done || !A.sc->nonzero)) return;      // (the host polls late: launches queued behind convergence do no work - main.c:757 has left the loop)
+  if (!A.force && pcg_idle(A.sc)) return;      // (the host polls late: launches queued behind convergence do no work - main.c:757 has left the loop)
   const MgHier& H = A.H;
   const int tid = threadIdx.x;
   const int tiles_x = (H.nx[A.lB] + A.tile - 1) / A.tile;
@@ -732,7 +726,7 @@ __global__ __launch_bounds__(MG_UP_THREADS) void k_mg_up(MgUpArgs A) {
   __shared__ int s_last;
   const MgHier& H = A.H;
   const int tid = threadIdx.x;
-  if (!A.force && (A.sc->done || !A.sc->nonzero)) return;      // behind convergence the level arrays are dead and the scalar epilogue must not run: every workgroup leaves at once (round 6; rounds 3-5 did the whole pass and skipped the epilogue)
+  if (!A.force && pcg_idle(A.sc)) return;      // behind convergence the level arrays are dead and the scalar epilogue must not run: every workgroup leaves at once (round 6; rounds 3-5 did the whole pass and skipped the epilogue)
   // Water cut off from the air (rare): its pressure is determined up to a constant, PCG delivers the one with n . M p = 0 (M the preconditioner, n the region's indicator)
   // and the reference's clamp (main.c:773-779) makes that constant observable.  The tile-local factor alone gives, like the reference's own, very nearly "mean 0 over the
   // region"; the dense level's pseudo-inverse keeps that, the Jacobi steps of the levels in between do not - so the correction is made mean-free over the CELLS of every
@@ -930,8 +924,8 @@ __global__ __launch_bounds__(MG_UP_THREADS) void k_mg_up(MgUpArgs A) {
     if (A.fin_op == MG_FIN_SLOT) { A.sc->comm_val2 = v; if (A.sc->comm_slot) A.sc->comm_slot[1] += v; }      // (row slabs, split cycle: this rank's share travels with the pair)
     else {
       v = A.sc->sigma_new + v;      // k_precond_tile left dot(z_tile, r) there (FIN_STORE_ONLY)
-      if (A.fin_op == MFIN_SIGMA_INIT) A.sc->sigma = v;                                                       // main.c:748
-      else if (A.fin_op == MFIN_BETA) { A.sc->sigma_new = v; A.sc->beta = v / A.sc->sigma; A.sc->sigma = v; }   // main.c:762-765
+      if (A.fin_op == FIN_SIGMA_INIT) A.sc->sigma = v;                                                       // main.c:748
+      else if (A.fin_op == FIN_BETA) { A.sc->sigma_new = v; A.sc->beta = v / A.sc->sigma; A.sc->sigma = v; }   // main.c:762-765
       else A.sc->sigma_new = v;
     }
     __hip_atomic_store(A.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -952,7 +946,7 @@ __global__ __launch_bounds__(MG_UP_THREADS) void k_mg_up(MgUpArgs A) {
 template <bool GATHER>
 __global__ __launch_bounds__(MG_FINE_THREADS) void k_mg_down1(MgDownArgs A) {
   extern __shared__ double lds[];
-  if (!A.force && (A.sc->done || !A.sc->nonzero)) return;      // (as k_mg_down: nothing behind convergence)
+  if (!A.force && pcg_idle(A.sc)) return;      // (as k_mg_down: nothing behind convergence)
   const MgHier& H = A.H;
   const int tid = threadIdx.x;
   const int nx = H.nx[0], ny = H.ny[0], cnx = H.nx[1], cny = H.ny[1];
@@ -1018,7 +1012,7 @@ __global__ __launch_bounds__(MG_FINE_THREADS) void k_mg_up0(MgUpArgs A) {
   __shared__ int s_last;
   const MgHier& H = A.H;
   const int tid = threadIdx.x;
-  if (!A.force && (A.sc->done || !A.sc->nonzero)) return;      // (as k_mg_up)
+  if (!A.force && pcg_idle(A.sc)) return;      // (as k_mg_up)
   const int n_null = (int)A.nullv[MG_NULL_MAX * 256];
   const int nx = H.nx[0], ny = H.ny[0], cnx = H.nx[1], cny = H.ny[1];
   const size_t n0n = (size_t)nx * ny;
@@ -1132,8 +1126,8 @@ __global__ __launch_bounds__(MG_FINE_THREADS) void k_mg_up0(MgUpArgs A) {
     for (int k = 0; k < MG_FINE_THREADS / 64; ++k) v += s_red[k];
     if (A.slot) { A.slot[0] = v; __hip_atomic_store(A.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }      // (split cycle: the ranks' shares are summed first)
     v = A.sc->sigma_new + v;      // k_precond_tile left dot(z_tile, r) there (FIN_STORE_ONLY)
-    if (A.fin_op == MFIN_SIGMA_INIT) A.sc->sigma = v;                                                       // main.c:748
-    else if (A.fin_op == MFIN_BETA) { A.sc->sigma_new = v; A.sc->beta = v / A.sc->sigma; A.sc->sigma = v; }   // main.c:762-765
+    if (A.fin_op == FIN_SIGMA_INIT) A.sc->sigma = v;                                                       // main.c:748
+    else if (A.fin_op == FIN_BETA) { A.sc->sigma_new = v; A.sc->beta = v / A.sc->sigma; A.sc->sigma = v; }   // main.c:762-765
     else A.sc->sigma_new = v;
     __hip_atomic_store(A.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -1535,7 +1529,7 @@ __global__ __launch_bounds__(256) void k_mg_split_unpack(MgHier H, MgSplitDst D,
 // behind the cycle: the ranks' {x_0 . rhs_0 over their own rows, gauge sums} -> dot(z, r) with its epilogue; the gauge of cut-off regions on this rank's rows
 __global__ __launch_bounds__(256) void k_mg_split_fold(PcgScalars* sc, const double* __restrict__ vals, int R, int fin_op, int force, MgHier H, const double* __restrict__ nullv, const double* __restrict__ n0,
                                                        size_t nstride, const double* __restrict__ m0, int row0, int row1) {
-  const bool idle = !force && (sc->done || !sc->nonzero);
+  const bool idle = !force && pcg_idle(sc);
   if (idle) return;
   const int n_null = (int)nullv[MG_NULL_MAX * 256];
   const size_t n0n = (size_t)H.nx[0] * H.ny[0];
@@ -1543,8 +1537,8 @@ __global__ __launch_bounds__(256) void k_mg_split_fold(PcgScalars* sc, const dou
     double v = 0.0;
     for (int r = 0; r < R; ++r) v += vals[(size_t)r * (1 + MG_NULL_MAX)];
     v = sc->sigma_new + v;
-    if (fin_op == MFIN_SIGMA_INIT) sc->sigma = v;
-    else if (fin_op == MFIN_BETA) { sc->sigma_new = v; sc->beta = v / sc->sigma; sc->sigma = v; }
+    if (fin_op == FIN_SIGMA_INIT) sc->sigma = v;
+    else if (fin_op == FIN_BETA) { sc->sigma_new = v; sc->beta = v / sc->sigma; sc->sigma = v; }
     else sc->sigma_new = v;
   }
   for (int q = 0; q < n_null && q < MG_NULL_MAX; ++q) {
@@ -1790,7 +1784,7 @@ int eu_mg_setup(euler_sim* S) {
 // ------------------------------------------------------------------------------------------ P_0 at single cells (the first search direction, ghost rows, the null-space fix)
 __global__ __launch_bounds__(256) void k_mg_search_init(double* __restrict__ s, const double* __restrict__ z, const uint8_t* __restrict__ mask, const double* __restrict__ y,
                                                         SkewGeom g, int nx0, int ny0, size_t e_lo, size_t e_cnt, const PcgScalars* sc) {
-  if (sc->done || !sc->nonzero) return;
+  if (pcg_idle(sc)) return;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < e_cnt; k += (size_t)gridDim.x * blockDim.x) {
     const size_t e = e_lo + k;
     double v = z[e];
@@ -1807,7 +1801,7 @@ int eu_mg_search_init(euler_sim* S) {
   return EULER_OK;
 }
 __global__ __launch_bounds__(256) void k_mg_add_row(double* __restrict__ row, const double* __restrict__ y, int X, int yrow, int nx0, int ny0, const PcgScalars* sc) {
-  if (sc->done || !sc->nonzero) return;
+  if (pcg_idle(sc)) return;
   const int x = blockIdx.x * 256 + threadIdx.x;
   if (x < X) row[x] = row[x] + mg_interp0(y, nx0, ny0, x, yrow);
 }

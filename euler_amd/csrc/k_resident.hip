@@ -8,7 +8,7 @@
 //     r, s, p and E^-1 of the chunk's 16 x 64 cells live in the wave's registers from the first iteration to the last (64 values per lane);
 //   * A s needs the chunk's halo - the record before and after it (64 cells each), the row below lane 0 and above lane 63 (16 each): every
 //     wave publishes those cells of z and s (write-through) before the iteration's second reduction; behind it the neighbours form the halo's
-//     s' = z + beta s themselves with the owner's expression (the same bits - how the row-slab mode keeps its ghost rows, k_pcg.hip SLAB 2);
+//     s' = z + beta s themselves with the owner's expression (the same bits - how the row-slab mode keeps its ghost rows, k_search.hip SLAB 2);
 //   * the two reductions of an iteration (dot(s, A s) -> alpha; max |r| and dot(z, r) -> done, beta) are all-gathers of 16-byte
 //     {value, generation} granules, one per workgroup, written by ONE write-through store and swept by every workgroup's first wave until
 //     all carry the iteration's generation, then folded in workgroup order (the same bits everywhere, so alpha, beta and `done` need no broadcast).
@@ -22,7 +22,7 @@
 //
 // Safety: the waits are bounded (2 s); a workgroup that gives up raises *err and every workgroup leaves; the host then solves the same system
 // with the multi-kernel path (b is untouched) and stops using this kernel on the handle.
-#include "euler_dev.h"
+#include "k_pcg.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -30,8 +30,6 @@
 #define RS_THREADS 256
 #define RS_WAVES 4
 #define RS_MAX_WG 768          // granules per kind; up to 3 workgroups per CU
-#define RS_SHL1 0x130          // DPP wave shifts (k_pcg.hip): lane l <- lane l + 1, lane 63 <- the injected value
-#define RS_SHR1 0x138          // lane l <- lane l - 1, lane 0 <- the injected value
 #define RS_TIMEOUT_TICKS 200000000ull   // of the 100 MHz wall clock
 
 struct ResArgs {
@@ -95,7 +93,7 @@ __device__ __forceinline__ void rs_ld_gran4(const unsigned long long* p0, const 
 __device__ __forceinline__ double rs_gran_val(const rs_u4& w) { return __hiloint2double((int)w.y, (int)w.x); }
 __device__ __forceinline__ unsigned long long rs_gran_tag(const rs_u4& w) { return ((unsigned long long)w.w << 32) | w.z; }
 
-// one cell of the E^-1 recurrence (main.c:586-600; k_pcg.hip factor_step), in T
+// one cell of the E^-1 recurrence (main.c:586-600; k_pcg.h factor_step), in T
 template <typename T> __device__ __forceinline__ T rs_factor_step(T aa, T own, T nbv) {
   const T cl = (T)-1 * own, cb = (T)-1 * nbv;
   T e = aa - cl * cl - cb * cb;
@@ -170,7 +168,7 @@ __device__ __forceinline__ bool rs_reduce(const ResArgs& a, int nwg, double (&v)
   return true;
 }
 
-// z = M_tile^-1 r (main.c:602-626 restricted to the tile: k_pcg.hip k_precond_tile) and this wave's share of dot(z, r)
+// z = M_tile^-1 r (main.c:602-626 restricted to the tile: k_tile.hip k_precond_tile) and this wave's share of dot(z, r)
 template <typename T>
 __device__ __forceinline__ void rs_tile_solve(const T (&rr)[16], const T* ee_l, const unsigned int (&mm)[8], T (&zz)[16], double& dsum) {
   T ee[16];      // E^-1 of the chunk: read-only after the factorisation, kept in LDS between the solves ([record][lane]: conflict-free)
@@ -180,7 +178,7 @@ __device__ __forceinline__ void rs_tile_solve(const T (&rr)[16], const T* ee_l, 
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
-    const T nbv = rs_shift<RS_SHR1>(out, (T)-0.0);
+    const T nbv = rs_shift<DPP_WAVE_SHR1>(out, (T)-0.0);
     const T t = rr[j] - own - nbv;
     const T qv = t * ee[j];
     const T res = (cm & CM_FLUID) ? qv : (T)0;
@@ -192,7 +190,7 @@ __device__ __forceinline__ void rs_tile_solve(const T (&rr)[16], const T* ee_l, 
 #pragma unroll
   for (int j = 15; j >= 0; --j) {
     const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
-    const T nbv = rs_shift<RS_SHL1>(out, (T)0);
+    const T nbv = rs_shift<DPP_WAVE_SHL1>(out, (T)0);
     const T kr = ((cm & CM_RIGHT) ? (T)-1 : (T)0) * ee[j], ku = ((cm & CM_UP) ? (T)-1 : (T)0) * ee[j];
     const T t = zz[j] - kr * own - ku * nbv;
     const T zv = t * ee[j];
@@ -254,7 +252,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void k_pcg_resident(ResArgs a) {    
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
-      const T nbv = rs_shift<RS_SHR1>(out, (T)0);
+      const T nbv = rs_shift<DPP_WAVE_SHR1>(out, (T)0);
       const T res = (cm & CM_FLUID) ? rs_factor_step<T>((T)(cm >> CM_DIAG_SHIFT), own, nbv) : ee[j];
       own = res; out = res;
       ee[j] = res;
@@ -337,7 +335,7 @@ __global__ __launch_bounds__(RS_THREADS, 2) void k_pcg_resident(ResArgs a) {    
       const int cm = (int)((mm[j >> 1] >> ((j & 1) * 8)) & 0xff);
       const T left = j > 0 ? ss[j > 0 ? j - 1 : 0] : spL, right = j < 15 ? ss[j < 15 ? j + 1 : 15] : spR;
       const T ej = edge_l[j];
-      const T dn = rs_shift<RS_SHR1>(left, ej), up = rs_shift<RS_SHL1>(right, ej);
+      const T dn = rs_shift<DPP_WAVE_SHR1>(left, ej), up = rs_shift<DPP_WAVE_SHL1>(right, ej);
       T v = (T)0;
       if (cm & CM_FLUID) {      // diag, right, up, left, down: the reference's order
         v = (T)(int)(cm >> CM_DIAG_SHIFT) * ss[j];

@@ -26,7 +26,7 @@
 // Every exchange goes through the four operations of euler_comm_ops (include/euler.h): RCCL over xGMI on a node,
 // torch.distributed / gloo in the tests (2-4 ranks sharing one GPU).  Sizes are bounded per substep (SL_* below); an overflow
 // raises a sticky device error (EULER_ESTATE at the next sync) instead of corrupting anything.
-#include "euler_dev.h"
+#include "k_pcg.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -60,10 +60,7 @@ struct SlabScratch {
   unsigned long long global_sources;   // source cells of all ranks (fixed by the scenario)
 };
 
-#define COMM_CALL(expr) do { if ((expr) != 0) { eu_set_error("communicator callback failed: %s", #expr); return EULER_ECOMM; } } while (0)
-
 int eu_launch_dt(euler_sim* S, float frame_time_left);     // k_grid.hip
-int eu_launch_project(euler_sim* S, float dt);
 
 // ------------------------------------------------------------------------------------------ allocation
 int eu_slab_alloc(euler_sim* S) {

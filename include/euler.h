@@ -581,7 +581,7 @@ uint64_t euler_hbm_bytes(const euler_sim* sim);   /* device memory the handle al
 /* Diagnostics: the band pipeline of the most recent IC(0) sweep launch.  For each of this rank's bands in
  * sweep order, 8 words: wave entry, first block's boundary ready, wave exit (100 MHz constant clock
  * ticks), (blocks run << 32 | blocks that had to wait for the previous band), and four hand-off time
- * stamps that only a development build fills (k_pcg.hip SW_TRACE_HANDOFF; else 0).  `out` holds
+ * stamps that only a development build fills (k_sweep.hip SW_TRACE_HANDOFF; else 0).  `out` holds
  * 8 * cap_bands words.  Returns the number of bands written (<= cap_bands) or a negative error. */
 int euler_sweep_timeline(euler_sim* sim, uint64_t* out, int32_t cap_bands);
 

@@ -1,5 +1,5 @@
 """z formed twice (tile-local mode, one GPU): k_precond_tile leaves only z's halo and the next k_search_apply forms z again from r with the same tile
-solve (k_pcg.hip tile_solve / tile_z_recompute).  EULER_OPT_TILE_STORE_Z = 1 restores the stored form.  Two handles of one process, one per form, step
+solve (k_pcg.h tile_solve / tile_z_recompute).  EULER_OPT_TILE_STORE_Z = 1 restores the stored form.  Two handles of one process, one per form, step
 side by side: every field and solver vector - z included, which every solve leaves whole - has the same bits after every frame."""
 import numpy as np
 import pytest

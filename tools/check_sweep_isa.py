@@ -11,7 +11,7 @@ the in-order vmcnt queue exactly (every global/buffer load, store and atomic ent
 drains it down to N) and reports any instruction that reads or overwrites a register whose load is
 still in the queue.
 
-usage: check_sweep_isa.py [k_pcg.s]   (default: compiles euler_amd/csrc/k_pcg.hip to a temp file)"""
+usage: check_sweep_isa.py [k_sweep.s]   (default: compiles euler_amd/csrc/k_sweep.hip to a temp file)"""
 import os
 import re
 import subprocess
@@ -25,10 +25,10 @@ sys.setrecursionlimit(100000)
 def isa_text():
     if len(sys.argv) > 1:
         return open(sys.argv[1]).read()
-    out = os.path.join(tempfile.mkdtemp(prefix="sweep_isa_"), "k_pcg.s")
+    out = os.path.join(tempfile.mkdtemp(prefix="sweep_isa_"), "k_sweep.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "euler_amd", "csrc"), "-S",
-                           "--cuda-device-only", "-o", out, os.path.join(ROOT, "euler_amd", "csrc", "k_pcg.hip")],
+                           "--cuda-device-only", "-o", out, os.path.join(ROOT, "euler_amd", "csrc", "k_sweep.hip")],
                           stderr=subprocess.DEVNULL)
     return open(out).read()
 
