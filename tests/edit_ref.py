@@ -1,7 +1,8 @@
 """The numpy restatement of euler_edit_box (include/euler.h, docs/editing.md) on a state dict - the dicts of resident_ref.moving_state / oracle_from_state and of
 euler_amd.read_snapshot / write_snapshot - and the scenes the edit tests share (test_edit_host.py holds them to what the GPU tests need, with the oracle alone).
 
-Deleting is the literal swap-with-last loop of refresh_marker_counts (main.c:105-116) with "the marker lies in the box" as its condition; seeding is
+Deleting is the literal swap-with-last loop of refresh_marker_counts (main.c:105-116) with "the marker lies in the box" as its condition (delete_in_box, the
+definition; edit_state uses delete_in_box_vectorised, the same array for millions of markers, which test_edit_host.py holds to the loop); seeding is
 euler_amd.seed_markers (sim_init's loop, main.c:255-266) over the eligible mask, from the state's RNG.
 
 Test infrastructure only: nothing here touches the GPU."""
@@ -39,6 +40,19 @@ def delete_in_box(markers, box):
     return m[:n].copy()
 
 
+def delete_in_box_vectorised(markers, box):
+    """delete_in_box restated for millions of markers: with D markers in the box and n' = n - D, the survivors below n' stay where they are and the k-th hole
+    below n' (ascending) gets the k-th survivor at or above n', counted from the back.  test_edit_host.py holds it to the literal loop."""
+    m = np.array(markers, np.float32).reshape(-1, 2)
+    x0, y0, x1, y1 = box
+    fx, fy = np.floor(m[:, 0]), np.floor(m[:, 1])
+    gone = (x0 <= fx) & (fx <= x1) & (y0 <= fy) & (fy <= y1)
+    n1 = len(m) - int(gone.sum())
+    out = m[:n1].copy()
+    out[np.nonzero(gone[:n1])[0]] = m[n1:][~gone[n1:]][::-1]
+    return out
+
+
 def edit_state(state, op, box):
     """-> the edited copy of `state` (arrays writable); Refused when n + 4 E > 4 X Y - 1"""
     x0, y0, x1, y1 = box
@@ -50,7 +64,7 @@ def edit_state(state, op, box):
         for name, one in (("solid", ea.EDIT_SOLID), ("sink", ea.EDIT_SINK), ("source", ea.EDIT_SOURCE)):
             st[name][sl] = 1 if op == one else 0
     if op in (ea.EDIT_SOLID, ea.EDIT_SINK, ea.EDIT_DRAIN):
-        st["markers"] = delete_in_box(st["markers"], box)
+        st["markers"] = delete_in_box_vectorised(st["markers"], box)
         st["count"][sl] = 0
     if op in (ea.EDIT_SOURCE, ea.EDIT_FILL):
         elig = np.zeros((Y, X), np.uint8)
@@ -69,8 +83,7 @@ def edit_state(state, op, box):
 def bins(markers, X, Y):
     """the marker counts per cell, as the uint8 grid the refresh would leave (it wraps)"""
     m = np.asarray(markers, np.float32).reshape(-1, 2)
-    c = np.zeros((Y, X), np.int64)
-    np.add.at(c, (np.floor(m[:, 1]).astype(np.int64), np.floor(m[:, 0]).astype(np.int64)), 1)
+    c = np.bincount(np.floor(m[:, 1]).astype(np.int64) * X + np.floor(m[:, 0]).astype(np.int64), minlength=X * Y).reshape(Y, X)
     return (c % 256).astype(np.uint8)
 
 
@@ -147,3 +160,131 @@ def continued(X, Y, what, frames=FRAMES_AFTER):
         out.append(rec)
     o.close()
     return tuple(out)
+
+
+# ----------------------------------------------------------------------------- synthetic states and the structured boxes of test_gpu_edit_boxes.py
+# 260 x 200 (X % 4 == 0: the interior is two census blocks wide, 5 x 4 workgroups of the cell pass) and 203 x 131 (ragged) hold boxes of more than one 64 x 64
+# tile of the cell pass; the two small grids are the existing tests'.  grid -> (seed, n): odd and even marker counts.
+BOX_GRIDS = {(96, 64): (11, 8741), (101, 45): (12, 6300), (260, 200): (13, 76383), (203, 131): (14, 38900)}
+OP_NAMES = tuple(OPS)
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_state(X, Y, seed, n):
+    """A seeded random state dict (the keys load_state of test_gpu_edit.py consumes), read-only: about 15 % solid, 3 % sink and 3 % source interior cells, mutually
+    exclusive, the border as the loader leaves it (the upscaled dam break's); n float32 markers in non-solid interior cells (sink and source cells included), count =
+    prev_count = their bins; small random u, v in the interior, zeros elsewhere.  Cell (1, 1) is open and empty, cell (X-2, Y-2) is open and holds marker 0: the
+    two single-cell boxes are one eligible and one ineligible cell for FILL."""
+    rng = np.random.default_rng(seed)
+    st = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in base_state(X, Y, 0).items()}
+    r = rng.random((Y - 2, X - 2))
+    for name, lo, hi in (("solid", 0.0, 0.15), ("sink", 0.15, 0.18), ("source", 0.18, 0.21)):
+        st[name][1:-1, 1:-1] = (lo <= r) & (r < hi)
+        st[name][1, 1] = st[name][Y - 2, X - 2] = 0
+    for name in ("u", "v"):
+        st[name][...] = 0
+        st[name][1:-1, 1:-1] = rng.uniform(-0.1, 0.1, (Y - 2, X - 2)).astype(np.float32)
+    for name in ("utmp", "vtmp", "precon"):
+        st[name][...] = 0
+    open_ = st["solid"] == 0
+    open_[0], open_[-1], open_[:, 0], open_[:, -1] = False, False, False, False
+    open_[1, 1] = False
+    ys, xs = np.nonzero(open_)
+    pick = rng.integers(0, len(xs), n)
+    cx, cy = xs[pick].astype(np.float32), ys[pick].astype(np.float32)
+    if n:
+        cx[0], cy[0] = X - 2, Y - 2
+    # (a fraction in [0.001, 0.999]: the float32 sum stays inside the cell on every grid here)
+    m = np.stack([cx + rng.uniform(0.001, 0.999, n).astype(np.float32), cy + rng.uniform(0.001, 0.999, n).astype(np.float32)], axis=1).astype(np.float32)
+    assert np.array_equal(np.floor(m[:, 0]), cx) and np.array_equal(np.floor(m[:, 1]), cy)
+    st["markers"] = m
+    st["count"] = bins(m, X, Y)
+    st["prev_count"] = st["count"].copy()
+    st["rng_state"] = int(rng.integers(1, 1 << 63))
+    st["source_exhausted"] = 0
+    for v in st.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return st
+
+
+def edge_markers(box):
+    """eight float32 markers at the edges of the box: x exactly on x0, one ulp below it, exactly on x1 + 1, one ulp below it (y inside the box), and the same four
+    in y (x inside) -> (the markers, whether each lies in the box)"""
+    x0, y0, x1, y1 = box
+    f, down = np.float32, lambda v: np.nextafter(np.float32(v), np.float32(-np.inf))
+    xs = [f(x0), down(x0), f(x1 + 1), down(x1 + 1)]
+    ys = [f(y0), down(y0), f(y1 + 1), down(y1 + 1)]
+    m = np.array([(x, f(y0 + 0.25)) for x in xs] + [(f(x0 + 0.75), y) for y in ys], np.float32)
+    return m, np.array([True, False, False, True] * 2)
+
+
+def with_edge_markers(state, box):
+    """`state` with edge_markers(box) in its marker array: the four in x in front, the four in y behind (the grids are left as they are)"""
+    e, _ = edge_markers(box)
+    st = dict(state)
+    st["markers"] = np.concatenate([e[:4], np.asarray(state["markers"], np.float32).reshape(-1, 2), e[4:]])
+    return st
+
+
+def box_families(X, Y):
+    """-> {family: [(op name, box), ...]} for a grid of BOX_GRIDS.  A family of few boxes meets all six ops on every box; the ops of the others go round, starting
+    at another op on each grid: every op meets every family on at least one grid (test_edit_host.py checks that, and the mix of cells and markers in each)."""
+    g = list(BOX_GRIDS).index((X, Y))
+    every = lambda boxes: [(op, b) for b in boxes for op in OP_NAMES]
+    spread = lambda boxes: [(OP_NAMES[(g + i) % 6], b) for i, b in enumerate(boxes)]
+    fam = {}
+    if X % 4 == 0:      # the dword path: all 16 (x0 & 3, x1 & 3) with more than one column, and one column at each residue; heights 1 .. 5
+        boxes = []
+        for r0 in range(4):
+            for r1 in range(4):
+                i = 4 * r0 + r1
+                x0 = 4 * (1 + (5 * i) % ((X - 24) // 4)) + r0
+                boxes.append((x0, (x0 & ~3) + 4 * (1 + (r0 + r1) % 3) + r1))
+        for r in range(4):
+            x0 = 4 * (2 + 3 * r) + r
+            boxes.append((x0, x0))
+        fam["edge alignment"] = spread([(x0, 1 + (7 * i) % (Y - 7), x1, 1 + (7 * i) % (Y - 7) + i % 5) for i, (x0, x1) in enumerate(boxes)])
+    fam["single cell"] = every([(1, 1, 1, 1), (X - 2, Y - 2, X - 2, Y - 2)])
+    fam["whole interior"] = every([(1, 1, X - 2, Y - 2)])      # (the state: with_edge_markers - four of them lie in border cells, outside)
+    if Y - 2 >= 65:      # columns of more than one 64-bit word of the mask, and of more than one workgroup
+        boxes = []
+        for h in sorted({65, 67, 128, 129, Y - 2}):
+            for w in (1, 2, 3, 5):
+                if h <= Y - 2:
+                    i = len(boxes)
+                    x0, y0 = 1 + (37 * i) % (X - 2 - w), 1 + (3 * i) % (Y - 1 - h)
+                    boxes.append((x0, y0, x0 + w - 1, y0 + h - 1))
+        fam["tall and narrow"] = spread(boxes)
+    fam["wide and flat"] = every([(1, Y // 2 + 1, X - 2, Y // 2 + 1)])
+    boxes = []
+    for h in (66, 97, 131, 198):      # more than one workgroup each way: the 64-wide ones start at x0 & ~3 (X % 4 == 0) or x0, the 64-high ones at y0
+        for w in (70, 101, 150):
+            if h <= Y - 2 and w <= X - 2:
+                i = len(boxes)
+                x0, y0 = 1 + (13 * i + 2) % (X - 1 - w), 1 + (5 * i) % (Y - 1 - h)
+                boxes.append((x0, y0, x0 + w - 1, y0 + h - 1))
+    if boxes:
+        fam["across workgroups"] = spread(boxes)
+    fam["edge markers"] = every([(X // 3, Y // 3, X // 3 + 9, Y // 3 + 6)])      # (the state: with_edge_markers)
+    for cases in fam.values():
+        for _, (x0, y0, x1, y1) in cases:
+            assert 1 <= x0 <= x1 <= X - 2 and 1 <= y0 <= y1 <= Y - 2, (X, Y, x0, y0, x1, y1)
+    return fam
+
+
+def family_state(X, Y, family, box):
+    """the state a case of box_families(X, Y) starts from"""
+    st = synthetic_state(X, Y, *BOX_GRIDS[(X, Y)])
+    return with_edge_markers(st, box) if family in ("edge markers", "whole interior") else st
+
+
+def random_chain(X, Y, seed, length=12):
+    """`length` seeded random (op name, box) pairs"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(length):
+        xa, xb = sorted(int(t) for t in rng.integers(1, X - 1, 2))
+        ya, yb = sorted(int(t) for t in rng.integers(1, Y - 1, 2))
+        out.append((OP_NAMES[int(rng.integers(0, 6))], (xa, ya, xb, yb)))
+    return out

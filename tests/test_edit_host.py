@@ -145,3 +145,125 @@ def test_source_on_a_scene_without_sources_pours():
     run = er.continued(96, 64, "source")
     assert er.edited_state(96, 64, "source")["source"].sum() == 12 and not er.base_state(96, 64)["source"].any()
     assert len(run[5]["markers"]) > len(er.edited_state(96, 64, "source")["markers"])
+
+
+# ----------------------------------------------------------------------------- the vectorised delete, the synthetic states and the boxes of test_gpu_edit_boxes.py
+def _delete_cases():
+    """(name, markers, box): random cases with n from 0 to about 300, and the named ones"""
+    rng = np.random.default_rng(2024)
+    cases = []
+    for k in range(320):
+        n = int(rng.integers(0, 301))
+        x0, x1 = sorted(int(t) for t in rng.integers(1, 19, 2))
+        y0, y1 = sorted(int(t) for t in rng.integers(1, 13, 2))
+        m = np.stack([rng.uniform(0.5, 19.5, n), rng.uniform(0.5, 13.5, n)], axis=1).astype(np.float32)
+        cases.append(("random %d" % k, m, (x0, y0, x1, y1)))
+    box = (4, 3, 9, 7)
+    inside = lambda n, s: np.stack([np.random.default_rng(s).uniform(4.0, 9.99, n), np.random.default_rng(s + 1).uniform(3.0, 7.99, n)], axis=1).astype(np.float32)
+    outside = lambda n, s: np.stack([np.random.default_rng(s).uniform(10.0, 19.0, n), np.random.default_rng(s + 1).uniform(0.5, 13.0, n)], axis=1).astype(np.float32)
+    cases.append(("no marker at all", np.zeros((0, 2), np.float32), box))
+    cases.append(("nothing deleted", outside(101, 1), box))
+    cases.append(("everything deleted", inside(77, 3), box))
+    cases.append(("one marker, deleted", inside(1, 5), box))
+    cases.append(("one marker, kept", outside(1, 7), box))
+    cases.append(("the last marker deleted", np.concatenate([outside(40, 9), inside(1, 11)]), box))
+    cases.append(("a run of deleted markers at the tail", np.concatenate([outside(30, 13), inside(3, 15), outside(8, 17), inside(12, 19)]), box))
+    cases.append(("more deletions than survivors", np.concatenate([inside(20, 21), outside(7, 23), inside(30, 25), outside(4, 27), inside(2, 29)]), box))
+    cases.append(("odd n", np.concatenate([outside(25, 31), inside(25, 33), outside(25, 35), inside(26, 37)]), box))
+    e, _ = er.edge_markers(box)
+    cases.append(("the eight edge markers alone", e, box))
+    cases.append(("edge markers among others", np.concatenate([e[:3], outside(11, 39), e[3:6], inside(9, 41), e[6:]]), box))
+    cases.append(("edge markers at the tail", np.concatenate([inside(5, 43), outside(5, 45), e]), box))
+    return cases
+
+
+def test_vectorised_delete_is_the_literal_loop():
+    """er.delete_in_box_vectorised (what edit_state uses) against er.delete_in_box, the definition: bit for bit, in order"""
+    cases = _delete_cases()
+    assert len(cases) >= 300
+    seen = set()
+    for name, m, box in cases:
+        want = er.delete_in_box(m, box)
+        got = er.delete_in_box_vectorised(m, box)
+        assert got.dtype == np.float32 and got.shape == want.shape, (name, got.shape, want.shape)
+        assert_bits(got, want, name)
+        n, d = len(m), len(m) - len(want)
+        gone = np.array([er.in_box(x, y, box) for x, y in m], bool)
+        seen |= {"none" if d == 0 else "all" if d == n else "some", "odd" if n % 2 else "even"}
+        if n and gone[-1]:
+            seen.add("last")
+        if n > 2 and gone[-3:].all() and not gone.all():
+            seen.add("tail run")
+        if 2 * d > n and d < n:
+            seen.add("more deleted than kept")
+        if n == 0:
+            seen.add("empty")
+    assert seen >= {"none", "all", "some", "odd", "even", "last", "tail run", "more deleted than kept", "empty"}, seen
+    # the edge markers are in or out of the box as floor() says: on x0 in, one ulp below out, on x1 + 1 out, one ulp below in
+    box = (4, 3, 9, 7)
+    e, inside = er.edge_markers(box)
+    assert [bool(er.in_box(x, y, box)) for x, y in e] == list(inside)
+    assert e.dtype == np.float32 and e[1, 0] < 4 and e[3, 0] < 10 and np.floor(e[1, 0]) == 3 and np.floor(e[3, 0]) == 9 and e[2, 0] == 10 and e[6, 1] == 8
+    assert len(er.delete_in_box(e, box)) == 4
+
+
+@pytest.mark.parametrize("grid", list(er.BOX_GRIDS))
+def test_synthetic_states_and_box_families_show_what_the_gpu_test_needs(grid):
+    """The synthetic state of every grid of test_gpu_edit_boxes.py is a consistent state, every family of boxes has, for FILL, an eligible and an ineligible cell and a
+    marker in a box and one outside, and over the grids every op meets every family"""
+    X, Y = grid
+    seed, n = er.BOX_GRIDS[grid]
+    st = er.synthetic_state(X, Y, seed, n)
+    loaded = er.base_state(X, Y, 0)
+    inner = (slice(1, -1), slice(1, -1))
+    for f in ("solid", "sink", "source"):
+        border = np.ones((Y, X), bool)
+        border[inner] = False
+        assert np.array_equal(st[f][border], loaded[f][border]), f
+    frac = lambda a: a[inner].mean()
+    assert 0.12 < frac(st["solid"]) < 0.18 and 0.02 < frac(st["sink"]) < 0.04 and 0.02 < frac(st["source"]) < 0.04
+    assert not ((st["solid"].astype(int) + st["sink"] + st["source"])[inner] > 1).any()
+    m = st["markers"]
+    assert m.dtype == np.float32 and len(m) == n
+    mx, my = np.floor(m[:, 0]).astype(int), np.floor(m[:, 1]).astype(int)
+    assert mx.min() >= 1 and mx.max() <= X - 2 and my.min() >= 1 and my.max() <= Y - 2 and not st["solid"][my, mx].any()
+    assert st["sink"][my, mx].any()      # (markers in sink cells: what a refresh would delete, the edit leaves)
+    assert np.array_equal(st["count"], er.bins(m, X, Y)) and np.array_equal(st["prev_count"], st["count"]) and st["count"].max() < 255
+    assert np.abs(st["u"]).max() <= 0.1 and st["u"][inner].any() and st["v"][inner].any() and not st["utmp"].any() and not st["vtmp"].any() and not st["precon"].any()
+    assert st["rng_state"] > 0 and st["source_exhausted"] == 0
+    fams = er.box_families(X, Y)
+    for family, cases in fams.items():
+        elig = inel = m_in = m_out = False
+        for op, box in cases:
+            s0 = er.family_state(X, Y, family, box)
+            x0, y0, x1, y1 = box
+            sl = (slice(y0, y1 + 1), slice(x0, x1 + 1))
+            e = (s0["solid"][sl] == 0) & (s0["sink"][sl] == 0) & (s0["count"][sl] == 0)
+            fx, fy = np.floor(s0["markers"][:, 0]), np.floor(s0["markers"][:, 1])
+            inb = (x0 <= fx) & (fx <= x1) & (y0 <= fy) & (fy <= y1)
+            elig, inel, m_in, m_out = elig or e.any(), inel or not e.all(), m_in or inb.any(), m_out or not inb.all()
+        assert elig and inel and m_in and m_out, (grid, family, elig, inel, m_in, m_out)
+    assert len(er.synthetic_state(X, Y, seed, 0)["markers"]) == 0 and not er.synthetic_state(X, Y, seed, 0)["count"].any()
+
+
+def test_every_op_meets_every_box_family():
+    met, shapes = {}, {}
+    for X, Y in er.BOX_GRIDS:
+        for family, cases in er.box_families(X, Y).items():
+            met.setdefault(family, set()).update(op for op, _ in cases)
+            shapes.setdefault(family, []).extend((X, Y, b) for _, b in cases)
+    assert set(met) == {"edge alignment", "single cell", "whole interior", "tall and narrow", "wide and flat", "across workgroups", "edge markers"}
+    for family, ops in met.items():
+        assert ops == set(er.OP_NAMES), (family, ops)
+    # edge alignment: on both X % 4 == 0 grids all 16 (x0 & 3, x1 & 3) and one column at each residue, heights 1 .. 5
+    for g in ((96, 64), (260, 200)):
+        bs = [b for X, Y, b in shapes["edge alignment"] if (X, Y) == g]
+        assert {(b[0] & 3, b[2] & 3) for b in bs if b[2] > b[0]} == {(a, c) for a in range(4) for c in range(4)}
+        assert {b[0] & 3 for b in bs if b[2] == b[0]} == {0, 1, 2, 3} and {b[3] - b[1] + 1 for b in bs} == {1, 2, 3, 4, 5}
+    for g in ((260, 200), (203, 131)):
+        bs = [b for X, Y, b in shapes["tall and narrow"] if (X, Y) == g]
+        assert {(b[2] - b[0] + 1, b[3] - b[1] + 1) for b in bs} >= {(w, h) for w in (1, 2, 3, 5) for h in (65, 67, 128, 129, g[1] - 2)}
+    bs = [b for X, Y, b in shapes["across workgroups"]]
+    assert {b[3] - b[1] + 1 for b in bs} == {66, 97, 131, 198} and min(b[2] - b[0] + 1 for b in bs) >= 70
+    assert {((b[0] - (b[0] & ~3)), b[1] > 1) for X, Y, b in shapes["across workgroups"] if X % 4 == 0} >= {(1, True), (3, True)}      # (unaligned in x, off the floor in y)
+    assert max(len([1 for X, Y, b in shapes[f] if (X, Y) == g]) for f in shapes for g in er.BOX_GRIDS) <= 24 and all(sum(len(c) for c in er.box_families(*g).values()) <= 90 for g in er.BOX_GRIDS)

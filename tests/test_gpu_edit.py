@@ -1,6 +1,7 @@
 """euler_edit_box on the GPU (docs/editing.md) against its numpy restatement (tests/edit_ref.py) and the oracle: the edit itself, the continuation from the edited
 state, the device edit against a load of the host-edited snapshot in every solver / advection mode, the lean stage forms, the observers right after an edit, the
-refusals and the source bookkeeping.  Grids 96 x 64, 101 x 45 (ragged: X % 4 != 0) and 130 x 70 (tile boundaries in x and y), all below 12 k markers."""
+refusals and the source bookkeeping.  Grids 96 x 64, 101 x 45 (ragged: X % 4 != 0) and 130 x 70 (tile boundaries in x and y): six hand-placed boxes of at most 22 x 21 cells, at most 12 k markers.
+Boxes of several workgroups, every edge alignment, markers on a box's edges and the paths only millions of markers or cells reach: test_gpu_edit_boxes.py."""
 import numpy as np
 import pytest
 
