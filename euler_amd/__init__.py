@@ -33,6 +33,12 @@ DIAG_CROWDED = 8      # EULER_DIAG_CROWDED
 DIAG_DTYPE = np.dtype({"names": ["cells", "fluid", "markers", "crowded", "mass_x", "mass_y", "div_l1", "ke_hi", "ke_lo", "count_max", "nonfinite", "max_div", "max_speed2"],
                        "formats": [np.uint64] * 9 + [np.uint32, np.uint32, np.float32, np.float32],
                        "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 84], "itemsize": 88})
+# euler_flow_px (include/euler.h): one pixel of the flow raster; EULER_FLOW_* flags of euler_flow_raster, EULER_PAINT_* fields of euler_flow_paint
+FLOW_PRESSURE = 1
+PAINT_VORTICITY, PAINT_PRESSURE, PAINT_SPEED = 0, 1, 2
+FLOW_DTYPE = np.dtype({"names": ["cells", "water", "nodes", "nonfinite", "u_pos", "u_neg", "v_pos", "v_neg", "w_pos", "w_neg", "p_sum", "max_speed2", "max_abs_w", "max_p", "reserved"],
+                       "formats": [np.uint32] * 4 + [np.uint64] * 7 + [np.float32] * 3 + [np.uint32],
+                       "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 84], "itemsize": 88})
 DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
  F_PRESSURE, F_PCG_B, F_PCG_R, F_PCG_Z, F_PCG_S, F_PCG_Q, F_CELLMASK,
@@ -96,6 +102,7 @@ EXPORTS = [
     "euler_diagnostics", "euler_diag_derive",
     "euler_overview_box", "euler_marker_raster", "euler_view_text", "euler_render_view",
     "euler_edit_box",
+    "euler_flow_raster", "euler_flow_paint",
 ]
 
 
@@ -177,6 +184,8 @@ def load_library():
         "euler_view_text": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
         "euler_render_view": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, C.c_char_p, i32, C.POINTER(i32)]),
         "euler_edit_box": (C.c_int, [vp, i32, i32, i32, i32, i32]),
+        "euler_flow_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_flow_paint": (C.c_int, [vp, vp, i32, i32, i32, f64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -189,6 +198,12 @@ def load_library():
 def _check(rc):
     if rc != 0:
         raise EulerError(rc, load_library().euler_last_error().decode(errors="replace"))
+
+
+def _check_host(rc, who):
+    """a host-only formatter that refuses leaves no message behind"""
+    if rc != 0:
+        raise EulerError(rc, "%s refused its arguments" % who)
 
 
 # --- host-only helpers (no GPU) ------------------------------------------------------------------
@@ -271,6 +286,18 @@ def view_text(cells, raster, scale, rainbow=False):
     buf = C.create_string_buffer(max(n.value, 1))
     _check(L.euler_view_text(cells.ctypes.data, raster.ctypes.data, bw, bh, int(scale), int(rainbow), buf, n.value, C.byref(n)))
     return buf.raw[: n.value]
+
+
+def flow_paint(flow, px, field, scale):
+    """A painted copy of the overview records px: their dye sums show `field` (PAINT_VORTICITY, PAINT_PRESSURE, PAINT_SPEED) of the flow records of the
+    same box, raster and state at `scale` (euler_flow_paint), so that overview_text / view_text with rainbow and overview_rgb(IMAGE_DYE) draw it."""
+    px = _overview_records(px).copy()
+    flow = np.ascontiguousarray(flow, FLOW_DTYPE)
+    if flow.shape != px.shape:
+        raise ValueError("flow_paint: flow records of shape %r for overview records of shape %r" % (flow.shape, px.shape))
+    h, w = px.shape
+    _check_host(load_library().euler_flow_paint(flow.ctypes.data, px.ctypes.data, w, h, int(field), float(scale)), "euler_flow_paint")
+    return px
 
 
 def write_ppm(path, rgb):
@@ -433,6 +460,15 @@ class Simulation:
             _check(self.L.euler_overview(self.h, w, h, dst, px.nbytes))
         else:
             _check(self.L.euler_overview_box(self.h, *(int(t) for t in box), w, h, dst, px.nbytes))
+        return px
+
+    def flow(self, w, h, box=None, pressure=False):
+        """The flow raster of the whole interior, or of box = (x0, y0, x1, y1) inclusive, over the pixels of overview(w, h, box) (euler_flow_raster): signed
+        sums of the velocity and of the vorticity with their maxima, with pressure=True also of the pressure: an array of FLOW_DTYPE, shape (h, w), row 0 = top."""
+        x0, y0, x1, y1 = (1, 1, self.X - 2, self.Y - 2) if box is None else (int(t) for t in box)
+        px = np.zeros((max(int(h), 0), max(int(w), 0)), FLOW_DTYPE)
+        dst = px.ctypes.data if px.size else np.zeros(1, FLOW_DTYPE).ctypes.data
+        _check(self.L.euler_flow_raster(self.h, x0, y0, x1, y1, w, h, FLOW_PRESSURE if pressure else 0, dst, px.nbytes))
         return px
 
     def marker_raster(self, box, scale):

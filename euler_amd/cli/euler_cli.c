@@ -11,7 +11,8 @@
  *
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
- *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>
+ *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
+ *         [--paint vorticity:S|pressure:S|speed:S] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
@@ -28,6 +29,11 @@
  * malformed edit or a box outside the interior is a usage error.  With --view, and only with it, the keys X (solid) C (clear) S (sink) O (source) W (fill)
  * D (drain) edit the BRUSH: the viewed box shrunk about its centre to a quarter of its sides - with Bw = X1 - X0 + 1: w = max(1, Bw / 4), from
  * X0 + (Bw - w) / 2 on; the same in y.
+ * --paint colours the frame of --fit / --view (both of its regimes) and the images of --ppm by a field of the flow raster (euler_flow_raster + euler_flow_paint,
+ * docs/flow_raster.md) in place of the dye: the mean vorticity of a pixel from blue (-S) over white to red (+S), its mean pressure or the speed of its mean
+ * velocity from blue (0) to red (S and above); the images are then written in the dye mode.  The pressure is reduced only for pressure:.  It needs --fit, --view
+ * or --ppm: on its own it is a usage error.  With --view, and only with it, the key v cycles unpainted -> vorticity -> pressure -> speed at the scales given
+ * or the defaults 1, 1000 and 10.
  * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
  * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
  */
@@ -46,7 +52,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -90,14 +96,32 @@ static int window_size(int* wx, int* wy) {
 }
 
 /* ---- --ppm: the whole interior, or the box of --view, as a binary PPM (euler_overview / euler_overview_box + euler_overview_rgb) ---------------- */
-static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const int* box, int W, int H, int mode, float scale) {
+/* --paint: the field of the flow raster over the box (NULL: the whole interior of xi x yi cells) and raster of the records px, painted into their dye sums */
+static int paint_records(euler_sim* sim, const int* box, int xi, int yi, euler_overview_px* px, int W, int H, int field, double scale) {
+  const size_t n = (size_t)W * (size_t)H;
+  euler_flow_px* fl = (euler_flow_px*)malloc(n * sizeof *fl);
+  if (!fl) { fprintf(stderr, "--paint: out of memory\n"); return -1; }
+  int rc = euler_flow_raster(sim, box ? box[0] : 1, box ? box[1] : 1, box ? box[2] : xi, box ? box[3] : yi, W, H, field == EULER_PAINT_PRESSURE ? EULER_FLOW_PRESSURE : 0, fl, n * sizeof *fl);
+  if (rc != EULER_OK) fprintf(stderr, "%s\n", euler_last_error());
+  else if ((rc = euler_flow_paint(fl, px, W, H, field, scale)) != EULER_OK) fprintf(stderr, "--paint: the flow records do not match the overview's\n");
+  free(fl);
+  return rc == EULER_OK ? 0 : -1;
+}
+
+/* paint < 0: unpainted; else the records are painted with that field at pscale and the image is written in the dye mode */
+static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const int* box, int xi, int yi, int W, int H, int mode, float scale, int paint, double pscale) {
   const size_t n = (size_t)W * (size_t)H;
   euler_overview_px* px = (euler_overview_px*)malloc(n * sizeof *px);
   uint8_t* rgb = (uint8_t*)malloc(n * 3);
   char* path = (char*)malloc(strlen(prefix) + 32);
   int ok = px && rgb && path;
   if (!ok) fprintf(stderr, "--ppm: out of memory\n");
-  if (ok && ((box ? euler_overview_box(sim, box[0], box[1], box[2], box[3], W, H, px, n * sizeof *px) : euler_overview(sim, W, H, px, n * sizeof *px)) != EULER_OK || euler_overview_rgb(px, W, H, mode, scale, rgb, n * 3) != EULER_OK)) {
+  if (ok && (box ? euler_overview_box(sim, box[0], box[1], box[2], box[3], W, H, px, n * sizeof *px) : euler_overview(sim, W, H, px, n * sizeof *px)) != EULER_OK) {
+    fprintf(stderr, "%s\n", euler_last_error());
+    ok = 0;
+  }
+  if (ok && paint >= 0 && paint_records(sim, box, xi, yi, px, W, H, paint, pscale) != 0) ok = 0;
+  if (ok && euler_overview_rgb(px, W, H, paint >= 0 ? EULER_IMAGE_DYE : mode, scale, rgb, n * 3) != EULER_OK) {
     fprintf(stderr, "%s\n", euler_last_error());
     ok = 0;
   }
@@ -139,7 +163,44 @@ typedef struct app {
   int box[4];                   /* x0, y0, x1, y1, inclusive, inside the interior */
   int xi, yi;                   /* the interior: X - 2, Y - 2 */
   int failed;                   /* a brush key's edit was refused */
+  int paint;                    /* --paint / the key v: -1 unpainted, else EULER_PAINT_* */
+  double paint_scale[3];        /* the scale of each field: the one given, else 1, 1000, 10 */
 } app_t;
+
+/* ---- --paint: the frame of --fit / --view with the flow field in place of the dye (docs/flow_raster.md) ----------------------------------- */
+static int parse_paint(const char* arg, int* field, double* scale) {
+  static const char* const fmt[3] = {"vorticity:%lf%c", "pressure:%lf%c", "speed:%lf%c"};      /* EULER_PAINT_* in their order */
+  char tail;
+  for (*field = 0; *field < 3; ++*field)
+    if (sscanf(arg, fmt[*field], scale, &tail) == 1) return *scale > 0.0 && *scale <= 1.7976931348623157e308 ? 0 : -1;
+  return -1;
+}
+/* what euler_render_fit (view = 0: b is the whole interior) and euler_render_view (view = 1) draw, from the same records painted; a malloc'd frame, NULL on failure */
+static char* painted_frame(app_t* a, const int* b, int view, int wx, int wy, int32_t* len) {
+  if (wx < 1 || wy < 1) { fprintf(stderr, "--paint: a window of %d x %d\n", wx, wy); return NULL; }
+  const int bw = b[2] - b[0] + 1, bh = b[3] - b[1] + 1;
+  int scale = 0;      /* euler_render_view's rule; 0: at or below one cell per glyph */
+  if (view && (long long)bw * 2 <= wx && (long long)bh * 2 <= wy)
+    for (scale = 16; (long long)bw * scale > wx || (long long)bh * scale > wy; scale >>= 1) {}
+  const int W = scale ? bw : (wx < bw ? wx : bw), H = scale ? bh : (wy < bh ? wy : bh);
+  const size_t n = (size_t)W * (size_t)H, rbytes = scale ? (size_t)bw * scale * bh * scale * sizeof(uint32_t) : 0;
+  euler_overview_px* px = (euler_overview_px*)malloc(n * sizeof *px);
+  uint32_t* ras = scale ? (uint32_t*)malloc(rbytes) : NULL;
+  char* out = NULL;
+  int ok = px && (!scale || ras);
+  if (!ok) fprintf(stderr, "--paint: out of memory\n");
+  if (ok && (euler_overview_box(a->sim, b[0], b[1], b[2], b[3], W, H, px, n * sizeof *px) != EULER_OK ||
+             (scale && euler_marker_raster(a->sim, b[0], b[1], b[2], b[3], scale, ras, rbytes) != EULER_OK))) { fprintf(stderr, "%s\n", euler_last_error()); ok = 0; }
+  if (ok && paint_records(a->sim, b, a->xi, a->yi, px, W, H, a->paint, a->paint_scale[a->paint]) != 0) ok = 0;
+  for (int pass = 0; ok && pass < 2; ++pass) {      /* the sizing protocol: the length, then the bytes */
+    const int32_t cap = pass ? *len : 0;
+    if (pass && !(out = (char*)malloc((size_t)cap + 1))) { fprintf(stderr, "--paint: out of memory\n"); ok = 0; break; }
+    if ((scale ? euler_view_text(px, ras, bw, bh, scale, 1, out, cap, len) : euler_overview_text(px, W, H, 1, out, cap, len)) != EULER_OK) { fprintf(stderr, "--paint: the frame formatter refused\n"); ok = 0; }
+  }
+  free(px); free(ras);
+  if (!ok) { free(out); out = NULL; }
+  return out;
+}
 
 /* ---- --edit and the brush keys: euler_edit_box (docs/editing.md) ------------------------------------------------------------------------ */
 #define MAX_EDITS 64
@@ -181,6 +242,7 @@ static void view_key(app_t* a, char c) {
     zoom_axis(&b[0], &b[2], a->xi, 2 * bw < a->xi ? 2 * bw : a->xi);
     zoom_axis(&b[1], &b[3], a->yi, 2 * bh < a->yi ? 2 * bh : a->yi);
   } else if (c == '0') { b[0] = 1; b[1] = 1; b[2] = a->xi; b[3] = a->yi; }
+  else if (c == 'v') a->paint = a->paint == EULER_PAINT_SPEED ? -1 : a->paint + 1;      /* unpainted -> vorticity -> pressure -> speed -> unpainted */
   else if (c && strchr("XCSOWD", c)) {      /* the brush: the box shrunk about its centre to a quarter of its sides */
     static const int ops[6] = {EULER_EDIT_SOLID, EULER_EDIT_CLEAR, EULER_EDIT_SINK, EULER_EDIT_SOURCE, EULER_EDIT_FILL, EULER_EDIT_DRAIN};
     const int w = bw / 4 > 1 ? bw / 4 : 1, h = bh / 4 > 1 ? bh / 4 : 1;
@@ -223,6 +285,8 @@ int main(int argc, char** argv) {
   int view = 0, vbox[4] = {0, 0, 0, 0};
   edit_t edits[MAX_EDITS];
   int n_edits = 0;
+  int paint = -1;
+  double paint_scale[3] = {1.0, 1000.0, 10.0};
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -277,6 +341,12 @@ int main(int argc, char** argv) {
       else if (sscanf(v, "speed:%f%c", &ppm_scale, &tail) == 1 && ppm_scale > 0.f) ppm_mode = EULER_IMAGE_SPEED;
       else { usage(argv[0]); return 1; }
     }
+    /* a field of the flow raster in place of the dye (docs/flow_raster.md) */
+    else if (!strcmp(argv[i], "--paint") && i + 1 < argc) {
+      double sc;
+      if (parse_paint(argv[++i], &paint, &sc) != 0) { usage(argv[0]); return 1; }
+      paint_scale[paint] = sc;
+    }
     /* the flow diagnostics as CSV (docs/diagnostics.md) */
     else if (!strcmp(argv[i], "--stats") && i + 1 < argc) stats = argv[++i];
     else if (!strcmp(argv[i], "--stats-every") && i + 1 < argc) { stats_every = atoi(argv[++i]); if (stats_every < 1) { usage(argv[0]); return 1; } }
@@ -291,6 +361,7 @@ int main(int argc, char** argv) {
     const int* eb = edits[k].box;
     if (eb[0] < 1 || eb[1] < 1 || eb[2] > cfg.X - 2 || eb[3] > cfg.Y - 2 || eb[0] > eb[2] || eb[1] > eb[3]) { usage(argv[0]); return 1; }
   }
+  if (paint >= 0 && !fit && !view && !ppm) { usage(argv[0]); return 1; }
   const int ppm_size_given = ppm_w > 0;
   if (ppm && view) {      /* the size follows the box frame by frame (below) */
     if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
@@ -321,6 +392,8 @@ int main(int argc, char** argv) {
   app.rainbow = cfg.rainbow;
   app.view = view; app.xi = cfg.X - 2; app.yi = cfg.Y - 2;
   memcpy(app.box, vbox, sizeof vbox);
+  app.paint = paint;
+  memcpy(app.paint_scale, paint_scale, sizeof paint_scale);
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK) {
@@ -370,26 +443,33 @@ int main(int argc, char** argv) {
     }
     int32_t len = 0;
     const int* b = app.box;
+    const int whole[4] = {1, 1, app.xi, app.yi};
+    char* painted = NULL;      /* --paint / the key v: the frame of --fit / --view from the painted records */
+    if (app.paint >= 0 && (fit || view) && !(painted = painted_frame(&app, view ? b : whole, view, wx, wy, &len))) { rc_exit = 1; break; }
 #define RENDER(out, cap) (view ? euler_render_view(app.sim, b[0], b[1], b[2], b[3], wx, wy, (out), (cap), &len) : render(app.sim, wx, wy, (out), (cap), &len))
-    if (RENDER(NULL, 0) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
-    if (len > cap) {
+    if (painted) {}
+    else if (RENDER(NULL, 0) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    if (!painted && len > cap) {
       cap = len + 4096;
       char* nb = (char*)realloc(buf, (size_t)cap);
       if (!nb) { rc_exit = 1; break; }
       buf = nb;
     }
-    if (RENDER(buf, cap) != EULER_OK || len > cap) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
+    if (!painted && (RENDER(buf, cap) != EULER_OK || len > cap)) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
     if (dump) {
       printf("--- frame %d (%d bytes)\n", f, (int)len);
-      fwrite(buf, 1, (size_t)len, stdout);
+      fwrite(painted ? painted : buf, 1, (size_t)len, stdout);
       printf("\n");
     } else {                               /* draw (main.c:953-959) */
       fflush(stdout);
       write_all("\x1b[H", 3);              /* reposition cursor */
-      write_all(buf, (size_t)len);
+      write_all(painted ? painted : buf, (size_t)len);
       write_all("\x1b[?25l", 6);           /* hide cursor */
     }
 #undef RENDER
+    free(painted);
+    const int pf = app.paint;
+    const double ps = pf >= 0 ? app.paint_scale[pf] : 0.0;
     if (ppm && view && f % ppm_every == 0) {      /* the box as it stands: --ppm-size clamped to it, else the divisor rule of the whole interior applied to it */
       const int bw = b[2] - b[0] + 1, bh = b[3] - b[1] + 1;
       int w = ppm_w < bw ? ppm_w : bw, h = ppm_h < bh ? ppm_h : bh;
@@ -398,8 +478,8 @@ int main(int argc, char** argv) {
         while (bw / d > 1024 || bh / d > 1024) ++d;
         w = bw / d > 1 ? bw / d : 1; h = bh / d > 1 ? bh / d : 1;
       }
-      if (write_ppm_frame(app.sim, ppm, f, b, w, h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
-    } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, ppm_w, ppm_h, ppm_mode, ppm_scale) != 0) { rc_exit = 1; break; }
+      if (write_ppm_frame(app.sim, ppm, f, b, app.xi, app.yi, w, h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
+    } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, app.xi, app.yi, ppm_w, ppm_h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
     if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }

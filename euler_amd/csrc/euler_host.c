@@ -1,7 +1,8 @@
 /*
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
  * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
- * whole-domain overview's records (text through the same frame formatter, RGB), the magnified frame of the viewport, and the values derived from a diagnostics record.
+ * whole-domain overview's records (text through the same frame formatter, RGB), the magnified frame of the viewport, the values derived from a diagnostics record,
+ * and the painter that shows a field of the flow raster through those formatters.
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -408,5 +409,44 @@ int euler_diag_derive(const euler_diag* rec, euler_diag_values* out) {
   out->com_y = (double)rec->mass_y / markers;
   out->markers_per_cell = markers / fluid;
   out->crowded_fraction = (double)rec->crowded / fluid;
+  return EULER_OK;
+}
+
+/* ---- flow raster: a field of euler_flow_px records painted into the dye sums of overview records (include/euler.h, docs/flow_raster.md) ---- */
+
+static uint32_t paint_q24(float x) {      /* q(x) of euler_overview_px */
+  const float c = x > 0.f ? (x > 1.f ? 1.f : x) : 0.f;
+  return (uint32_t)(c * 16777216.f);
+}
+static double paint_clamp(double t, double lo) { return t < lo ? lo : (t > 1.0 ? 1.0 : t); }
+
+int euler_flow_paint(const euler_flow_px* flow, euler_overview_px* px, int32_t W, int32_t H, int32_t field, double scale) {
+  if (!flow || !px || W < 1 || H < 1) return EULER_EINVAL;
+  if (field != EULER_PAINT_VORTICITY && field != EULER_PAINT_PRESSURE && field != EULER_PAINT_SPEED) return EULER_EINVAL;
+  if (!(scale > 0.0) || !isfinite(scale)) return EULER_EINVAL;
+  const size_t n = (size_t)W * (size_t)H;
+  for (size_t k = 0; k < n; ++k)      /* the two rasters are of one box, raster and state */
+    if (flow[k].cells != px[k].cells || flow[k].water != px[k].water) return EULER_EINVAL;
+  for (size_t k = 0; k < n; ++k) {
+    const euler_flow_px* f = flow + k;
+    const double water = (double)f->water;
+    double lin[3];
+    if (field == EULER_PAINT_VORTICITY) {
+      const double m = f->nodes ? ((double)f->w_pos - (double)f->w_neg) / 1048576.0 / (double)f->nodes : 0.0;
+      const double t = paint_clamp(m / scale, -1.0);
+      if (t >= 0.0) { lin[0] = 1.0; lin[1] = 1.0 - t; lin[2] = 1.0 - t; }
+      else { lin[0] = 1.0 + t; lin[1] = 1.0 + t; lin[2] = 1.0; }
+    } else {
+      double m = 0.0;
+      if (f->water && field == EULER_PAINT_PRESSURE) m = (double)f->p_sum / 256.0 / water;
+      else if (f->water) {
+        const double mu = ((double)f->u_pos - (double)f->u_neg) / 1048576.0 / water, mv = ((double)f->v_pos - (double)f->v_neg) / 1048576.0 / water;
+        m = sqrt(mu * mu + mv * mv);
+      }
+      const double t = paint_clamp(m / scale, 0.0);
+      lin[0] = t; lin[1] = 0.5; lin[2] = 1.0 - t;
+    }
+    for (int c = 0; c < 3; ++c) px[k].dye[c] = (uint64_t)f->water * paint_q24((float)lin[c]);
+  }
   return EULER_OK;
 }

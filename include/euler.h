@@ -425,6 +425,52 @@ typedef struct euler_diag_values {   /* what a user reads off a record; all 0 wh
 int euler_diagnostics(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, euler_diag* out, size_t out_bytes);
 int euler_diag_derive(const euler_diag* rec, euler_diag_values* out);   /* host only, no GPU */
 
+/* ---- flow raster (docs/flow_raster.md) ------------------------------------------------------------ */
+/* Where does the water turn, which way does it move, how is the pressure spread?  The box, the raster and the pixel geometry of euler_overview_box
+ * (a flow pixel covers the cells of the overview pixel at the same index), reduced on the device to the record below.  Per cell i = y * X + x, in
+ * float32 without contraction; WATER is the overview's: !solid && !sink && count > 0.
+ *   dx = (u[i] + u[i-1]) / 2, dy = (v[i] + v[i-X]) / 2        the cell-centre velocity of a water cell (euler_overview_px.max_speed2)
+ *   w  = (v[i+1] - v[i]) - (u[i+X] - u[i])                    the vorticity (h = 1) at the NODE of cell (x, y), its top-right corner; the node is WET when
+ *                                                             the cells i, i+1, i+X, i+X+1 are all water, and belongs to the pixel of cell (x, y) (for a cell in
+ *                                                             the box's last column or top row the neighbours lie outside the box, inside the grid)
+ *   pf = (float)p                                             p: the double euler_get_field(EULER_F_PRESSURE) returns for a water cell
+ *   qv(a) = (uint64_t)((a < 4096.f ? a : 4096.f) * 1048576.f), a >= 0                               2^-20 units, saturating at 2^12
+ *   qp(a) = (uint64_t)((a > 0.f ? (a < 16777216.f ? a : 16777216.f) : 0.f) * 256.f)                 2^-8 units, saturating at 2^24
+ * Both scales are powers of two: the multiply is exact, the conversion truncates - the same on host and device.  A NaN term adds nothing to its sums
+ * and maxima; an infinity saturates its sum and shows in its maximum; -0.f counts on the positive side with 0.  No sum can wrap (a term is at most 2^32,
+ * a grid has at most 2^28 cells).  Every field is an integer sum or a maximum of non-negative floats taken on their bit patterns: the record does not
+ * depend on the launch geometry, the atomics or the tile map (tests compare bits). */
+enum { EULER_FLOW_PRESSURE = 1 };   /* flags: also reduce the pressure (p_sum, max_p) */
+typedef struct euler_flow_px {   /* 88 bytes, no padding */
+  uint32_t cells;       /* cells of the pixel */
+  uint32_t water;       /* water cells */
+  uint32_t nodes;       /* wet nodes whose vorticity is not a NaN */
+  uint32_t nonfinite;   /* water cells with a NaN in any term they contribute (dx, dy, the w of their wet node, pf with the flag); once per cell */
+  uint64_t u_pos, u_neg;   /* sums of qv(dx) over the water cells with dx >= 0, of qv(-dx) over those with dx < 0 */
+  uint64_t v_pos, v_neg;   /* the same for dy */
+  uint64_t w_pos, w_neg;   /* the same for w over the wet nodes */
+  uint64_t p_sum;       /* sum of qp(pf) over the water cells; 0 without EULER_FLOW_PRESSURE */
+  float    max_speed2;  /* max dx*dx + dy*dy over the water cells */
+  float    max_abs_w;   /* max fabsf(w) over the wet nodes */
+  float    max_p;       /* max of pf > 0 ? pf : 0; 0 without the flag */
+  uint32_t reserved;    /* 0 */
+} euler_flow_px;
+/* The box, W and H as for euler_overview_box; out_bytes exactly W * H * sizeof(euler_flow_px) and no flag bit but EULER_FLOW_PRESSURE: else EULER_EINVAL.
+ * EULER_ESTATE without a loaded state and on a row-slab handle.  Reads the state only: stepping afterwards gives the bits of a run that never
+ * called it (with the flag the pending pressure is first finished in memory, as euler_get_field(EULER_F_PRESSURE) does).  The records' device buffer
+ * comes with the first call, grows with W * H (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy; no whole-grid staging copy is made. */
+int euler_flow_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                      int32_t W, int32_t H, int32_t flags, euler_flow_px* out, size_t out_bytes);
+/* Host only, no GPU: paints a field of the flow records into the dye sums of overview records of the same box, raster and state, so that every
+ * formatter that shows the dye shows the field: euler_overview_text / euler_view_text with rainbow = 1, euler_overview_rgb(EULER_IMAGE_DYE).
+ * Per pixel, in double: m_w = (w_pos - w_neg) / 2^20 / nodes (0 without nodes); m_p = p_sum / 256 / water; m_u = (u_pos - u_neg) / 2^20 / water, m_v
+ * alike, m_s = sqrt(m_u^2 + m_v^2).  VORTICITY: t = clamp(m_w / scale, -1, 1), linear colour (1, 1-t, 1-t) for t >= 0, (1+t, 1+t, 1) for t < 0 (white in
+ * the middle, red one way, blue the other).  PRESSURE, SPEED: t = clamp(m / scale, 0, 1), colour (t, 0.5, 1-t).  dye[c] = water * q((float)L_c) with the
+ * q of euler_overview_px: the formatters' mean dye is exactly q(L_c) / 2^24.  Only px[k].dye is written.  EULER_EINVAL with px unchanged: a null
+ * pointer, W < 1, H < 1, an unknown field, a scale that is not a finite positive number, a pixel whose cells or water differ between the rasters. */
+enum { EULER_PAINT_VORTICITY = 0, EULER_PAINT_PRESSURE = 1, EULER_PAINT_SPEED = 2 };
+int euler_flow_paint(const euler_flow_px* flow, euler_overview_px* px, int32_t W, int32_t H, int32_t field, double scale);
+
 /* ---- device-side scene editing (docs/editing.md) -------------------------------------------------- */
 /* Open a gate, drop a block of water, raise a wall, drain a pool while the run goes on: a box of interior cells [x0, x1] x [y0, y1] (inclusive, as for
  * euler_diagnostics) and the markers in it are edited ON THE DEVICE; nothing but a few counters crosses to the host.  A marker is "in the box" when
