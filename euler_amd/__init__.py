@@ -39,6 +39,14 @@ PAINT_VORTICITY, PAINT_PRESSURE, PAINT_SPEED = 0, 1, 2
 FLOW_DTYPE = np.dtype({"names": ["cells", "water", "nodes", "nonfinite", "u_pos", "u_neg", "v_pos", "v_neg", "w_pos", "w_neg", "p_sum", "max_speed2", "max_abs_w", "max_p", "reserved"],
                        "formats": [np.uint32] * 4 + [np.uint64] * 7 + [np.float32] * 3 + [np.uint32],
                        "offsets": [0, 4, 8, 12, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 84], "itemsize": 88})
+# euler_gauge, euler_gauge_rec (include/euler.h): one instrument of euler_gauges and its record; the doubles euler_gauge_derive forms from a record
+GAUGE_LEVEL, GAUGE_PRESSURE, GAUGE_FORCE, GAUGE_FLUX = range(4)      # EULER_GAUGE_*
+GAUGES_MAX = 1024
+GAUGE_DTYPE = np.dtype({"names": ["kind", "x0", "y0", "x1", "y1", "reserved"], "formats": [np.int32] * 6, "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
+GAUGE_REC_DTYPE = np.dtype({"names": ["cells", "fluid", "lo_x", "hi_x", "lo_y", "hi_y", "terms", "nonfinite", "a_pos", "a_neg", "b_pos", "b_neg", "max_a", "max_b"],
+                            "formats": [np.uint32] * 8 + [np.uint64] * 4 + [np.float32] * 2,
+                            "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 56, 64, 68], "itemsize": 72})
+GAUGE_VALUES = ("a", "b", "mean_a", "depth")      # euler_gauge_values, four doubles
 DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
  F_PRESSURE, F_PCG_B, F_PCG_R, F_PCG_Z, F_PCG_S, F_PCG_Q, F_CELLMASK,
@@ -103,6 +111,7 @@ EXPORTS = [
     "euler_overview_box", "euler_marker_raster", "euler_view_text", "euler_render_view",
     "euler_edit_box",
     "euler_flow_raster", "euler_flow_paint",
+    "euler_gauges", "euler_gauge_derive",
 ]
 
 
@@ -186,6 +195,8 @@ def load_library():
         "euler_edit_box": (C.c_int, [vp, i32, i32, i32, i32, i32]),
         "euler_flow_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
         "euler_flow_paint": (C.c_int, [vp, vp, i32, i32, i32, f64]),
+        "euler_gauges": (C.c_int, [vp, vp, i32, vp, C.c_size_t]),
+        "euler_gauge_derive": (C.c_int, [vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -316,6 +327,14 @@ def diag_derive(rec):
     out = np.zeros(len(DIAG_VALUES), np.float64)
     _check(load_library().euler_diag_derive(rec.ctypes.data, out.ctypes.data))
     return dict(zip(DIAG_VALUES, (float(x) for x in out)))
+
+
+def gauge_derive(rec, kind):
+    """One euler_gauge_rec record (GAUGE_REC_DTYPE) of a gauge of `kind` -> the dict of euler_gauge_derive's doubles (host only)."""
+    rec = np.ascontiguousarray(rec, GAUGE_REC_DTYPE).reshape(1)
+    out = np.zeros(len(GAUGE_VALUES), np.float64)
+    _check_host(load_library().euler_gauge_derive(rec.ctypes.data, int(kind), out.ctypes.data), "euler_gauge_derive")
+    return dict(zip(GAUGE_VALUES, (float(x) for x in out)))
 
 
 SNAPSHOT_F32 = ("u", "v", "utmp", "vtmp")
@@ -511,6 +530,22 @@ class Simulation:
         out = {n: (float(rec[n]) if n in ("max_div", "max_speed2") else int(rec[n])) for n in DIAG_DTYPE.names}
         out.update(diag_derive(rec))
         return out
+
+    def gauges(self, gauges):
+        """A list of instruments evaluated on the device in one launch and one read-back (euler_gauges, docs/gauges.md): `gauges` is a list of
+        (kind, (x0, y0, x1, y1)) - kind one of GAUGE_LEVEL, GAUGE_PRESSURE, GAUGE_FORCE, GAUGE_FLUX, the box inclusive - or an array of GAUGE_DTYPE.
+        Returns the records, an array of GAUGE_REC_DTYPE with one entry per gauge."""
+        if isinstance(gauges, np.ndarray) and gauges.dtype == GAUGE_DTYPE:
+            g = np.ascontiguousarray(gauges).reshape(-1)
+        else:
+            g = np.zeros(len(gauges), GAUGE_DTYPE)
+            for k, (kind, box) in enumerate(gauges):
+                g[k] = (int(kind),) + tuple(int(t) for t in box) + (0,)
+        rec = np.zeros(len(g), GAUGE_REC_DTYPE)
+        src = g.ctypes.data if g.size else np.zeros(1, GAUGE_DTYPE).ctypes.data
+        dst = rec.ctypes.data if rec.size else np.zeros(1, GAUGE_REC_DTYPE).ctypes.data
+        _check(self.L.euler_gauges(self.h, src, len(g), dst, rec.nbytes))
+        return rec
 
     def edit_box(self, op, box):
         """Edit box = (x0, y0, x1, y1), inclusive, and the markers in it on the device (euler_edit_box, docs/editing.md): op is one of EDIT_SOLID,

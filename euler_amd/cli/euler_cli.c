@@ -12,7 +12,7 @@
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
- *         [--paint vorticity:S|pressure:S|speed:S] <scenario>
+ *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
@@ -36,6 +36,10 @@
  * or the defaults 1, 1000 and 10.
  * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
  * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
+ * --gauge (up to 64 times) places an instrument on the box of interior cells [X0, X1] x [Y0, Y1]: level (extent of the fluid), pressure, force (on the solid
+ * cells the box's fluid touches) or flux (through the right and top faces of its cells); --gauges writes FILE (created or truncated) as CSV: a header line,
+ * then one line per gauge after every N-th frame (--gauges-every, default 1; frame 0 included), all gauges of a frame from ONE euler_gauges call
+ * (docs/gauges.md).  --gauge without --gauges or the reverse, a malformed spec, a box outside the interior and a 65th gauge are usage errors.
  */
 #include <errno.h>
 #include <signal.h>
@@ -48,11 +52,12 @@
 #include <unistd.h>
 
 #include "euler.h"
+#include "cli_gauges.h"
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -150,6 +155,21 @@ static int write_stats_line(euler_sim* sim, FILE* out, const char* path, int fra
                          (unsigned long long)d.fluid, (unsigned long long)d.markers, (unsigned)d.count_max, (unsigned long long)d.crowded, (double)d.max_div, v.mean_abs_div,
                          v.kinetic_energy, v.com_x, v.com_y, (unsigned)d.nonfinite) > 0 && fflush(out) == 0;
   if (!ok) fprintf(stderr, "--stats: cannot write %s: %s\n", path, strerror(errno));
+  return ok ? 0 : -1;
+}
+
+/* ---- --gauges: one CSV line per gauge and frame, all gauges of a frame from one euler_gauges call (docs/gauges.md) ---------------- */
+static int write_gauge_lines(euler_sim* sim, FILE* out, const char* path, int frame, const euler_gauge* g, int n) {
+  euler_gauge_rec rec[MAX_GAUGES];
+  char line[512];
+  if (euler_gauges(sim, g, n, rec, (size_t)n * sizeof *rec) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); return -1; }
+  int ok = 1;
+  for (int k = 0; ok && k < n; ++k) {
+    const int len = format_gauge_line(line, sizeof line, frame, k, g[k].kind, rec + k);
+    ok = len > 0 && (size_t)len < sizeof line && fputs(line, out) >= 0;
+  }
+  ok = ok && fflush(out) == 0;
+  if (!ok) fprintf(stderr, "--gauges: cannot write %s: %s\n", path, strerror(errno));
   return ok ? 0 : -1;
 }
 
@@ -282,6 +302,9 @@ int main(int argc, char** argv) {
   const char* ppm = NULL;
   const char* stats = NULL;
   int stats_every = 1;
+  euler_gauge gauge_list[MAX_GAUGES];
+  int n_gauges = 0, gauges_every = 1;
+  const char* gauges = NULL;
   int view = 0, vbox[4] = {0, 0, 0, 0};
   edit_t edits[MAX_EDITS];
   int n_edits = 0;
@@ -350,6 +373,10 @@ int main(int argc, char** argv) {
     /* the flow diagnostics as CSV (docs/diagnostics.md) */
     else if (!strcmp(argv[i], "--stats") && i + 1 < argc) stats = argv[++i];
     else if (!strcmp(argv[i], "--stats-every") && i + 1 < argc) { stats_every = atoi(argv[++i]); if (stats_every < 1) { usage(argv[0]); return 1; } }
+    /* the batched gauges as CSV (docs/gauges.md) */
+    else if (!strcmp(argv[i], "--gauge") && i + 1 < argc) { if (n_gauges == MAX_GAUGES || parse_gauge(argv[++i], &gauge_list[n_gauges++]) != 0) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--gauges") && i + 1 < argc) gauges = argv[++i];
+    else if (!strcmp(argv[i], "--gauges-every") && i + 1 < argc) { gauges_every = atoi(argv[++i]); if (gauges_every < 1) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
@@ -362,6 +389,11 @@ int main(int argc, char** argv) {
     if (eb[0] < 1 || eb[1] < 1 || eb[2] > cfg.X - 2 || eb[3] > cfg.Y - 2 || eb[0] > eb[2] || eb[1] > eb[3]) { usage(argv[0]); return 1; }
   }
   if (paint >= 0 && !fit && !view && !ppm) { usage(argv[0]); return 1; }
+  if ((n_gauges > 0) != (gauges != NULL)) { usage(argv[0]); return 1; }
+  for (int k = 0; k < n_gauges; ++k) {
+    const euler_gauge* gb = &gauge_list[k];
+    if (gb->x0 < 1 || gb->y0 < 1 || gb->x1 > cfg.X - 2 || gb->y1 > cfg.Y - 2 || gb->x0 > gb->x1 || gb->y0 > gb->y1) { usage(argv[0]); return 1; }
+  }
   const int ppm_size_given = ppm_w > 0;
   if (ppm && view) {      /* the size follows the box frame by frame (below) */
     if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
@@ -409,6 +441,11 @@ int main(int argc, char** argv) {
   if (stats) {
     stats_file = fopen(stats, "w");
     if (!stats_file || fputs(k_stats_header, stats_file) < 0 || fflush(stats_file) != 0) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
+  }
+  FILE* gauges_file = NULL;
+  if (gauges && !rc_exit) {
+    gauges_file = fopen(gauges, "w");
+    if (!gauges_file || fputs(k_gauges_header, gauges_file) < 0 || fflush(gauges_file) != 0) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
   }
   int32_t cap = 0;
   char* buf = NULL;
@@ -481,9 +518,11 @@ int main(int argc, char** argv) {
       if (write_ppm_frame(app.sim, ppm, f, b, app.xi, app.yi, w, h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
     } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, app.xi, app.yi, ppm_w, ppm_h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
     if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
+    if (gauges_file && f % gauges_every == 0 && write_gauge_lines(app.sim, gauges_file, gauges, f, gauge_list, n_gauges) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }
   if (stats_file && fclose(stats_file) != 0 && !rc_exit) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
+  if (gauges_file && fclose(gauges_file) != 0 && !rc_exit) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }
   euler_stats st;
   if (euler_get_stats(app.sim, &st) == EULER_OK)

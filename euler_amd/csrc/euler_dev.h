@@ -163,8 +163,8 @@ struct euler_sim {
   float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when blocked_dirty): whole-grid handles only
   int solidT_dirty;
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
-  eu_devbuf ov_buf, diag_buf, vr_buf, flow_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
-                          // raster, euler_flow_raster's records; each allocated by its pass's first call and grown on demand
+  eu_devbuf ov_buf, diag_buf, vr_buf, flow_buf, gauge_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
+                          // raster, euler_flow_raster's records, euler_gauges' records and chunk table; each allocated by its pass's first call and grown on demand
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)

@@ -2,7 +2,7 @@
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
  * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
  * whole-domain overview's records (text through the same frame formatter, RGB), the magnified frame of the viewport, the values derived from a diagnostics record,
- * and the painter that shows a field of the flow raster through those formatters.
+ * the painter that shows a field of the flow raster through those formatters, and the host side of the batched gauges (list check, chunk table, derived values).
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -448,5 +448,46 @@ int euler_flow_paint(const euler_flow_px* flow, euler_overview_px* px, int32_t W
     }
     for (int c = 0; c < 3; ++c) px[k].dye[c] = (uint64_t)f->water * paint_q24((float)lin[c]);
   }
+  return EULER_OK;
+}
+
+/* ---- batched gauges: the list checked, cut into chunks, and the values read off a record (include/euler.h, docs/gauges.md) ---- */
+
+int eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what) {
+  for (int32_t k = 0; k < n; ++k) {
+    const char* w = NULL;
+    if (g[k].kind < EULER_GAUGE_LEVEL || g[k].kind > EULER_GAUGE_FLUX) w = "an unknown kind";
+    else if (g[k].reserved != 0) w = "reserved is not 0";
+    else if (g[k].x0 < 1 || g[k].y0 < 1 || g[k].x1 > X - 2 || g[k].y1 > Y - 2 || g[k].x0 > g[k].x1 || g[k].y0 > g[k].y1) w = "its box is not inside the interior";
+    if (w) { if (what) *what = w; return k; }
+  }
+  return -1;
+}
+
+size_t eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out) {
+  size_t m = 0;
+  for (int32_t k = 0; k < n; ++k) {
+    const int32_t tx0 = g[k].x0 >> 6, tx1 = g[k].x1 >> 6, ty0 = g[k].y0 >> 6, ty1 = g[k].y1 >> 6;
+    if (!out) { m += (size_t)(tx1 - tx0 + 1) * (size_t)(ty1 - ty0 + 1); continue; }
+    for (int32_t ty = ty0; ty <= ty1; ++ty)
+      for (int32_t tx = tx0; tx <= tx1; ++tx) {      /* the tile clipped to the box */
+        eu_gauge_chunk* c = out + m++;
+        c->gauge = k; c->kind = g[k].kind;
+        c->x0 = tx == tx0 ? g[k].x0 : tx << 6; c->x1 = tx == tx1 ? g[k].x1 : (tx << 6) + 63;
+        c->y0 = ty == ty0 ? g[k].y0 : ty << 6; c->y1 = ty == ty1 ? g[k].y1 : (ty << 6) + 63;
+      }
+  }
+  return m;
+}
+
+int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_values* out) {
+  if (!rec || !out || kind < EULER_GAUGE_LEVEL || kind > EULER_GAUGE_FLUX) return EULER_EINVAL;
+  memset(out, 0, sizeof *out);
+  if (!rec->fluid) return EULER_OK;
+  const double scale = kind == EULER_GAUGE_FLUX ? 1048576.0 : 256.0;
+  out->a = ((double)rec->a_pos - (double)rec->a_neg) / scale;
+  out->b = ((double)rec->b_pos - (double)rec->b_neg) / scale;
+  out->mean_a = rec->terms ? out->a / (double)rec->terms : 0.0;
+  out->depth = (double)rec->hi_y - (double)rec->lo_y + 1.0;
   return EULER_OK;
 }

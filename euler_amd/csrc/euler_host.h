@@ -13,6 +13,10 @@ uint64_t euler_rng_jump(uint64_t state, uint64_t steps);   /* xorshift64* state 
 int      euler_seed_markers_rows(const uint8_t* fluid, int32_t X, int32_t Y, int32_t row_lo, int32_t row_hi, uint64_t* rng_state,
                                  float* markers_xy, uint32_t* keys, uint64_t cap, uint64_t* n_total, uint64_t* n_kept);
 #define EULER_RNG_SEED 0x9bd185c449534b91ull /* main.c:204 */
+/* euler_gauges (k_gauges.hip, docs/gauges.md): the list checked and cut along the 64 x 64 tile grid.  A chunk lies in one tile, hence in one band of the skewed arrays */
+typedef struct eu_gauge_chunk { int32_t gauge, kind, x0, y0, x1, y1; } eu_gauge_chunk;
+int      eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what);   /* the index of the first gauge refused (what: why), -1: none */
+size_t   eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out);   /* out == NULL: the count only; the list must have passed eu_gauge_check */
 #ifdef __cplusplus
 }
 #endif

@@ -471,6 +471,51 @@ int euler_flow_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_
 enum { EULER_PAINT_VORTICITY = 0, EULER_PAINT_PRESSURE = 1, EULER_PAINT_SPEED = 2 };
 int euler_flow_paint(const euler_flow_px* flow, euler_overview_px* px, int32_t W, int32_t H, int32_t field, double scale);
 
+/* ---- batched gauges (docs/gauges.md) -------------------------------------------------------------- */
+/* How high does the water stand at a column, where is the front, what load does a gate carry, how much passes under it, what does a pressure sensor
+ * read?  A LIST of small instruments - each a kind and an inclusive box of interior cells - evaluated on the device in one launch and one read-back.
+ * Per cell i = y * X + x, float32 without contraction; a FLUID cell is the diagnostics': count > 0 && !solid.  pf = (float)p, p the double
+ * euler_get_field(EULER_F_PRESSURE) returns for the cell; qp, qv are euler_flow_px's.  A signed term a adds qv(a) to the _pos sum when a >= 0 (-0.f too)
+ * and qv(-a) to the _neg sum otherwise.  A NaN term adds nothing to its sums and maxima and counts its cell once in nonfinite; an infinity saturates its
+ * sum and shows in its maximum.  Every kind fills cells, fluid and the extent; beyond that
+ *   LEVEL     nothing: hi_y over a strip of columns is a wave gauge, hi_x / lo_x a front tracker
+ *   PRESSURE  over the fluid cells: a_pos = sum qp(pf), max_a = max(pf > 0 ? pf : 0), terms = fluid; a one-cell box is a pressure sensor
+ *   FORCE     what the fluid cells of the box put on the solid cells they touch (h = 1, density 1: a wetted face carries pf): solid at x+1: qp(pf) into
+ *             a_pos, at x-1: a_neg, at y+1: b_pos, at y-1: b_neg; terms counts wetted faces; max_a, max_b the largest face pressure in x and in y.  The
+ *             solid neighbour may lie outside the box and on the border ring: the load on a gate is the box of the gate grown by one cell
+ *   FLUX      per cell of the box its right face u[i] and its top face v[i], where the face is live as the velocity advection tests it:
+ *             (count[i] || count[i+1]) && !(solid[i] || solid[i+1]) for u, with i+X for v; u into a_pos / a_neg, v into b_pos / b_neg; terms counts live
+ *             faces of both kinds; max_a = max |u|, max_b = max |v|.  A box one column wide gives the discharge through x + 1/2
+ * No sum can wrap: a term is at most 2^32 and a box has at most 2^28 cells.  Every field is an integer sum, an integer extreme or a maximum of
+ * non-negative floats taken on their bit patterns: a record does not depend on launch geometry, atomics or the tile map (tests compare bits). */
+typedef struct euler_gauge {      /* 24 bytes */
+  int32_t kind;                   /* EULER_GAUGE_* */
+  int32_t x0, y0, x1, y1;         /* inclusive, inside [1, X-2] x [1, Y-2] */
+  int32_t reserved;               /* must be 0 */
+} euler_gauge;
+enum { EULER_GAUGE_LEVEL = 0, EULER_GAUGE_PRESSURE = 1, EULER_GAUGE_FORCE = 2, EULER_GAUGE_FLUX = 3 };
+#define EULER_GAUGES_MAX 1024
+typedef struct euler_gauge_rec {  /* 72 bytes, no padding */
+  uint32_t cells, fluid;                /* cells of the box; fluid cells */
+  uint32_t lo_x, hi_x, lo_y, hi_y;      /* extent of the fluid cells of the box; lo = 0xffffffff, hi = 0 when fluid == 0 */
+  uint32_t terms, nonfinite;            /* terms summed (per kind, above); cells with a NaN term */
+  uint64_t a_pos, a_neg, b_pos, b_neg;
+  float    max_a, max_b;
+} euler_gauge_rec;
+typedef struct euler_gauge_values {   /* what a user reads off a record; all 0 when fluid == 0 */
+  double a, b;        /* (a_pos - a_neg) / scale, (b_pos - b_neg) / scale; scale 2^8 for PRESSURE and FORCE, 2^20 for FLUX */
+  double mean_a;      /* a / terms (0 without terms): the mean pressure of a PRESSURE gauge */
+  double depth;       /* hi_y - lo_y + 1 */
+} euler_gauge_values;
+/* n gauges, 1 <= n <= EULER_GAUGES_MAX, into n records; gauges may overlap and repeat.  Refusals in this order: a null pointer (EULER_EINVAL), a row-slab
+ * handle, nothing loaded (EULER_ESTATE); n out of range or out_bytes != n * sizeof(euler_gauge_rec) (EULER_EINVAL); then per gauge, naming its index: an
+ * unknown kind, reserved != 0, a box outside the interior or with x0 > x1 or y0 > y1 (EULER_EINVAL).  A refused call allocates nothing and leaves out
+ * untouched.  Reads the state only: stepping afterwards gives the bits of a run that never called it (with a PRESSURE or FORCE gauge in the list the
+ * pending pressure is first finished in memory, as euler_get_field(EULER_F_PRESSURE) does).  The device buffer of the pass comes with the first call, grows
+ * with the list (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy. */
+int euler_gauges(euler_sim* sim, const euler_gauge* g, int32_t n, euler_gauge_rec* out, size_t out_bytes);
+int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_values* out);   /* host only, no GPU; EULER_EINVAL: a null pointer, an unknown kind */
+
 /* ---- device-side scene editing (docs/editing.md) -------------------------------------------------- */
 /* Open a gate, drop a block of water, raise a wall, drain a pool while the run goes on: a box of interior cells [x0, x1] x [y0, y1] (inclusive, as for
  * euler_diagnostics) and the markers in it are edited ON THE DEVICE; nothing but a few counters crosses to the host.  A marker is "in the box" when
