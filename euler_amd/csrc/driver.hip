@@ -246,7 +246,7 @@ extern "C" int euler_set_precond(euler_sim* S, int32_t precond, int32_t tile_rec
   // (a row-slab handle runs whatever preconditioner it is given WITHOUT coupling between the slabs - eu_install_comm forced S->couple = 0 and
   // refuses EULER_SLAB_EXACT for it - so EULER_PRECOND_IC0 here means slab-local IC(0): valid, and not the single-GPU iterates)
   S->cfg.precond = precond;
-  S->lean_ok = 0;      // the next assembly writes the solver arrays whole (k_build_system)
+  eu_vd_solver_arrays_foreign(&S->vd);      // the next assembly writes the solver arrays whole (k_build_system)
   return EULER_OK;
 }
 
@@ -406,7 +406,7 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
   DALLOC(S->solid, Cw); DALLOC(S->source, Cw); DALLOC(S->sink, Cw); DALLOC(S->count, Cw); DALLOC(S->prev_count, Cw);
   DALLOC(S->count32, Cw);
   if (!S->slab_on) { DALLOC(S->blockedT, Cw); DALLOC(S->uT, Cw); DALLOC(S->vT, Cw); DALLOC(S->countT, Cw); DALLOC(S->solidT, Cw); }      // (the marker stage's column-major copies)
-  eu_state_replaced(S);
+  eu_vd_replaced(&S->vd);
   DALLOC(S->sys_m, Cw); DALLOC(S->sys_div, Cw);
   if (S->cfg.rainbow) for (float*& d : S->dye) DALLOC(d, Cw);      // (the window like every row-major field; the whole grid without slabs)
   // MAX_MARKER_COUNT = 4 X Y (main.c:92) is the GLOBAL cap; a slab holds the markers inside its rows: room for 6 per owned cell
@@ -582,7 +582,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   HIPCHK(hipMemcpyAsync(S->solid + wo, solid + wo, Cw, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(S->source + wo, source + wo, Cw, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(S->sink + wo, sink + wo, Cw, hipMemcpyHostToDevice, st));
-  eu_state_replaced(S);
+  eu_vd_replaced(&S->vd);
   for (float* f : {S->u, S->v, S->utmp, S->vtmp}) HIPCHK(hipMemsetAsync(f + wo, 0, Cw * sizeof(float), st));
   for (double* d : {S->b, S->p, S->r, S->z, S->s, S->s2, S->q, S->precon}) HIPCHK(hipMemsetAsync(d + S->skew_off, 0, S->Sw * sizeof(double), st));
   for (float* d : S->dye) if (d) HIPCHK(hipMemsetAsync(d + wo, 0, Cw * sizeof(float), st));
@@ -765,11 +765,7 @@ extern "C" int euler_timestep(euler_sim* S, float frame_time_left, float* dt) {
 }
 
 static int run_stage(euler_sim* S, int stage, float dt) {
-  if (stage != EULER_STAGE_REFRESH_COUNTS) S->prebin_valid = 0;      // (what k_advect_bin_a2 binned belongs to the refresh that follows it DIRECTLY)
-  if (stage == EULER_STAGE_EXTRAPOLATE && S->maxsq_state == 2) S->maxsq_state = 1;      // (writes u, v; inside a substep the timestep has consumed the maxima long before)
-  if (stage == EULER_STAGE_REFRESH_COUNTS) { S->uv_clean = S->uv_clean == 1 ? 2 : 0; S->uv_zb = 0; }      // (prev <- cur: once is what k_zero_bounds4<true> expects)
-  if (stage == EULER_STAGE_REFRESH_COUNTS) { S->utmp_clean = S->utmp_clean == 1 ? 2 : 0; S->countT_clean = S->countT_clean == 1 ? 2 : 0; }      // (the same for what the tile map's readers left)
-  if (stage == EULER_STAGE_SOURCES) S->uv_zb = 0;                                                        // (the count grid changes)
+  eu_vd_stage_begin(&S->vd, stage);      // (each launcher reports what it ran: eu_valid.h)
   switch (stage) {
     case EULER_STAGE_ADVECT_MARKERS: return eu_launch_advect_markers(S, dt);
     case EULER_STAGE_REFRESH_COUNTS: return eu_launch_refresh_counts(S);
@@ -955,7 +951,7 @@ int eu_set_source_count(euler_sim* S, size_t nsrc) {
 extern "C" int euler_set_field(euler_sim* S, int32_t f, const void* src, size_t src_bytes) {
   if (!S || !src) return EULER_EINVAL;
   if (field_is_skewed(f)) { int rcp = eu_pressure_current(S); if (rcp) return rcp; }      // (the pressure is finished from the solver's arrays before a caller overwrites any of them)
-  eu_state_edited(S);
+  eu_vd_edited(&S->vd);
   if (S->slab_on && (f == EULER_F_MARKERS || f == EULER_F_MARKER_KEYS || f == EULER_F_COUNT || f == EULER_F_PREV_COUNT ||
                      f == EULER_F_SOLID || f == EULER_F_SOURCE)) {
     // (solid cells are read through ghost rows, the source cells of ALL ranks decide whether the source stage runs at all: facts
@@ -968,7 +964,7 @@ extern "C" int euler_set_field(euler_sim* S, int32_t f, const void* src, size_t 
   if (rc) return rc;
   if (src_bytes != b) { eu_set_error("euler_set_field(%d): %zu bytes given, %zu expected", f, src_bytes, b); return EULER_EINVAL; }
   if (field_is_skewed(f)) {
-    S->lean_ok = 0;      // a caller's values in the solver arrays: the next assembly writes them whole
+    eu_vd_solver_arrays_foreign(&S->vd);      // a caller's values in the solver arrays: the next assembly writes them whole
     if (f == EULER_F_PCG_S) { S->s_stale = 0; S->s_launched = 0; S->s_none = 0; }      // (every element of S->s is the caller's now)
     rc = ensure_rowmajor_tmp(S);
     if (rc) return rc;
@@ -983,7 +979,7 @@ extern "C" int euler_set_field(euler_sim* S, int32_t f, const void* src, size_t 
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(S->stream));
   }
-  if (f == EULER_F_SOLID || f == EULER_F_SINK) { S->blocked_dirty = 1; S->solidT_dirty = 1; }      // (the marker stage's column-major copies follow at their next use)
+  if (f == EULER_F_SOLID || f == EULER_F_SINK) eu_vd_masks_changed(&S->vd);      // (the marker stage's column-major copies follow at their next use)
   if (f == EULER_F_SOURCE) {
     const uint8_t* s = (const uint8_t*)src;
     size_t nsrc = 0;
@@ -1003,7 +999,7 @@ __global__ void k_set_marker_state(MarkerState* ms, unsigned long long n, unsign
 extern "C" int euler_set_markers(euler_sim* S, const float* xy, uint64_t n) {
   if (!S || (!xy && n) || n > S->max_markers) return EULER_EINVAL;
   if (S->slab_on) { eu_set_error("euler_set_markers: not on a row-slab handle"); return EULER_ESTATE; }
-  eu_state_edited(S);
+  eu_vd_edited(&S->vd);
   if (n) HIPCHK(hipMemcpyAsync(S->markers[S->cur], xy, n * 8, hipMemcpyHostToDevice, S->stream));
   hipLaunchKernelGGL(k_set_marker_state, dim3(1), dim3(1), 0, S->stream, S->ms, (unsigned long long)n,
                      (unsigned long long)S->max_markers, 1, 0ull, 0, 0);

@@ -8,6 +8,7 @@
 
 #include "euler.h"
 #include "euler_host.h"
+#include "eu_valid.h"
 
 // ------------------------------------------------------------------------------------------
 // reference constants (main.c:58-60)
@@ -141,12 +142,7 @@ struct euler_sim {
   float *u, *v, *utmp, *vtmp;
   uint8_t *solid, *source, *sink, *count, *prev_count;
   unsigned int* count32;   // the binning counters of the window, COLUMN-major: [x][y - win_lo] (k_markers.hip), never shifted
-  int p_pending;           // k_velocity_update_para finished and clamped the pressure in LDS only: 1 - memory still lacks the last fmadds and the clamp, 2 - the clamp (eu_pressure_current)
-  int maxsq_state;         // ms->max_u2_bits / max_v2_bits: 0 - zero, 2 - the maxima of u, v as they stand (k_velocity_update_para), 1 - maxima of a state that has been edited since
-  int uv_clean;            // 1: the last velocity update left every sample without the fluid property / with the solid property zero; 2: ... and exactly one refresh_marker_counts has run since (k_zero_bounds4<true>); 0: unknown
-  int uv_zb;               // zero_bounds has run with the count grid as it stands (k_velocity_update_para need not store the zeros of the air and the walls again)
-  int count32_dirty;       // the counters hold something (between a binning launch and the k_narrow_counts<true> that clears them; whole-grid handles)
-  int prebin_valid;        // the advection stage in front binned its own output (k_advect_bin_a2): the next refresh keeps the counters and the delete ballot
+  eu_valid vd;             // what each pass has left for the next and whether it still holds (eu_valid.h): touched through the eu_vd_* events and queries only
   unsigned long long* delmask;   // [ceil(max_markers/64)] that pass's delete ballot (whole-grid handles)
   // Round 6, the TILE MAP (whole-grid handles): per 64 x 64 cells, "some cell of the tile holds markers" for the count grid as it stands (tmap) and for the previous one
   // (tmap + tmap_n) - a superset: a set flag over an empty tile is harmless.  k_narrow_counts<true> writes both at every refresh, k_source_place sets what it fills; the
@@ -155,13 +151,8 @@ struct euler_sim {
   // array, below): most of a dam break's grid.  DESIGN.md section 4 "tiles without water".
   uint8_t* tmap;
   int tmap_nx, tmap_n;     // tiles per row; tiles in all (the previous grid's flags start at tmap + tmap_n; at tmap + 2 tmap_n: a marker has entered the tile since the last refresh)
-  int tmap_valid;          // both maps describe count / prev_count (0: somebody else wrote the grids since the last refresh)
-  int utmp_clean;          // 1: utmp / vtmp are zero wherever the typed fluid property of the count grid does not hold (k_advect_velocity wrote them); 2: ... of prev_count (one refresh since); 0: unknown
-  int countT_clean;        // the same for countT (k_transpose_for_markers)
-  uint8_t* blockedT;       // sink | solid per cell, COLUMN-major like count32 (whole-grid handles; k_bin_markers); rebuilt when blocked_dirty
-  int blocked_dirty;
-  float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when blocked_dirty): whole-grid handles only
-  int solidT_dirty;
+  uint8_t* blockedT;       // sink | solid per cell, COLUMN-major like count32 (whole-grid handles; k_bin_markers); rebuilt when eu_vd_blocked_due
+  float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when eu_vd_solidT_due): whole-grid handles only
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
   eu_devbuf ov_buf, diag_buf, vr_buf, flow_buf, gauge_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
                           // raster, euler_flow_raster's records, euler_gauges' records and chunk table; each allocated by its pass's first call and grown on demand
@@ -249,7 +240,6 @@ struct euler_sim {
   uint8_t* chunk_prev;    // the previous solve's flags (k_build_system<true>: where stale masks / p / r may sit)
   uint8_t* chunk_part;    // this solve: some cell of the chunk is not CM_INTERIOR (the listed entry of an interior chunk carries EU_CHUNK_INTERIOR)
   size_t hbm_bytes;       // device memory this handle allocated: at creation, plus the search directions' ring when the first multi-kernel solve needs it (euler_hbm_bytes)
-  int lean_ok;            // the solver arrays have only been written by solves since chunk_prev was current (else k_build_system writes them whole)
   double* zhalo;          // tile-local mode on one GPU (k_pcg.h tile_z_recompute): [band][T / 16][2][64] - records 0 and 15 of every tile's z; allocated by the first solve that needs them
   double* zrows;          // [band][2][X]: lane 0's / lane 63's z by column (with zhalo)
   int z_halo_last;        // the solve's last k_precond_tile left z as its halo only: the next k_search_apply forms z again (ZR)
@@ -370,23 +360,8 @@ int  eu_slab_after_restore(euler_sim* S);   // collective: the job-wide facts a 
 int  eu_slab_error_sync(euler_sim* S);      // collective: the ranks' sticky error words -> their maximum on every rank
 int  eu_slab_same_everywhere(euler_sim* S, const double* vals, int n, int* same);   // collective: do these host-side values agree on every rank?
 int  eu_slab_status_sync(euler_sim* S, int local_rc, int* worst);   // collective: a host-side status code -> non-zero on every rank if any rank failed
-// the grids of the handle were (re)written whole - allocation, a scenario load, a snapshot: nothing one stage prepared for the next describes them any more
-static inline void eu_state_replaced(euler_sim* S) {
-  S->blocked_dirty = 1; S->solidT_dirty = 1;      // (the column-major copies of the solid / sink grids)
-  S->prebin_valid = 0;
-  if (S->maxsq_state == 2) S->maxsq_state = 1;
-  S->p_pending = 0;
-  S->uv_clean = 0; S->uv_zb = 0;
-  S->tmap_valid = 0; S->utmp_clean = 0; S->countT_clean = 0;
-}
-// somebody other than the substep's own sequence is about to write the state: what one stage prepared for the next no longer describes it
-static inline void eu_state_edited(euler_sim* S) {
-  S->prebin_valid = 0;                               // (k_advect_bin_a2's counts and delete ballot)
-  if (S->maxsq_state == 2) S->maxsq_state = 1;       // (k_velocity_update_para's maxima of u, v: stale, cleared before the next accumulation)
-  S->uv_clean = 0; S->uv_zb = 0; S->tmap_valid = 0; S->utmp_clean = 0; S->countT_clean = 0;                     // (what the lean zero_bounds / the velocity update's skipped zero stores rely on)
-}
 // the tile map describes both count grids and this handle's passes may use it (EULER_OPT_NO_TILE_MAP: rounds 1-5's forms)
-static inline bool eu_tile_map_on(const euler_sim* S) { return S->tmap && S->tmap_valid && !S->slab_on && S->opt[EULER_OPT_NO_TILE_MAP] == 0; }
+static inline bool eu_tile_map_on(const euler_sim* S) { return eu_vd_tile_map(&S->vd, !S->tmap || S->slab_on || S->opt[EULER_OPT_NO_TILE_MAP] != 0) != 0; }
 // launch groups implemented in the kernel files
 int eu_launch_timestep(euler_sim* S, float frame_time_left);
 int eu_launch_advect_markers(euler_sim* S, float dt);
@@ -483,6 +458,9 @@ __device__ __forceinline__ float eu_frac(float f, bool start_ok, bool end_ok) { 
 __device__ __forceinline__ float eu_clampf(float lo, float x, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // interpolate(), main.c:337-364.  TYPE 0 = cell centres (P), 1 = U samples, 2 = V samples.
+// CONSUMERS of the transposed inputs (TR): uT, vT and countT are left UNWRITTEN over tiles without water (k_transpose_for_markers, lean - eu_valid.h countT_clean), so a
+// sample of q is valid only where its bit of the props byte is set; the bytes over an idle tile are the zeros an earlier full pass left, its samples are whatever was there.
+// Read a sample without its bit and the lean and the plain form stop giving the same bits.
 // TR: q and g.count are stored COLUMN-major, [x][y] (the marker stage's copies: k_markers.hip) - the same values, the strides swapped
 // PROPS: g.count does not hold counts but, per cell, the typed fluid properties of the four corners of an interpolation whose BASE cell it is (bits 0-3 U-typed, 4-7 V-typed,
 // corner order v00 v01 v10 v11; k_transpose_for_markers): one byte gather instead of six

@@ -188,7 +188,7 @@ static int ed_run(euler_sim* S, int op, const EdBox& b) {
     eu_set_error("euler_edit_box: %llu markers and %llu cells to seed: more than the %llu the array holds", n, E, (unsigned long long)S->max_markers - 1ull);
     return EULER_EINVAL;
   }
-  eu_state_edited(S);
+  eu_vd_edited(&S->vd);
   if (del && n) {
     const size_t nwords = (size_t)((n + 63) / 64);
     HIPCHK(hipMemsetAsync(S->evmask, 0, nwords * sizeof(unsigned long long), S->stream));
@@ -207,7 +207,7 @@ static int ed_run(euler_sim* S, int op, const EdBox& b) {
   if ((del && n) || (seed && E)) hipLaunchKernelGGL(k_edit_commit, dim3(1), dim3(1), 0, S->stream, S->ms, S->rng_jump, del && n ? 1 : 0, seed && E ? 1 : 0);
   HIPCHK(hipGetLastError());
   if (op != EULER_EDIT_DRAIN && op != EULER_EDIT_FILL) {      // a mask changed: the marker stage's column-major copies and the source stage's cell count follow
-    S->blocked_dirty = 1; S->solidT_dirty = 1;
+    eu_vd_masks_changed(&S->vd);
     const size_t src_new = S->n_source_cells - (size_t)src_old + (op == EULER_EDIT_SOURCE ? (size_t)Bw * b.Bh : 0);
     if (src_new != S->n_source_cells && (rc = eu_set_source_count(S, src_new))) return rc;
   }

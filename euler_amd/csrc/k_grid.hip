@@ -97,11 +97,10 @@ int eu_launch_timestep(euler_sim* S, float frame_time_left) {
     LAUNCH(S, KC_TIMESTEP, k_maxsq<false>, dim3(nb), dim3(256), S->u, S->v, S->X, S->Y, S->ms, S->row_lo, S->row_hi, frame_time_left);
     return eu_slab_timestep(S, frame_time_left);
   }
-  if (S->maxsq_state == 2) {      // k_velocity_update_para left the maxima of exactly these u, v (nothing has written them since: driver.hip drops the state otherwise)
-    S->maxsq_state = 0;
-    return eu_launch_dt(S, frame_time_left);
-  }
-  if (S->maxsq_state == 1) { HIPCHK(hipMemsetAsync(&S->ms->max_u2_bits, 0, 2 * sizeof(unsigned int), S->stream)); S->maxsq_state = 0; }      // (maxima of a state edited since)
+  const int mode = eu_vd_timestep_mode(&S->vd);
+  eu_vd_timestep_ran(&S->vd);
+  if (mode == EU_DT_ONLY) return eu_launch_dt(S, frame_time_left);      // k_velocity_update_para left the maxima of exactly these u, v (nothing has written them since)
+  if (mode == EU_DT_CLEAR_MAXSQ) HIPCHK(hipMemsetAsync(&S->ms->max_u2_bits, 0, 2 * sizeof(unsigned int), S->stream));      // (maxima of a state edited since)
   LAUNCH(S, KC_TIMESTEP, k_maxsq<true>, dim3(nb), dim3(256), S->u, S->v, S->X, S->Y, S->ms, S->row_lo, S->row_hi, frame_time_left);
   return EULER_OK;
 }
@@ -169,7 +168,7 @@ __device__ __forceinline__ uint2 eu_props4(const uint8_t* __restrict__ g, size_t
 // property, IS zero (the velocity update sets the air's and the walls' faces to 0, main.c:784-790, 797-803; in the first substep u = v = 0).  Of the samples zero_bounds has to
 // zero now - no fluid property in the NEW count grid, or solid - only two kinds can hold anything else: those that had the fluid property in the previous grid and no wall
 // (a velocity that the water has left), and walls' samples that extrapolate has just written (fluid now, not before).  16384^2 dam break: 1.5 GB of zeros per substep not written.
-// (Valid while exactly one refresh_marker_counts lies between the last velocity update and this call and nobody edited the state: euler_sim.uv_clean.)
+// (Valid while exactly one refresh_marker_counts lies between the last velocity update and this call and nobody edited the state: eu_vd_lean_zero_bounds.)
 template <bool LEAN>
 __global__ __launch_bounds__(256) void k_zero_bounds4(float* u, float* v, const uint8_t* __restrict__ cur,
                                                       const uint8_t* __restrict__ solid, int X, int Y, int y0, int y1, const uint8_t* __restrict__ prev,
@@ -229,18 +228,18 @@ int eu_launch_extrapolate(euler_sim* S) {
     if (tm) while (rep < 16 && ((size_t)S->X * S->Y >> 24) >= (size_t)(2 * rep)) rep *= 2;      // (8192^2: 4, 16384^2: 16 - at least 4 K workgroups)
     grid4.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
     LAUNCH(S, KC_EXTRAPOLATE, k_extrapolate4, grid4, dim3(256), S->u, S->v, S->prev_count, S->count, S->X, S->Y, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-    if (!S->slab_on && S->uv_clean == 2 && S->opt[EULER_OPT_VELOCITY_TWO_PASS] == 0)
+    if (eu_vd_lean_zero_bounds(&S->vd, S->slab_on, S->opt[EULER_OPT_VELOCITY_TWO_PASS] != 0))
       LAUNCH(S, KC_EXTRAPOLATE, k_zero_bounds4<true>, grid4, dim3(256), S->u, S->v, S->count, S->solid, S->X, S->Y, S->row_lo, S->row_hi, S->prev_count, tm, S->tmap_nx, S->tmap_n, rep);
     else
       LAUNCH(S, KC_EXTRAPOLATE, k_zero_bounds4<false>, grid4, dim3(256), S->u, S->v, S->count, S->solid, S->X, S->Y, S->row_lo, S->row_hi, (const uint8_t*)nullptr,
              (const uint8_t*)nullptr, 0, 0, rep);
-    S->uv_zb = 1;      // (zero_bounds has run with the count grid as it stands)
+    eu_vd_extrapolated(&S->vd);
     return EULER_OK;
   }
   dim3 grid((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4);   // this rank's rows (all of them without slabs)
   LAUNCH(S, KC_EXTRAPOLATE, k_extrapolate, grid, dim3(256), S->u, S->v, S->prev_count, S->count, S->X, S->Y, S->row_lo, S->row_hi);
   LAUNCH(S, KC_EXTRAPOLATE, k_zero_bounds, grid, dim3(256), S->u, S->v, S->count, S->solid, S->X, S->Y, S->row_lo, S->row_hi);
-  S->uv_zb = 1;
+  eu_vd_extrapolated(&S->vd);
   return EULER_OK;
 }
 
@@ -408,7 +407,7 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
   dim3 grid((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4);
   // (the tile map: utmp / vtmp must be what this kernel left one refresh ago, and nothing but the refresh may have touched the count grids since)
-  const bool lean = eu_tile_map_on(S) && S->utmp_clean == 2 && !(S->cfg.viscosity > 0.f);
+  const bool lean = eu_vd_lean_advect(&S->vd, eu_tile_map_on(S), S->cfg.viscosity > 0.f);
   int rep = 1;
   if (lean) while (rep < 16 && ((size_t)S->X * S->Y >> 22) >= (size_t)(2 * rep)) rep *= 2;      // (2048^2: 1, 4096^2: 4, 8192^2 and beyond: 16 - at least 16 K workgroups)
   grid.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
@@ -427,7 +426,7 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
   else
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-  S->utmp_clean = (S->cfg.viscosity > 0.f) ? 0 : 1;      // (the diffusion extension writes utmp / vtmp behind this)
+  eu_vd_advected_velocity(&S->vd, S->cfg.viscosity > 0.f);      // (the diffusion extension writes utmp / vtmp behind this, with u, v as its scratch)
   // (a row-slab handle exchanges the ghost rows of utmp / vtmp between the two: eu_slab_substep calls eu_launch_diffuse itself)
   return S->slab_on ? EULER_OK : eu_launch_diffuse(S, dt);
 }
@@ -782,7 +781,7 @@ __global__ __launch_bounds__(256) void k_velocity_update_para(const float* __res
                                                               int band_lo, int do_max, int skip_zero,      // this rank's bands start at band_lo; do_max 0: a row slab's maxima are k_maxsq's (all-reduced)
                                                               const uint8_t* __restrict__ tmap, int tnx) {
   // skip_zero: the faces this pass sets to 0 - the air's, the walls' (main.c:784-790, 797-803) - are not stored: zero_bounds zeroed exactly those samples of u, v earlier in
-  // this substep, with the same count grid (euler_sim.uv_zb), and nothing has written them since
+  // this substep, with the same count grid (eu_vd_update_skips_zeros), and nothing has written them since
   __shared__ double sp[65][VU_W + 1];
   __shared__ float s_mu[4], s_mv[4];
   const int units = g.T / VU_W;
@@ -944,7 +943,7 @@ int eu_launch_build_system(euler_sim* S, float dt) {
   HIPCHK(hipMemsetAsync(S->chunk_flag, 0, S->chunk_cap + 64, S->stream));
   HIPCHK(hipMemsetAsync(S->chunk_part, 0, S->chunk_cap + 64, S->stream));
   // the lean assembly needs every solve since the arrays were last written whole to have been a tile-mode solve of this handle
-  const bool lean = eu_is_tile(S) && S->cfg.sweep_mode != EULER_SWEEP_SIMPLE && S->lean_ok;
+  const bool lean = eu_vd_lean_assembly(&S->vd, eu_is_tile(S) && S->cfg.sweep_mode != EULER_SWEEP_SIMPLE);
   const bool gather = S->opt[EULER_OPT_BUILD_GATHER] != 0;      // (experiments: the one-kernel diagonal gather of rounds 1-2)
   const bool two_pass = S->opt[EULER_OPT_BUILD_TWO_PASS] != 0;  // (rounds 3-5: a row-major pass and a skewed gather)
   if (!gather && !two_pass) {
@@ -971,7 +970,7 @@ int eu_launch_build_system(euler_sim* S, float dt) {
   else
     LAUNCH(S, KC_BUILD_SYSTEM, k_build_system<false>, dim3(eu_blocks(S->e_cnt, 256)), dim3(256), S->utmp, S->vtmp, S->count,
            S->solid, S->b, S->r, S->p, S->q, S->z, S->cellmask, S->sc, S->geom, dt, S->e_lo, S->e_cnt, S->chunk_flag, S->chunk_part, S->chunk_prev);
-  S->lean_ok = 1;      // this solve's flags describe everything that is non-zero from here on
+  eu_vd_assembled(&S->vd);      // p is written afresh; this solve's flags describe everything that is non-zero from here on
   LAUNCH(S, KC_BUILD_SYSTEM, k_pack_chunk_bits, dim3(eu_blocks(S->chunk_words, 256)), dim3(256), S->chunk_flag, S->chunk_bits, S->chunk_words, S->chunk_cap);
   // the ascending list of this solve's active chunks (k_search_apply, k_precond_tile)
   int rc = eu_ordered_select(S, S->chunk_bits, S->chunk_words, S->chunk_list, &S->sc->n_chunks);
@@ -984,9 +983,9 @@ int eu_launch_build_system(euler_sim* S, float dt) {
 
 // The finished, clamped pressure in memory: k_velocity_update_para forms it in LDS only.  Whoever reads S->p between two solves comes through here first.
 int eu_pressure_current(euler_sim* S) {
-  if (!S->p_pending) return EULER_OK;
-  const int mode = S->p_pending;
-  S->p_pending = 0;
+  const int mode = eu_vd_pressure_owes(&S->vd);
+  if (!mode) return EULER_OK;
+  eu_vd_pressure_made_current(&S->vd);
   if (mode == 1) { int rc = eu_launch_finish_p(S); if (rc) return rc; }
   LAUNCH(S, KC_VELOCITY_UPDATE, k_clamp_p, dim3(eu_blocks(S->e_cnt, 256 * 4, 4096)), dim3(256), S->p, S->cellmask, S->e_lo, S->e_cnt);
   return EULER_OK;
@@ -1002,19 +1001,18 @@ int eu_launch_velocity_update(euler_sim* S, float dt, int finish) {
     ring.n = S->s_ring_n > 0 ? S->s_ring_n : 1; ring.steps = ring.n; ring.use = finish && S->s_ring_n > 0;
     if (!ring.use) for (int k = 0; k < 8; ++k) ring.s[k] = S->p;      // (never read)
     const int do_max = S->slab_on ? 0 : 1;
-    if (do_max && S->maxsq_state != 0) HIPCHK(hipMemsetAsync(&S->ms->max_u2_bits, 0, 2 * sizeof(unsigned int), S->stream));      // (maxima no timestep consumed)
+    if (eu_vd_update_clears_maxima(&S->vd, do_max)) HIPCHK(hipMemsetAsync(&S->ms->max_u2_bits, 0, 2 * sizeof(unsigned int), S->stream));      // (maxima no timestep consumed)
     LAUNCH(S, KC_VELOCITY_UPDATE, k_velocity_update_para, dim3((unsigned)((size_t)(S->band_hi - S->band_lo) * (S->geom.T / VU_W))), dim3(256), S->utmp, S->vtmp, S->u, S->v, S->p, S->cellmask,
-           S->count, S->solid, S->geom, dt, S->sc, ring, S->ms, S->band_lo, do_max, (!S->slab_on && S->uv_zb) ? 1 : 0,
+           S->count, S->solid, S->geom, dt, S->sc, ring, S->ms, S->band_lo, do_max, eu_vd_update_skips_zeros(&S->vd, S->slab_on),
            eu_tile_map_on(S) ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr, S->tmap_nx);
-    S->uv_clean = 1;      // every sample without the fluid property, every wall's sample is zero now (k_zero_bounds4<true> of the next substep relies on it)
-    S->p_pending = ring.use ? 1 : 2;
-    if (do_max) S->maxsq_state = 2;      // the maxima of u, v as they stand are in ms (eu_launch_timestep: k_dt alone)
+    eu_vd_velocity_updated(&S->vd, 1, ring.use, do_max);
     return EULER_OK;
   }
   if (finish) { int rc = eu_launch_finish_p(S); if (rc) return rc; }
   dim3 grid((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4);
   LAUNCH(S, KC_VELOCITY_UPDATE, k_velocity_update, grid, dim3(256), S->utmp, S->vtmp, S->u, S->v, S->p, S->count,
          S->solid, S->geom, dt, S->row_lo, S->row_hi);
+  eu_vd_velocity_updated(&S->vd, 0, 0, 0);
   return EULER_OK;
 }
 

@@ -178,6 +178,7 @@ __device__ __forceinline__ float time_to(float p0, float p1, float vel) {   // m
 // <= 0.375 cells from p and the displacement stays <= 0.75 cells: still at most one boundary per axis.  With TR, uT / vT are not refreshed in tiles the last copy left
 // alone (k_transpose_for_markers, lean): such stale samples are never read here either - eu_interp<.., TR> uses a sample only where its corner bit in countT is set, and
 // that bit belongs to the sample's cell, not to the query point, so a midpoint lookup sees exactly the live samples a start-point lookup there would.
+// (The rule for any new reader of uT / vT / countT: euler_dev.h eu_interp, docs/stage_validity.md.)
 template <bool TR, bool RK2>
 __device__ __forceinline__ AdvectOut advect_one(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v,
                                                 const uint8_t* __restrict__ solid, float px, float py, float dt, float dt_mid) {
@@ -544,26 +545,25 @@ __global__ __launch_bounds__(256) void k_transpose_for_markers(const float* __re
 static bool eu_markers_column_major(euler_sim* S) {      // (whole-grid handles; EULER_OPT_MARKERS_ROWMAJOR: the row-major kernels, for A-B timing)
   const bool off = S->opt[EULER_OPT_MARKERS_ROWMAJOR] != 0;
   if (off || S->slab_on || !S->uT) return false;
-  const bool lean = eu_tile_map_on(S) && S->countT_clean == 2 && !S->solidT_dirty;
+  const bool lean = eu_vd_lean_transpose(&S->vd, eu_tile_map_on(S));
   LAUNCH(S, KC_MARKER_ADVECT, k_transpose_for_markers, dim3((S->X + 63) / 64, (S->Y + TM_ROWS - 1) / TM_ROWS), dim3(256), S->u, S->v, S->count, S->solid, S->uT, S->vT, S->countT, S->solidT,
-         S->X, S->Y, S->solidT_dirty, lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr, S->tmap_nx, S->tmap_n);
-  S->solidT_dirty = 0;
-  S->countT_clean = 1;
+         S->X, S->Y, eu_vd_solidT_due(&S->vd), lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr, S->tmap_nx, S->tmap_n);
+  eu_vd_transposed(&S->vd);
   return true;
 }
 
 __global__ void k_blocked_transpose(const uint8_t* __restrict__ sink, const uint8_t* __restrict__ solid, uint8_t* __restrict__ blockedT, int X, int Y);
 static int eu_blocked_current(euler_sim* S) {      // sink | solid, column-major (the solid / sink grids changed: scenario load, euler_set_field, a snapshot)
-  if (S->blocked_dirty) {
+  if (eu_vd_blocked_due(&S->vd)) {
     LAUNCH(S, KC_MARKER_BIN, k_blocked_transpose, dim3((S->X + 63) / 64, (S->Y + 63) / 64), dim3(256), S->sink, S->solid, S->blockedT, S->X, S->Y);
-    S->blocked_dirty = 0;
+    eu_vd_blocked_rebuilt(&S->vd);
   }
   return EULER_OK;
 }
 // the binning counters are all zero between two refreshes (k_narrow_counts<true> clears what it reads); a refresh that did not get that far leaves them marked
 static int eu_count32_clean(euler_sim* S) {
-  if (S->count32_dirty) HIPCHK(hipMemsetAsync(S->count32, 0, S->Cw * sizeof(unsigned int), S->stream));
-  S->count32_dirty = 1;      // (from here until the next k_narrow_counts<true>)
+  if (eu_vd_count32_must_clear(&S->vd)) HIPCHK(hipMemsetAsync(S->count32, 0, S->Cw * sizeof(unsigned int), S->stream));
+  eu_vd_binning_began(&S->vd);
   return EULER_OK;
 }
 
@@ -574,7 +574,6 @@ static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
   const float2* in = S->markers[S->cur];
   float2* out = S->markers[S->cur ^ 1];
   const unsigned nb = eu_blocks((size_t)n, 256), nb_b = eu_blocks((size_t)n, 256, 4096);
-  S->prebin_valid = 0;
   if (eu_markers_column_major(S)) {
     GridRef gt = g;
     gt.count = S->countT;
@@ -593,10 +592,10 @@ static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
     if (fuse) {
       LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, true, RK2>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
              S->blockedT, S->count32, S->delmask, S->Y, S->tmap + 2 * (size_t)S->tmap_n, S->tmap_nx, dt);
-      S->prebin_valid = 1;      // (consumed by the refresh that follows; anything else in between drops it: driver.hip)
     } else
       LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<true, false, RK2>), dim3(nb_b), dim3(256), in, out, S->uT, S->vT, S->solidT, gt, n, S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr,
              (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, dt);
+    eu_vd_advected_markers(&S->vd, fuse);      // (fused: consumed by the refresh that follows; anything else in between drops it)
     S->cur ^= 1;
     return EULER_OK;
   }
@@ -608,6 +607,7 @@ static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
          S->act_dt, S->ms, dt);
   LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false, RK2>), dim3(nb_b), dim3(256), in, out, S->u, S->v, S->solid, g, n,
          S->act_idx, S->act_dt, S->ms, (const unsigned int*)nullptr, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, dt);
+  eu_vd_advected_markers(&S->vd, 0);
   S->cur ^= 1;
   return EULER_OK;
 }
@@ -631,7 +631,7 @@ __global__ __launch_bounds__(256) void k_rotate_counts(uint8_t* __restrict__ pre
   }
 }
 
-// sink | solid per cell, COLUMN-major like count32 (static between scenario edits: rebuilt when euler_sim.blocked_dirty says so).  The marker array walks the grid column by
+// sink | solid per cell, COLUMN-major like count32 (static between scenario edits: rebuilt when eu_vd_blocked_due says so).  The marker array walks the grid column by
 // column, so a wave's 64 markers sit in ~16 cells of one column: in the row-major grids that is 16-17 cache lines per gather and two gathers per marker (1.37 ms at 8192^2,
 // bound by lines per gather like k_advect_markers_a: profiles/r04_marker_gather_experiment.md); here it is one gather out of one or two lines, next to the counters' own line.
 __global__ __launch_bounds__(256) void k_blocked_transpose(const uint8_t* __restrict__ sink, const uint8_t* __restrict__ solid, uint8_t* __restrict__ blockedT, int X, int Y) {
@@ -792,22 +792,20 @@ int eu_launch_refresh_counts(euler_sim* S) {      // (whole-grid handles; row sl
   const unsigned long long n = S->n_markers_host;
   unsigned long long* delmask = S->evmask;
   int rc;
-  const int touch_known = S->prebin_valid && S->opt[EULER_OPT_NO_TILE_MAP] == 0;      // (k_advect_bin_a2 / pass B marked every tile a marker entered)
-  if (S->prebin_valid) delmask = S->delmask;      // the advection pass in front binned what it wrote (k_advect_bin_a2): the counters and the delete ballot stand
+  const int touch_known = eu_vd_touch_known(&S->vd, S->opt[EULER_OPT_NO_TILE_MAP] != 0);      // (k_advect_bin_a2 / pass B marked every tile a marker entered)
+  if (eu_vd_prebinned(&S->vd)) delmask = S->delmask;      // the advection pass in front binned what it wrote (k_advect_bin_a2): the counters and the delete ballot stand
   else {
     if ((rc = eu_blocked_current(S)) || (rc = eu_count32_clean(S))) return rc;
     LAUNCH(S, KC_MARKER_BIN, k_bin_markers, dim3(eu_blocks((size_t)n, 256)), dim3(256), S->markers[S->cur], n, S->blockedT,
            S->count32, S->evmask, S->X, S->Y);
   }
-  S->prebin_valid = 0;
   rc = eu_ordered_select(S, delmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_deleted);
   if (rc) return rc;
   eu_marker_compact(S, delmask);
   // prev <- cur, cur <- the counters, the counters <- 0
   LAUNCH(S, KC_MARKER_BIN, k_narrow_counts<true>, dim3((S->X + 63) / 64, (S->win_hi - S->win_lo + 63) / 64), dim3(256), S->count, S->count32, S->X,
-         S->win_lo, S->win_hi, S->ms, 0, S->prev_count, S->tmap, S->tmap_nx, S->tmap_n, S->tmap_valid, touch_known);
-  S->tmap_valid = 1;      // (both maps are what this pass saw; euler_set_option(EULER_OPT_NO_TILE_MAP) only stops the READERS)
-  S->count32_dirty = 0;
+         S->win_lo, S->win_hi, S->ms, 0, S->prev_count, S->tmap, S->tmap_nx, S->tmap_n, eu_vd_tile_map(&S->vd, 0), touch_known);      // (do the maps it is about to rewrite describe the grids?)
+  eu_vd_refreshed(&S->vd);
   return EULER_OK;
 }
 
@@ -880,6 +878,7 @@ int eu_source_fill(euler_sim* S) {   // the parallel draws of this rank's append
 }
 
 int eu_launch_sources(euler_sim* S) {
+  eu_vd_sources_ran(&S->vd);      // (the stage, source cells or not)
   if (S->n_source_cells == 0) return EULER_OK;   // no '?' cells: the reference's loop body never runs
   LAUNCH(S, KC_SOURCES, k_source_mask, dim3(eu_blocks(S->C, 256)), dim3(256), S->source, S->count, S->C, S->cellmask64);
   int rc = eu_ordered_select(S, S->cellmask64, (S->C + 63) / 64, S->sel_idx, &S->ms->n_events);

@@ -549,7 +549,6 @@ struct Solve {
 static int project_begin(euler_sim* S, float dt, Solve& v) {
   S->s_launched = 0;      // (EULER_F_PCG_S: no multi-kernel iteration of this solve has run yet)
   S->z_halo_last = 0;
-  S->p_pending = 0;       // (the assembly writes p afresh: whatever the last solve left unfinished in memory is gone with it)
   S->pcg_fields_resident = 0;
   v.prev = *S->sc_host;      // (the previous solve's final scalars: a resident launch that has to be redone must not leave its own in their place)
   // the previous solve's final scalars are in sc_host by now (copied at its end, synced since)
@@ -615,7 +614,7 @@ static int project_resident(euler_sim* S, float dt, Solve& v) {
       if (err != 2) { S->res_fallbacks += 1; S->res_disabled = 1; }      // a wait ran out (the workgroups were not all resident - another process on the device?): the handle keeps to the multi-kernel path from here on
       // (error 2: more active chunks than fit - the scene grew; this system with the multi-kernel path: k_pcg_reset + the assembly again, written whole)
       S->solve_seq -= 1;
-      S->lean_ok = 0;
+      eu_vd_solver_arrays_foreign(&S->vd);
       S->res_skip_once = 1;
       *S->sc_host = v.prev;      // (solve_iters[] and the look-ahead of the redo are the previous SOLVE's, not the aborted launch's)
       return eu_launch_project(S, dt);

@@ -411,8 +411,8 @@ extern "C" int euler_load_state(euler_sim* S, const char* path) {
     if ((rc = eu_slab_after_restore(S))) return rc;      // collective: the source cells of all ranks
     if ((rc = eu_sync_marker_state(S))) return rc;
   } else if (rc) return rc;
-  S->lean_ok = 0;      // the solver arrays may hold another state's pressure and masks: the next assembly writes them whole
-  eu_state_replaced(S);      // (the solid / sink grids were replaced)
+  eu_vd_solver_arrays_foreign(&S->vd);      // the solver arrays may hold another state's pressure and masks: the next assembly writes them whole
+  eu_vd_replaced(&S->vd);      // (the solid / sink grids were replaced)
   memset(&S->stats, 0, sizeof S->stats);
   S->stats.frames = h0.frames; S->stats.total_substeps = h0.total_substeps; S->stats.total_pcg_iterations = h0.total_pcg_iterations;
   S->loaded = 1;

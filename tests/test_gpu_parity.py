@@ -1031,6 +1031,31 @@ def test_round_6_stage_forms_leave_the_same_bits_as_rounds_1_to_5(precond):
 
 
 @pytest.mark.gpu
+def test_a_viscous_velocity_stage_behind_a_projection_drops_the_timestep_shortcut():
+    """k_velocity_update_para leaves the maxima of u, v for the next timestep (k_dt alone).  With viscosity the velocity stage rewrites u, v - they are the diffusion's
+    Jacobi scratch - so PROJECT, ADVECT_VELOCITY, timestep must take the maxima of the arrays as they stand (eu_valid.h: advected_velocity(viscous)).  Two handles run
+    the same sequence; one then has its u written back unchanged, which drops the maxima the documented way: the same dt, the same u, v."""
+    from euler_amd import scenarios
+    sims = [ea.Simulation(96, 64, dot_mode=ea.DOT_SEQUENTIAL, viscosity=0.5).load_text(scenarios.dam_break(), upscale=True) for _ in range(2)]
+    for s in sims:
+        for _ in range(8):      # (from frame 8 on the dam break is fast enough for the CFL limit to set dt; at 5 both handles get the frame time whatever the maxima)
+            s.step()
+        dt = s.timestep(0.1)
+        for st in range(6):
+            s.stage(st, dt)
+        s.stage(ea.STAGE_PROJECT, dt)
+        s.stage(ea.STAGE_ADVECT_VELOCITY, dt)
+    a, b = sims
+    b.set(ea.F_U, b.get(ea.F_U))
+    dta, dtb = a.timestep(0.1), b.timestep(0.1)
+    print("dt", dta, dtb)
+    assert dta == dtb
+    assert_bits(a.get(ea.F_U), b.get(ea.F_U), "u")
+    assert_bits(a.get(ea.F_V), b.get(ea.F_V), "v")
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
 def test_round_6_stage_forms_at_configs2_size_over_frames():
     """The same comparison at BASELINE configs[2]'s size (8192^2 half tank, 134 M markers): the bit-exact tests against the recorded oracle run ONE substep from a fresh load,
     where the tile map is not valid yet - on grids this large its readers take 64 rows per workgroup (`rep`), a form the small grids never run.  Three frames, the solves
