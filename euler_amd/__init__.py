@@ -46,6 +46,12 @@ GAUGE_DTYPE = np.dtype({"names": ["kind", "x0", "y0", "x1", "y1", "reserved"], "
 GAUGE_REC_DTYPE = np.dtype({"names": ["cells", "fluid", "lo_x", "hi_x", "lo_y", "hi_y", "terms", "nonfinite", "a_pos", "a_neg", "b_pos", "b_neg", "max_a", "max_b"],
                             "formats": [np.uint32] * 8 + [np.uint64] * 4 + [np.float32] * 2,
                             "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 56, 64, 68], "itemsize": 72})
+# euler_forcing, euler_force_box (include/euler.h): the forcing record of euler_set_forcing and one force box ("pump")
+FORCE_BOXES_MAX = 64
+FORCING_DTYPE = np.dtype({"names": ["gx", "gy", "shake_x", "shake_y", "shake_hz", "shake_phase", "nboxes", "reserved", "reserved2"],
+                          "formats": [np.float32] * 4 + [np.float64] * 2 + [np.int32] * 2 + [np.float64],
+                          "offsets": [0, 4, 8, 12, 16, 24, 32, 36, 40], "itemsize": 48})
+FORCE_BOX_DTYPE = np.dtype({"names": ["x0", "y0", "x1", "y1", "fx", "fy"], "formats": [np.int32] * 4 + [np.float32] * 2, "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
 GAUGE_VALUES = ("a", "b", "mean_a", "depth")      # euler_gauge_values, four doubles
 DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
@@ -112,6 +118,7 @@ EXPORTS = [
     "euler_edit_box",
     "euler_flow_raster", "euler_flow_paint",
     "euler_gauges", "euler_gauge_derive",
+    "euler_forcing_default", "euler_set_forcing", "euler_get_forcing", "euler_forcing_at", "euler_get_time", "euler_set_time",
 ]
 
 
@@ -197,6 +204,12 @@ def load_library():
         "euler_flow_paint": (C.c_int, [vp, vp, i32, i32, i32, f64]),
         "euler_gauges": (C.c_int, [vp, vp, i32, vp, C.c_size_t]),
         "euler_gauge_derive": (C.c_int, [vp, i32, vp]),
+        "euler_forcing_default": (C.c_int, [vp]),
+        "euler_set_forcing": (C.c_int, [vp, vp, vp]),
+        "euler_get_forcing": (C.c_int, [vp, vp, vp, i32]),
+        "euler_forcing_at": (C.c_int, [vp, f64, C.POINTER(f32)]),
+        "euler_get_time": (C.c_int, [vp, C.POINTER(f64)]),
+        "euler_set_time": (C.c_int, [vp, f64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
@@ -335,6 +348,32 @@ def gauge_derive(rec, kind):
     out = np.zeros(len(GAUGE_VALUES), np.float64)
     _check_host(load_library().euler_gauge_derive(rec.ctypes.data, int(kind), out.ctypes.data), "euler_gauge_derive")
     return dict(zip(GAUGE_VALUES, (float(x) for x in out)))
+
+
+def forcing_default():
+    """The default forcing record (euler_forcing_default): gravity (0, -10), no shake, no boxes; FORCING_DTYPE, shape ()."""
+    f = np.zeros((), FORCING_DTYPE)
+    _check_host(load_library().euler_forcing_default(f.ctypes.data), "euler_forcing_default")
+    return f
+
+
+def forcing_record(gravity=(0.0, -10.0), shake=None, nboxes=0):
+    """A forcing record (FORCING_DTYPE, shape ()): gravity = (gx, gy); shake = None or (sx, sy, hz[, phase in radians])."""
+    f = forcing_default()
+    f["gx"], f["gy"] = gravity
+    if shake is not None:
+        f["shake_x"], f["shake_y"], f["shake_hz"] = shake[:3]
+        f["shake_phase"] = shake[3] if len(shake) > 3 else 0.0
+    f["nboxes"] = nboxes
+    return f
+
+
+def forcing_at(f, t):
+    """The uniform acceleration (ax, ay) of forcing record f at simulated time t, two np.float32 (euler_forcing_at, host only)."""
+    f = np.ascontiguousarray(f, FORCING_DTYPE).reshape(1)
+    a = (C.c_float * 2)()
+    _check_host(load_library().euler_forcing_at(f.ctypes.data, float(t), a), "euler_forcing_at")
+    return np.float32(a[0]), np.float32(a[1])
 
 
 SNAPSHOT_F32 = ("u", "v", "utmp", "vtmp")
@@ -546,6 +585,38 @@ class Simulation:
         dst = rec.ctypes.data if rec.size else np.zeros(1, GAUGE_REC_DTYPE).ctypes.data
         _check(self.L.euler_gauges(self.h, src, len(g), dst, rec.nbytes))
         return rec
+
+    def set_forcing(self, gravity=(0.0, -10.0), shake=None, boxes=()):
+        """Drive the tank (euler_set_forcing, docs/forcing.md): gravity = (gx, gy); shake = None or (sx, sy, hz[, phase]) - a harmonic acceleration of the
+        tank frame; boxes = a list of ((x0, y0, x1, y1), (fx, fy)) or an array of FORCE_BOX_DTYPE - accelerations added to the live faces of the boxes' cells
+        in list order."""
+        if isinstance(boxes, np.ndarray) and boxes.dtype == FORCE_BOX_DTYPE:
+            b = np.ascontiguousarray(boxes).reshape(-1)
+        else:
+            b = np.zeros(len(boxes), FORCE_BOX_DTYPE)
+            for k, (box, force) in enumerate(boxes):
+                b[k] = tuple(int(t) for t in box) + (float(force[0]), float(force[1]))
+        f = forcing_record(gravity, shake, len(b))
+        _check(self.L.euler_set_forcing(self.h, f.ctypes.data, b.ctypes.data if b.size else None))
+        return self
+
+    def forcing(self):
+        """(record, boxes) as set (euler_get_forcing): FORCING_DTYPE of shape () and an array of FORCE_BOX_DTYPE."""
+        f = np.zeros((), FORCING_DTYPE)
+        b = np.zeros(FORCE_BOXES_MAX, FORCE_BOX_DTYPE)
+        _check(self.L.euler_get_forcing(self.h, f.ctypes.data, b.ctypes.data, FORCE_BOXES_MAX))
+        return f, b[: int(f["nboxes"])].copy()
+
+    @property
+    def time(self):
+        """The handle's clock of simulated time (euler_get_time): 0 after a load, += dt behind every substep."""
+        t = C.c_double(0)
+        _check(self.L.euler_get_time(self.h, C.byref(t)))
+        return t.value
+
+    @time.setter
+    def time(self, t):
+        _check(self.L.euler_set_time(self.h, float(t)))
 
     def edit_box(self, op, box):
         """Edit box = (x0, y0, x1, y1), inclusive, and the markers in it on the device (euler_edit_box, docs/editing.md): op is one of EDIT_SOLID,

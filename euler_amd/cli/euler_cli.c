@@ -12,7 +12,8 @@
  *   euler [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace]
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
- *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] <scenario>
+ *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
+ *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
@@ -40,6 +41,11 @@
  * cells the box's fluid touches) or flux (through the right and top faces of its cells); --gauges writes FILE (created or truncated) as CSV: a header line,
  * then one line per gauge after every N-th frame (--gauges-every, default 1; frame 0 included), all gauges of a frame from ONE euler_gauges call
  * (docs/gauges.md).  --gauge without --gauges or the reverse, a malformed spec, a box outside the interior and a 65th gauge are usage errors.
+ * --gravity, --shake and --force drive the tank (euler_set_forcing, docs/forcing.md), set once behind the load (also behind --resume: a snapshot records
+ * neither the forcing nor the clock): the uniform acceleration (default 0,-10), a harmonic acceleration of the tank frame of amplitude SX,SY at HZ per second
+ * of simulated time with the phase in degrees, and (up to 64 times) an acceleration FX,FY on the live faces of the cells of the box [X0, X1] x [Y0, Y1], in
+ * command-line order.  A malformed spec, a 65th box, a box outside the interior and a value out of range (beyond 1e4 in size, not finite, HZ < 0) are usage
+ * errors.  Without the three the forcing is never touched.
  */
 #include <errno.h>
 #include <signal.h>
@@ -53,11 +59,12 @@
 
 #include "euler.h"
 #include "cli_gauges.h"
+#include "cli_forcing.h"
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -310,6 +317,10 @@ int main(int argc, char** argv) {
   int n_edits = 0;
   int paint = -1;
   double paint_scale[3] = {1.0, 1000.0, 10.0};
+  euler_forcing forcing;
+  euler_force_box force_boxes[MAX_FORCE_BOXES];
+  int forcing_given = 0, n_force_boxes = 0;
+  euler_forcing_default(&forcing);
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -377,6 +388,10 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--gauge") && i + 1 < argc) { if (n_gauges == MAX_GAUGES || parse_gauge(argv[++i], &gauge_list[n_gauges++]) != 0) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--gauges") && i + 1 < argc) gauges = argv[++i];
     else if (!strcmp(argv[i], "--gauges-every") && i + 1 < argc) { gauges_every = atoi(argv[++i]); if (gauges_every < 1) { usage(argv[0]); return 1; } }
+    /* forcing: gravity vector, shaken tank, force boxes (docs/forcing.md) */
+    else if (!strcmp(argv[i], "--gravity") && i + 1 < argc) { if (parse_gravity(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
+    else if (!strcmp(argv[i], "--shake") && i + 1 < argc) { if (parse_shake(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
+    else if (!strcmp(argv[i], "--force") && i + 1 < argc) { if (n_force_boxes == MAX_FORCE_BOXES || parse_force(argv[++i], &force_boxes[n_force_boxes++]) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
@@ -394,6 +409,11 @@ int main(int argc, char** argv) {
     const euler_gauge* gb = &gauge_list[k];
     if (gb->x0 < 1 || gb->y0 < 1 || gb->x1 > cfg.X - 2 || gb->y1 > cfg.Y - 2 || gb->x0 > gb->x1 || gb->y0 > gb->y1) { usage(argv[0]); return 1; }
   }
+  for (int k = 0; k < n_force_boxes; ++k) {
+    const euler_force_box* fb = &force_boxes[k];
+    if (fb->x0 < 1 || fb->y0 < 1 || fb->x1 > cfg.X - 2 || fb->y1 > cfg.Y - 2 || fb->x0 > fb->x1 || fb->y0 > fb->y1) { usage(argv[0]); return 1; }
+  }
+  forcing.nboxes = n_force_boxes;
   const int ppm_size_given = ppm_w > 0;
   if (ppm && view) {      /* the size follows the box frame by frame (below) */
     if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
@@ -428,7 +448,8 @@ int main(int argc, char** argv) {
   memcpy(app.paint_scale, paint_scale, sizeof paint_scale);
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
-      (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK) {
+      (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
+      (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK)) {
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }

@@ -275,7 +275,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   eu_rccl_release(S);
   eu_slab_release(S);
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf}) eu_devbuf_release(S, b);
+  for (eu_devbuf* b : {&S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf}) eu_devbuf_release(S, b);
   // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
   // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
   const size_t wo = S->shifted ? S->win_off : 0;
@@ -339,6 +339,7 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
   if (!S) return EULER_ENOMEM;
   g_alloc_bytes = 0;
   S->cfg = *cfg;
+  (void)euler_forcing_default(&S->forcing);      // (the reference's gravity until euler_set_forcing says otherwise)
   if (S->cfg.max_iterations <= 0) S->cfg.max_iterations = 100;
   if (S->cfg.max_substeps <= 0) S->cfg.max_substeps = 8;
   if (S->cfg.frame_time <= 0.f) S->cfg.frame_time = 0.1f;
@@ -607,6 +608,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   rc = eu_sync_marker_state(S);
   if (rc) return rc;
   memset(&S->stats, 0, sizeof(S->stats));
+  S->time = 0.0;      // (the forcing stays as set: docs/forcing.md)
   S->loaded = 1;
   return EULER_OK;
 }
@@ -822,6 +824,7 @@ extern "C" int euler_substep(euler_sim* S, float dt) {
   rc = eu_sync_marker_state(S);
   if (rc) return rc;
   account_substep(S, dt);
+  S->time += (double)dt;
   S->stats.total_pcg_iterations += (uint64_t)S->sc_host->iters;
   S->stats.last_pcg_iterations = S->sc_host->iters;
   S->stats.last_residual = S->sc_host->rnorm;
@@ -842,6 +845,7 @@ extern "C" int euler_step(euler_sim* S) {
     rc = substep_async(S, dt);
     if (rc) return rc;
     account_substep(S, dt);
+    S->time += (double)dt;      // (the next substep's forcing is taken at its own start: docs/forcing.md)
     ++nsub;
   }
   int rc = S->slab_on ? eu_slab_error_sync(S) : EULER_OK;      // an overflow on one rank fails the frame on every rank

@@ -156,6 +156,14 @@ struct euler_sim {
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
   eu_devbuf ov_buf, diag_buf, vr_buf, flow_buf, gauge_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
                           // raster, euler_flow_raster's records, euler_gauges' records and chunk table; each allocated by its pass's first call and grown on demand
+  // euler_set_forcing (docs/forcing.md): the record and the boxes as set, whether the uniform part differs from the reference's (0, EU_G) - only then do the forced
+  // instantiations of the velocity advection run -, the clock, and on the device the boxes with their tile table (k_forcing.hip; uploaded once per euler_set_forcing)
+  euler_forcing forcing;
+  euler_force_box force_boxes[EULER_FORCE_BOXES_MAX];
+  int force_uniform;
+  unsigned int force_ntiles;
+  double time;            // simulated time: 0 after a load, += (double)dt behind every substep
+  eu_devbuf force_buf;
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -369,6 +377,7 @@ int eu_launch_refresh_counts(euler_sim* S);
 int eu_launch_sources(euler_sim* S);
 int eu_launch_extrapolate(euler_sim* S);
 int eu_launch_advect_velocity(euler_sim* S, float dt);
+int eu_launch_force_boxes(euler_sim* S, float dt);   // k_forcing.hip: the force boxes of euler_set_forcing over utmp / vtmp (inside eu_launch_advect_velocity)
 int eu_launch_diffuse(euler_sim* S, float dt);     // the diffusion extension alone (row slabs: behind the ghost rows of utmp / vtmp)
 int eu_launch_project(euler_sim* S, float dt);
 int eu_resident_capacity(euler_sim* S, int f32);            // k_resident.hip: workgroups of the resident PCG kernel the device holds at once

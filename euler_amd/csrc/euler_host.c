@@ -2,7 +2,8 @@
  * euler_host.c — host-only C parts of libeuler_hip.so: scenario text -> cell grids, the
  * xorshift64* stream, initial marker seeding, the ASCII frame formatter, and the formatters of the
  * whole-domain overview's records (text through the same frame formatter, RGB), the magnified frame of the viewport, the values derived from a diagnostics record,
- * the painter that shows a field of the flow raster through those formatters, and the host side of the batched gauges (list check, chunk table, derived values).
+ * the painter that shows a field of the flow raster through those formatters, the host side of the batched gauges (list check, chunk table, derived values), and the host side of the forcing (defaults, the uniform acceleration at a time, the check of
+ * the record and its boxes, the tile table).
  *
  * These are the pieces of the reference's sim_init (main.c:209-274) and draw_rows
  * (main.c:914-951) that never touch the hot path; they run once (init) or over a terminal-sized
@@ -477,6 +478,66 @@ size_t eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out) {
         c->y0 = ty == ty0 ? g[k].y0 : ty << 6; c->y1 = ty == ty1 ? g[k].y1 : (ty << 6) + 63;
       }
   }
+  return m;
+}
+
+/* ---- forcing: the record's defaults and its uniform part, the list checked and cut into the tile table (include/euler.h, docs/forcing.md) ---- */
+
+int euler_forcing_default(euler_forcing* f) {
+  if (!f) return EULER_EINVAL;
+  memset(f, 0, sizeof *f);
+  f->gy = -10.f;      /* k_gravity (main.c:60) */
+  return EULER_OK;
+}
+
+int euler_forcing_at(const euler_forcing* f, double t, float a[2]) {
+  if (!f || !a) return EULER_EINVAL;
+  const double s = sin(2.0 * 3.14159265358979323846 * f->shake_hz * t + f->shake_phase);
+  a[0] = (float)((double)f->gx + (double)f->shake_x * s);
+  a[1] = (float)((double)f->gy + (double)f->shake_y * s);
+  return EULER_OK;
+}
+
+static int force_value_ok(float x) { return isfinite(x) && fabsf(x) <= 1e4f; }
+
+int eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32_t X, int32_t Y, char* why, size_t cap) {
+#define REFUSE(...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return EULER_EINVAL; } while (0)
+  if (f->reserved != 0 || f->reserved2 != 0.0) REFUSE("reserved and reserved2 must be 0");
+  if (!force_value_ok(f->gx) || !force_value_ok(f->gy) || !force_value_ok(f->shake_x) || !force_value_ok(f->shake_y))
+    REFUSE("gravity (%g, %g) and shake (%g, %g) must be finite and at most 1e4 in size", (double)f->gx, (double)f->gy, (double)f->shake_x, (double)f->shake_y);
+  if (!isfinite(f->shake_hz) || f->shake_hz < 0.0 || !isfinite(f->shake_phase)) REFUSE("shake_hz %g must be finite and >= 0, shake_phase %g finite", f->shake_hz, f->shake_phase);
+  if (f->nboxes < 0 || f->nboxes > EULER_FORCE_BOXES_MAX) REFUSE("%d boxes (0 ... %d)", f->nboxes, EULER_FORCE_BOXES_MAX);
+  if (f->nboxes > 0 && !boxes) REFUSE("%d boxes and a null list", f->nboxes);
+  for (int32_t k = 0; k < f->nboxes; ++k)
+    if (!force_value_ok(boxes[k].fx) || !force_value_ok(boxes[k].fy)) REFUSE("box %d: force (%g, %g) must be finite and at most 1e4 in size", k, (double)boxes[k].fx, (double)boxes[k].fy);
+  for (int32_t k = 0; k < f->nboxes; ++k) {
+    const euler_force_box* b = boxes + k;
+    if (b->x0 < 1 || b->y0 < 1 || b->x1 > X - 2 || b->y1 > Y - 2 || b->x0 > b->x1 || b->y0 > b->y1)
+      REFUSE("box %d: [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", k, b->x0, b->x1, b->y0, b->y1, X - 2, Y - 2);
+  }
+#undef REFUSE
+  return EULER_OK;
+}
+
+/* (eu_gauge_chunks cuts every box for itself, a tile that n boxes touch n times; here a tile comes once and carries its boxes, so the tiles' bit sets are formed
+ * over the tile grid and the touched ones listed row by row) */
+size_t eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
+  if (n < 1) return 0;
+  const int32_t tnx = (X + 63) >> 6, tny = (Y + 63) >> 6;
+  uint64_t* set = (uint64_t*)calloc((size_t)tnx * (size_t)tny, sizeof(uint64_t));
+  if (!set) return (size_t)-1;
+  for (int32_t k = 0; k < n; ++k)
+    for (int32_t ty = b[k].y0 >> 6; ty <= b[k].y1 >> 6; ++ty)
+      for (int32_t tx = b[k].x0 >> 6; tx <= b[k].x1 >> 6; ++tx) set[(size_t)ty * tnx + tx] |= 1ull << k;
+  size_t m = 0;
+  for (int32_t ty = 0; ty < tny; ++ty)
+    for (int32_t tx = 0; tx < tnx; ++tx) {
+      const uint64_t s = set[(size_t)ty * tnx + tx];
+      if (!s) continue;
+      if (out) { out[m].tx = tx; out[m].ty = ty; out[m].boxes = s; }
+      ++m;
+    }
+  free(set);
   return m;
 }
 

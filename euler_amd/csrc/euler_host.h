@@ -17,6 +17,11 @@ int      euler_seed_markers_rows(const uint8_t* fluid, int32_t X, int32_t Y, int
 typedef struct eu_gauge_chunk { int32_t gauge, kind, x0, y0, x1, y1; } eu_gauge_chunk;
 int      eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what);   /* the index of the first gauge refused (what: why), -1: none */
 size_t   eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out);   /* out == NULL: the count only; the list must have passed eu_gauge_check */
+/* euler_set_forcing (k_forcing.hip, docs/forcing.md): the record and the list checked, and the list cut along the 64 x 64 tile grid into a TILE TABLE: one entry per
+ * tile that any box touches, with the boxes that touch it as a bit set - bit k = box k, walked from bit 0 up: the ascending list (at most 64 boxes) */
+typedef struct eu_force_tile { int32_t tx, ty; uint64_t boxes; } eu_force_tile;
+int      eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
+size_t   eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);   /* out == NULL: the count only; the list must have passed eu_forcing_check; (size_t)-1: no memory */
 #ifdef __cplusplus
 }
 #endif

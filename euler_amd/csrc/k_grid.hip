@@ -250,11 +250,13 @@ int eu_launch_extrapolate(euler_sim* S) {
 // gravity it adds to non-fluid faces never survive).
 // RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the midpoint velocity (euler_dev.h eu_mid_vel_*); everything else as it stands
 // MC (EULER_OPT_ADVECT_MACCORMACK): the forward pass - the same values without gravity, into the scratch grids that k_mc_correct_velocity reads
-template <bool RK2, bool MC = false>
-__global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict__ u, const float* __restrict__ v,
-                                                         float* __restrict__ uout, float* __restrict__ vout,
-                                                         const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
-                                                         const uint8_t* __restrict__ tmap, int tnx, int tn, int rep) {
+// FORCED (euler_set_forcing, docs/forcing.md): the uniform acceleration (ax, ay) of the substep stands where EU_G stands; a u face is touched only when ax != 0.f
+// (x + 0.f is not x for x = -0.f).  The kernels below are the body under the names and signatures they always had, and under new ones that take (ax, ay).
+template <bool RK2, bool MC, bool FORCED>
+__device__ __forceinline__ void advect_velocity_body(const float* __restrict__ u, const float* __restrict__ v,
+                                                     float* __restrict__ uout, float* __restrict__ vout,
+                                                     const uint8_t* __restrict__ solid, const GridRef& g, float dt, int y0, int y1,
+                                                     const uint8_t* __restrict__ tmap, int tnx, int tn, int rep, float ax, float ay) {
   const int X = g.X, Y = g.Y;
   // round 6 (tmap: whole-grid handles whose utmp / vtmp this kernel wrote one refresh ago): a tile with no water in or next to it now and then holds the zeros it would get.
   // A workgroup takes 64 columns x 4 rep rows (rep = 16 on large grids: the tile; a wave that only looks at the map and leaves still costs its microsecond - 16384^2: 2.9 M of them)
@@ -274,6 +276,7 @@ __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict
         if (RK2) { const float2 m = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
         const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;     // main.c:392-393
         out = eu_interp<1>(g, u, px, py);
+        if (FORCED && !MC && ax != 0.f) out += ax * dt;
       }
       uout[i] = out;
     }
@@ -285,22 +288,36 @@ __global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict
         if (RK2) { const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
         const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
         out = eu_interp<2>(g, v, px, py);
-        if (!MC) out += EU_G * dt;                                        // main.c:542
+        if (!MC) out += (FORCED ? ay : EU_G) * dt;                        // main.c:542
       }
       vout[i] = out;
     }
   }
 }
+template <bool RK2, bool MC = false>
+__global__ __launch_bounds__(256) void k_advect_velocity(const float* __restrict__ u, const float* __restrict__ v,
+                                                         float* __restrict__ uout, float* __restrict__ vout,
+                                                         const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
+                                                         const uint8_t* __restrict__ tmap, int tnx, int tn, int rep) {
+  advect_velocity_body<RK2, MC, false>(u, v, uout, vout, solid, g, dt, y0, y1, tmap, tnx, tn, rep, 0.f, EU_G);
+}
+template <bool RK2>
+__global__ __launch_bounds__(256) void k_advect_velocity_forced(const float* __restrict__ u, const float* __restrict__ v,
+                                                                float* __restrict__ uout, float* __restrict__ vout,
+                                                                const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
+                                                                const uint8_t* __restrict__ tmap, int tnx, int tn, int rep, float ax, float ay) {
+  advect_velocity_body<RK2, false, true>(u, v, uout, vout, solid, g, dt, y0, y1, tmap, tnx, tn, rep, ax, ay);
+}
 
 // EULER_OPT_ADVECT_MACCORMACK, the correction pass (docs/advection_maccormack.md): per live face the forward trace again (its value and the limiter's lo / hi, recomputed
 // rather than stored), the backward trace - the same code with -dt - into the forward results uf / vf, half the round-trip error added, the result clamped to [lo, hi].
 // Writes utmp / vtmp like k_advect_velocity<RK2> (0 on faces that are not live, gravity last); the same tile-map skip.
-template <bool RK2>
-__global__ __launch_bounds__(256) void k_mc_correct_velocity(const float* __restrict__ u, const float* __restrict__ v,
-                                                             const float* __restrict__ uf, const float* __restrict__ vf,
-                                                             float* __restrict__ uout, float* __restrict__ vout,
-                                                             const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
-                                                             const uint8_t* __restrict__ tmap, int tnx, int tn, int rep) {
+template <bool RK2, bool FORCED>
+__device__ __forceinline__ void mc_correct_velocity_body(const float* __restrict__ u, const float* __restrict__ v,
+                                                         const float* __restrict__ uf, const float* __restrict__ vf,
+                                                         float* __restrict__ uout, float* __restrict__ vout,
+                                                         const uint8_t* __restrict__ solid, const GridRef& g, float dt, int y0, int y1,
+                                                         const uint8_t* __restrict__ tmap, int tnx, int tn, int rep, float ax, float ay) {
   const int X = g.X, Y = g.Y;
   if (tmap && eu_tiles_idle(tmap, tnx, tn, (y0 + (int)blockIdx.y * 4 * rep) >> 6, (int)blockIdx.x, 1)) return;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -327,6 +344,7 @@ __global__ __launch_bounds__(256) void k_mc_correct_velocity(const float* __rest
         const float f = eu_interp_mc<1, true>(g, u, px, py, a1, lo, hi);
         const float b = eu_interp_mc<1, false>(g, uf, qx, qy, a2, lo, hi);
         out = eu_mc_correct(f, u0, b, a1, a2, lo, hi);
+        if (FORCED && ax != 0.f) out += ax * dt;                          // after the clamp, as gravity
       }
       uout[i] = out;
     }
@@ -347,11 +365,27 @@ __global__ __launch_bounds__(256) void k_mc_correct_velocity(const float* __rest
         const float f = eu_interp_mc<2, true>(g, v, px, py, a1, lo, hi);
         const float b = eu_interp_mc<2, false>(g, vf, qx, qy, a2, lo, hi);
         out = eu_mc_correct(f, v0, b, a1, a2, lo, hi);
-        out += EU_G * dt;                                                 // main.c:542, after the clamp
+        out += (FORCED ? ay : EU_G) * dt;                                 // main.c:542, after the clamp
       }
       vout[i] = out;
     }
   }
+}
+template <bool RK2>
+__global__ __launch_bounds__(256) void k_mc_correct_velocity(const float* __restrict__ u, const float* __restrict__ v,
+                                                             const float* __restrict__ uf, const float* __restrict__ vf,
+                                                             float* __restrict__ uout, float* __restrict__ vout,
+                                                             const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
+                                                             const uint8_t* __restrict__ tmap, int tnx, int tn, int rep) {
+  mc_correct_velocity_body<RK2, false>(u, v, uf, vf, uout, vout, solid, g, dt, y0, y1, tmap, tnx, tn, rep, 0.f, EU_G);
+}
+template <bool RK2>
+__global__ __launch_bounds__(256) void k_mc_correct_velocity_forced(const float* __restrict__ u, const float* __restrict__ v,
+                                                                    const float* __restrict__ uf, const float* __restrict__ vf,
+                                                                    float* __restrict__ uout, float* __restrict__ vout,
+                                                                    const uint8_t* __restrict__ solid, GridRef g, float dt, int y0, int y1,
+                                                                    const uint8_t* __restrict__ tmap, int tnx, int tn, int rep, float ax, float ay) {
+  mc_correct_velocity_body<RK2, true>(u, v, uf, vf, uout, vout, solid, g, dt, y0, y1, tmap, tnx, tn, rep, ax, ay);
 }
 
 // EXTENSION (the reference is inviscid): one explicit diffusion step of the advected
@@ -412,20 +446,39 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   if (lean) while (rep < 16 && ((size_t)S->X * S->Y >> 22) >= (size_t)(2 * rep)) rep *= 2;      // (2048^2: 1, 4096^2: 4, 8192^2 and beyond: 16 - at least 16 K workgroups)
   grid.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
   const uint8_t* tm = lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr;
+  // euler_set_forcing (docs/forcing.md; never on a row slab): the uniform acceleration of this substep, formed once on the host at the handle's clock.  A handle that
+  // holds the default record launches what it always launched
+  float acc[2] = {0.f, EU_G};
+  if (S->force_uniform) (void)euler_forcing_at(&S->forcing, S->time, acc);
   if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (never on a row slab either; the forward pass skips the same tiles: no mask reads the scratch there)
     if (S->opt[EULER_OPT_ADVECT_RK2]) {
       LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<true, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
-             S->tmap_nx, S->tmap_n, rep);
+      if (S->force_uniform)
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity_forced<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+               S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
+      else
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+               S->tmap_nx, S->tmap_n, rep);
     } else {
       LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<false, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
-             S->tmap_nx, S->tmap_n, rep);
+      if (S->force_uniform)
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity_forced<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+               S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
+      else
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+               S->tmap_nx, S->tmap_n, rep);
     }
+  } else if (S->force_uniform) {
+    if (S->opt[EULER_OPT_ADVECT_RK2])
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity_forced<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
+    else
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity_forced<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
   } else if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
   else
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+  // the force boxes (k_forcing.hip): live faces of utmp / vtmp only, so what the advection leaves for the next pass stands as it is (docs/stage_validity.md)
+  if (S->forcing.nboxes > 0) { int rc = eu_launch_force_boxes(S, dt); if (rc) return rc; }
   eu_vd_advected_velocity(&S->vd, S->cfg.viscosity > 0.f);      // (the diffusion extension writes utmp / vtmp behind this, with u, v as its scratch)
   // (a row-slab handle exchanges the ghost rows of utmp / vtmp between the two: eu_slab_substep calls eu_launch_diffuse itself)
   return S->slab_on ? EULER_OK : eu_launch_diffuse(S, dt);

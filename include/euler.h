@@ -543,6 +543,39 @@ int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_val
 enum { EULER_EDIT_SOLID = 0, EULER_EDIT_CLEAR = 1, EULER_EDIT_SINK = 2, EULER_EDIT_SOURCE = 3, EULER_EDIT_FILL = 4, EULER_EDIT_DRAIN = 5 };
 int euler_edit_box(euler_sim* sim, int32_t op, int32_t x0, int32_t y0, int32_t x1, int32_t y1);
 
+/* ---- forcing: gravity vector, shaken tank, force boxes (docs/forcing.md) --------------------------- */
+/* Tilt or shake the tank, drive a current with a pump, run in reduced or zero gravity.  The handle keeps a double clock `time` (0 after a load, advanced
+ * by time += (double)dt behind every substep of euler_step / euler_substep, in substep order; euler_stage does not advance it; it is not part of a
+ * snapshot: euler_load_state leaves it at 0 and the forcing as set, the caller restores both).  The uniform acceleration of a substep is
+ * euler_forcing_at(f, time at the start of that substep): in double, a[0] = (float)(gx + shake_x sin(2 pi shake_hz t + shake_phase)), a[1] likewise from
+ * gy, shake_y.  Per live face (live as for the FLUX gauge above), float32 without contraction, last in the velocity advection (with MacCormack: behind the
+ * clamp): a live v face gets out += a[1] * dt, always; a live u face gets out += a[0] * dt ONLY when a[0] != 0.f (x + 0.f is not x for x = -0.f).  Then,
+ * in front of the diffusion extension, the boxes: for k = 0 .. nboxes - 1 in list order, for every cell i of box k, utmp[i] += fx_k * dt where the cell's
+ * right face is live and vtmp[i] += fy_k * dt where its top face is live (the product rounded, then the add).  Boxes may overlap and repeat: the adds on a
+ * face come in list order.  A face that is not live stays 0.  The default record (0, -10, no shake, no boxes) is the reference's k_gravity: a handle that
+ * holds it runs the kernels and produces the bits of one that never called euler_set_forcing. */
+#define EULER_FORCE_BOXES_MAX 64
+typedef struct euler_force_box { int32_t x0, y0, x1, y1; float fx, fy; } euler_force_box;   /* 24 bytes; inclusive, inside [1, X-2] x [1, Y-2] */
+typedef struct euler_forcing {     /* 48 bytes, no padding */
+  float   gx, gy;                  /* uniform acceleration; default 0, -10 */
+  float   shake_x, shake_y;        /* amplitudes of a harmonic acceleration of the tank frame; default 0 */
+  double  shake_hz, shake_phase;   /* frequency in 1 / s of simulated time, phase in radians */
+  int32_t nboxes, reserved;        /* reserved must be 0 */
+  double  reserved2;               /* must be 0 */
+} euler_forcing;
+int euler_forcing_default(euler_forcing* f);
+/* Refusals, in this order: a null sim or f (EULER_EINVAL); a row-slab handle (EULER_ESTATE: a slab keeps the reference's gravity); nothing loaded
+ * (EULER_ESTATE); reserved or reserved2 not 0; a non-finite value or |gx|, |gy|, |shake_x|, |shake_y| > 1e4; shake_hz < 0 or non-finite, a non-finite
+ * phase; nboxes outside [0, EULER_FORCE_BOXES_MAX] or boxes == NULL with nboxes > 0; a box's fx or fy non-finite or beyond 1e4 in size (a value comes in
+ * front of any box's place); a box outside the interior or with x0 > x1 / y0 > y1, naming the index of the first such box (all EULER_EINVAL).  A refused call changes and allocates nothing.  May be called between any two calls - frames,
+ * substeps, stages; touches no grid.  The boxes and their tile table go to a device buffer of the handle once per call (grown on demand, counted in
+ * euler_hbm_bytes, released by euler_destroy). */
+int euler_set_forcing(euler_sim* sim, const euler_forcing* f, const euler_force_box* boxes);   /* boxes may be NULL when nboxes == 0 */
+int euler_get_forcing(euler_sim* sim, euler_forcing* f, euler_force_box* boxes, int32_t cap);  /* boxes may be NULL (the record alone); else cap >= nboxes */
+int euler_forcing_at(const euler_forcing* f, double t, float a[2]);   /* host only, no GPU */
+int euler_get_time(euler_sim* sim, double* t);
+int euler_set_time(euler_sim* sim, double t);   /* EULER_EINVAL: a non-finite t */
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
