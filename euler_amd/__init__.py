@@ -52,6 +52,12 @@ FORCING_DTYPE = np.dtype({"names": ["gx", "gy", "shake_x", "shake_y", "shake_hz"
                           "formats": [np.float32] * 4 + [np.float64] * 2 + [np.int32] * 2 + [np.float64],
                           "offsets": [0, 4, 8, 12, 16, 24, 32, 36, 40], "itemsize": 48})
 FORCE_BOX_DTYPE = np.dtype({"names": ["x0", "y0", "x1", "y1", "fx", "fy"], "formats": [np.int32] * 4 + [np.float32] * 2, "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
+# euler_tracer (include/euler.h): one passive tracer; EULER_TRACER_* flag bits; EULER_TRACER_RASTER_ALL of euler_tracer_raster
+TRACERS_MAX = 1 << 22
+TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER_WAS_DRY = 1, 2, 4, 8, 16, 32
+TRACER_RASTER_ALL = 1
+TRACER_DTYPE = np.dtype({"names": ["x", "y", "path", "age", "wet_time", "substeps", "flags", "reserved"],
+                         "formats": [np.float32] * 5 + [np.uint32] * 3, "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 GAUGE_VALUES = ("a", "b", "mean_a", "depth")      # euler_gauge_values, four doubles
 DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
@@ -119,6 +125,7 @@ EXPORTS = [
     "euler_flow_raster", "euler_flow_paint",
     "euler_gauges", "euler_gauge_derive",
     "euler_forcing_default", "euler_set_forcing", "euler_get_forcing", "euler_forcing_at", "euler_get_time", "euler_set_time",
+    "euler_tracers_add", "euler_tracers_count", "euler_tracers_get", "euler_tracers_clear", "euler_tracer_raster", "euler_tracer_paint",
 ]
 
 
@@ -210,11 +217,19 @@ def load_library():
         "euler_forcing_at": (C.c_int, [vp, f64, C.POINTER(f32)]),
         "euler_get_time": (C.c_int, [vp, C.POINTER(f64)]),
         "euler_set_time": (C.c_int, [vp, f64]),
+        "euler_tracers_add": (C.c_int, [vp, vp, C.c_size_t]),
+        "euler_tracers_count": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
+        "euler_tracers_get": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
+        "euler_tracers_clear": (C.c_int, [vp]),
+        "euler_tracer_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_tracer_paint": (C.c_int, [vp, vp, i32, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)   # AttributeError here = a symbol include/euler.h declares is not exported
         fn.restype = res
         fn.argtypes = args
+    L.eu_tracer_lattice.restype = C.c_size_t      # (internal, euler_host.h: the lattice of a box as the command line seeds it)
+    L.eu_tracer_lattice.argtypes = [i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 
@@ -374,6 +389,33 @@ def forcing_at(f, t):
     a = (C.c_float * 2)()
     _check_host(load_library().euler_forcing_at(f.ctypes.data, float(t), a), "euler_forcing_at")
     return np.float32(a[0]), np.float32(a[1])
+
+
+def tracer_lattice(box, k):
+    """The k x k lattice (k = 1, 2 or 4) of every cell of box = (x0, y0, x1, y1), inclusive: float32 positions of shape (n, 2), cell x outer, cell y inner,
+    i outer, j inner, at x + (i + 0.5) / k, y + (j + 0.5) / k - what `euler --tracer-box` adds (docs/tracers.md)."""
+    x0, y0, x1, y1 = (int(t) for t in box)
+    L = load_library()
+    n = L.eu_tracer_lattice(x0, y0, x1, y1, int(k), None)
+    if n == 0:
+        raise ValueError("tracer_lattice: a box with x0 <= x1, y0 <= y1 and k = 1, 2 or 4")
+    xy = np.empty((n, 2), np.float32)
+    L.eu_tracer_lattice(x0, y0, x1, y1, int(k), xy.ctypes.data)
+    return xy
+
+
+def tracer_paint(counts, px, fg, bg=None):
+    """A painted copy of the overview records px: where the tracer raster `counts` of the same box and raster is > 0 a water pixel's dye shows the linear
+    colour fg, elsewhere bg (None: it stays) - euler_tracer_paint, so that overview_text / view_text with rainbow and overview_rgb(IMAGE_DYE) draw the tracers."""
+    px = _overview_records(px).copy()
+    counts = np.ascontiguousarray(counts, np.uint32)
+    if counts.shape != px.shape:
+        raise ValueError("tracer_paint: counts of shape %r for overview records of shape %r" % (counts.shape, px.shape))
+    h, w = px.shape
+    f = np.ascontiguousarray(fg, np.float32).reshape(3)
+    b = None if bg is None else np.ascontiguousarray(bg, np.float32).reshape(3)
+    _check_host(load_library().euler_tracer_paint(counts.ctypes.data, px.ctypes.data, w, h, f.ctypes.data, None if b is None else b.ctypes.data), "euler_tracer_paint")
+    return px
 
 
 SNAPSHOT_F32 = ("u", "v", "utmp", "vtmp")
@@ -617,6 +659,41 @@ class Simulation:
     @time.setter
     def time(self, t):
         _check(self.L.euler_set_time(self.h, float(t)))
+
+    # --- passive tracers (docs/tracers.md)
+    def add_tracers(self, xy):
+        """Append tracers at the positions xy, shape (n, 2) in the markers' units (euler_tracers_add): they move with the flow by the marker's rule in
+        front of every marker advection and accumulate path, age and wet time."""
+        a = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        _check(self.L.euler_tracers_add(self.h, a.ctypes.data if len(a) else None, len(a)))
+        return self
+
+    @property
+    def n_tracers(self):
+        n = C.c_size_t(0)
+        _check(self.L.euler_tracers_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def tracers(self, first=0, n=None):
+        """Records [first, first + n) (n = None: to the end) in the order they were added (euler_tracers_get): an array of TRACER_DTYPE."""
+        if n is None:
+            n = max(self.n_tracers - int(first), 0)
+        out = np.zeros(int(n), TRACER_DTYPE)
+        _check(self.L.euler_tracers_get(self.h, int(first), int(n), out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def clear_tracers(self):
+        _check(self.L.euler_tracers_clear(self.h))
+        return self
+
+    def tracer_raster(self, box, w, h, all=False):
+        """The live tracers (all=True: the retired ones too) per pixel of overview(w, h, box) (euler_tracer_raster): uint32, shape (h, w), row 0 = top.
+        box = None: the whole interior."""
+        x0, y0, x1, y1 = (1, 1, self.X - 2, self.Y - 2) if box is None else (int(t) for t in box)
+        out = np.zeros((max(int(h), 0), max(int(w), 0)), np.uint32)
+        dst = out.ctypes.data if out.size else np.zeros(1, np.uint32).ctypes.data
+        _check(self.L.euler_tracer_raster(self.h, x0, y0, x1, y1, int(w), int(h), TRACER_RASTER_ALL if all else 0, dst, out.nbytes))
+        return out
 
     def edit_box(self, op, box):
         """Edit box = (x0, y0, x1, y1), inclusive, and the markers in it on the device (euler_edit_box, docs/editing.md): op is one of EDIT_SOLID,

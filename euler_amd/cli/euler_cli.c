@@ -13,7 +13,8 @@
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
  *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
- *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... <scenario>
+ *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]...
+ *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
@@ -46,6 +47,14 @@
  * of simulated time with the phase in degrees, and (up to 64 times) an acceleration FX,FY on the live faces of the cells of the box [X0, X1] x [Y0, Y1], in
  * command-line order.  A malformed spec, a 65th box, a box outside the interior and a value out of range (beyond 1e4 in size, not finite, HZ < 0) are usage
  * errors.  Without the three the forcing is never touched.
+ * --tracer (up to 1024 times) and --tracer-box (up to 64 times; the K x K lattice of every cell of the box, K = 1, 2 or 4) place passive tracers
+ * (euler_tracers_add, docs/tracers.md), added once behind the load in command-line order.  --emit (up to 64 times) is a point that releases a tracer right before
+ * the step that produces frame F whenever F % EVERY == 0 (default 1; F = 0 counts: before frame 0 is drawn) - a streakline; the emitters of a frame go in
+ * command-line order in ONE euler_tracers_add and are silently skipped once the store is full.  --tracers writes FILE (created or truncated) as CSV: a header line, then
+ * one line per tracer after every N-th frame (--tracers-every, default 1; frame 0 included).  --tracers-show paints the pixels that hold a live tracer yellow in the
+ * frame of --fit / --view (both regimes) and the images of --ppm (euler_tracer_raster + euler_tracer_paint, behind any --paint; the other water pixels blue unless
+ * --rainbow or --paint colour them; the images are then written in the dye mode); with --view, and only with it, the key t toggles it.  A malformed spec, a 1025th
+ * tracer, a 65th box or emitter, a position or box outside the interior and --tracers-show without --fit, --view or --ppm are usage errors.
  */
 #include <errno.h>
 #include <signal.h>
@@ -60,11 +69,13 @@
 #include "euler.h"
 #include "cli_gauges.h"
 #include "cli_forcing.h"
+#include "cli_tracers.h"
+#include "euler_host.h"      /* eu_tracer_lattice */
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -120,8 +131,21 @@ static int paint_records(euler_sim* sim, const int* box, int xi, int yi, euler_o
   return rc == EULER_OK ? 0 : -1;
 }
 
+/* --tracers-show: the tracer raster of the box (NULL: the whole interior) at the records' raster, painted into their dye sums; blue_rest: the other water pixels blue */
+static int show_tracers(euler_sim* sim, const int* box, int xi, int yi, euler_overview_px* px, int W, int H, int blue_rest) {
+  static const float fg[3] = {1.f, 0.9f, 0.f}, bg[3] = {0.25f, 0.5f, 1.f};
+  const size_t n = (size_t)W * (size_t)H;
+  uint32_t* counts = (uint32_t*)malloc(n * sizeof *counts);
+  if (!counts) { fprintf(stderr, "--tracers-show: out of memory\n"); return -1; }
+  int rc = euler_tracer_raster(sim, box ? box[0] : 1, box ? box[1] : 1, box ? box[2] : xi, box ? box[3] : yi, W, H, 0, counts, n * sizeof *counts);
+  if (rc != EULER_OK) fprintf(stderr, "%s\n", euler_last_error());
+  else if ((rc = euler_tracer_paint(counts, px, W, H, fg, blue_rest ? bg : NULL)) != EULER_OK) fprintf(stderr, "--tracers-show: the painter refused\n");
+  free(counts);
+  return rc == EULER_OK ? 0 : -1;
+}
+
 /* paint < 0: unpainted; else the records are painted with that field at pscale and the image is written in the dye mode */
-static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const int* box, int xi, int yi, int W, int H, int mode, float scale, int paint, double pscale) {
+static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const int* box, int xi, int yi, int W, int H, int mode, float scale, int paint, double pscale, int show, int rainbow) {
   const size_t n = (size_t)W * (size_t)H;
   euler_overview_px* px = (euler_overview_px*)malloc(n * sizeof *px);
   uint8_t* rgb = (uint8_t*)malloc(n * 3);
@@ -133,7 +157,8 @@ static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const 
     ok = 0;
   }
   if (ok && paint >= 0 && paint_records(sim, box, xi, yi, px, W, H, paint, pscale) != 0) ok = 0;
-  if (ok && euler_overview_rgb(px, W, H, paint >= 0 ? EULER_IMAGE_DYE : mode, scale, rgb, n * 3) != EULER_OK) {
+  if (ok && show && show_tracers(sim, box, xi, yi, px, W, H, !rainbow && paint < 0) != 0) ok = 0;
+  if (ok && euler_overview_rgb(px, W, H, paint >= 0 || show ? EULER_IMAGE_DYE : mode, scale, rgb, n * 3) != EULER_OK) {
     fprintf(stderr, "%s\n", euler_last_error());
     ok = 0;
   }
@@ -180,6 +205,54 @@ static int write_gauge_lines(euler_sim* sim, FILE* out, const char* path, int fr
   return ok ? 0 : -1;
 }
 
+/* ---- --tracers: one CSV line per tracer and frame (euler_tracers_get, docs/tracers.md) ---------------- */
+static int write_tracer_lines(euler_sim* sim, FILE* out, const char* path, int frame) {
+  size_t n = 0;
+  double t = 0.0;
+  char line[256];
+  if (euler_tracers_count(sim, &n) != EULER_OK || euler_get_time(sim, &t) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); return -1; }
+  euler_tracer* rec = (euler_tracer*)malloc((n ? n : 1) * sizeof *rec);
+  if (!rec) { fprintf(stderr, "--tracers: out of memory\n"); return -1; }
+  if (euler_tracers_get(sim, 0, n, rec, n * sizeof *rec) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); free(rec); return -1; }
+  int ok = 1;
+  for (size_t k = 0; ok && k < n; ++k) {
+    const int len = format_tracer_line(line, sizeof line, frame, t, k, rec + k);
+    ok = len > 0 && (size_t)len < sizeof line && fputs(line, out) >= 0;
+  }
+  ok = ok && fflush(out) == 0;
+  if (!ok) fprintf(stderr, "--tracers: cannot write %s: %s\n", path, strerror(errno));
+  free(rec);
+  return ok ? 0 : -1;
+}
+/* --emit: the emitters due at frame f, in command-line order, in one euler_tracers_add; those the store has no room for are skipped */
+static int emit_tracers(euler_sim* sim, const cli_emitter* e, int n, int f) {
+  float xy[2 * MAX_EMITTERS];
+  size_t m = 0, have = 0;
+  if (euler_tracers_count(sim, &have) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); return -1; }
+  for (int k = 0; k < n; ++k)
+    if (f % e[k].every == 0 && have + m < EULER_TRACERS_MAX) { xy[2 * m] = e[k].x; xy[2 * m + 1] = e[k].y; ++m; }
+  if (m && euler_tracers_add(sim, xy, m) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); return -1; }
+  return 0;
+}
+/* --tracer / --tracer-box: everything placed on the command line, in its order, in one euler_tracers_add behind the load */
+static int add_seeds(euler_sim* sim, const cli_seed* s, int n) {
+  size_t total = 0;
+  for (int k = 0; k < n; ++k) total += s[k].k ? eu_tracer_lattice(s[k].box[0], s[k].box[1], s[k].box[2], s[k].box[3], s[k].k, NULL) : 1;
+  if (!total) return 0;
+  if (total > EULER_TRACERS_MAX) { fprintf(stderr, "--tracer-box: %zu tracers (at most %u)\n", total, (unsigned)EULER_TRACERS_MAX); return -1; }
+  float* xy = (float*)malloc(total * 2 * sizeof *xy);
+  if (!xy) { fprintf(stderr, "--tracer: out of memory\n"); return -1; }
+  size_t m = 0;
+  for (int k = 0; k < n; ++k) {
+    if (s[k].k) m += eu_tracer_lattice(s[k].box[0], s[k].box[1], s[k].box[2], s[k].box[3], s[k].k, xy + 2 * m);
+    else { xy[2 * m] = s[k].x; xy[2 * m + 1] = s[k].y; ++m; }
+  }
+  const int rc = euler_tracers_add(sim, xy, total);
+  if (rc != EULER_OK) fprintf(stderr, "%s\n", euler_last_error());
+  free(xy);
+  return rc == EULER_OK ? 0 : -1;
+}
+
 /* ---- the reference's loop state (main.c:85-88) ----------------------------------------------- */
 typedef struct app {
   euler_sim* sim;
@@ -192,6 +265,7 @@ typedef struct app {
   int failed;                   /* a brush key's edit was refused */
   int paint;                    /* --paint / the key v: -1 unpainted, else EULER_PAINT_* */
   double paint_scale[3];        /* the scale of each field: the one given, else 1, 1000, 10 */
+  int show;                     /* --tracers-show / the key t: the pixels that hold a live tracer are painted */
 } app_t;
 
 /* ---- --paint: the frame of --fit / --view with the flow field in place of the dye (docs/flow_raster.md) ----------------------------------- */
@@ -218,7 +292,8 @@ static char* painted_frame(app_t* a, const int* b, int view, int wx, int wy, int
   if (!ok) fprintf(stderr, "--paint: out of memory\n");
   if (ok && (euler_overview_box(a->sim, b[0], b[1], b[2], b[3], W, H, px, n * sizeof *px) != EULER_OK ||
              (scale && euler_marker_raster(a->sim, b[0], b[1], b[2], b[3], scale, ras, rbytes) != EULER_OK))) { fprintf(stderr, "%s\n", euler_last_error()); ok = 0; }
-  if (ok && paint_records(a->sim, b, a->xi, a->yi, px, W, H, a->paint, a->paint_scale[a->paint]) != 0) ok = 0;
+  if (ok && a->paint >= 0 && paint_records(a->sim, b, a->xi, a->yi, px, W, H, a->paint, a->paint_scale[a->paint]) != 0) ok = 0;
+  if (ok && a->show && show_tracers(a->sim, b, a->xi, a->yi, px, W, H, !a->rainbow && a->paint < 0) != 0) ok = 0;
   for (int pass = 0; ok && pass < 2; ++pass) {      /* the sizing protocol: the length, then the bytes */
     const int32_t cap = pass ? *len : 0;
     if (pass && !(out = (char*)malloc((size_t)cap + 1))) { fprintf(stderr, "--paint: out of memory\n"); ok = 0; break; }
@@ -270,6 +345,7 @@ static void view_key(app_t* a, char c) {
     zoom_axis(&b[1], &b[3], a->yi, 2 * bh < a->yi ? 2 * bh : a->yi);
   } else if (c == '0') { b[0] = 1; b[1] = 1; b[2] = a->xi; b[3] = a->yi; }
   else if (c == 'v') a->paint = a->paint == EULER_PAINT_SPEED ? -1 : a->paint + 1;      /* unpainted -> vorticity -> pressure -> speed -> unpainted */
+  else if (c == 't') a->show = !a->show;
   else if (c && strchr("XCSOWD", c)) {      /* the brush: the box shrunk about its centre to a quarter of its sides */
     static const int ops[6] = {EULER_EDIT_SOLID, EULER_EDIT_CLEAR, EULER_EDIT_SINK, EULER_EDIT_SOURCE, EULER_EDIT_FILL, EULER_EDIT_DRAIN};
     const int w = bw / 4 > 1 ? bw / 4 : 1, h = bh / 4 > 1 ? bh / 4 : 1;
@@ -321,6 +397,10 @@ int main(int argc, char** argv) {
   euler_force_box force_boxes[MAX_FORCE_BOXES];
   int forcing_given = 0, n_force_boxes = 0;
   euler_forcing_default(&forcing);
+  static cli_seed seeds[MAX_CLI_TRACERS + MAX_TRACER_BOXES];
+  cli_emitter emitters[MAX_EMITTERS];
+  int n_seeds = 0, n_points = 0, n_tboxes = 0, n_emitters = 0, tracers_every = 1, tracers_show = 0;
+  const char* tracers = NULL;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -392,6 +472,13 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--gravity") && i + 1 < argc) { if (parse_gravity(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--shake") && i + 1 < argc) { if (parse_shake(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--force") && i + 1 < argc) { if (n_force_boxes == MAX_FORCE_BOXES || parse_force(argv[++i], &force_boxes[n_force_boxes++]) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
+    /* passive tracers: points, lattices, emitters, the CSV and the painting (docs/tracers.md) */
+    else if (!strcmp(argv[i], "--tracer") && i + 1 < argc) { if (n_points++ == MAX_CLI_TRACERS || parse_tracer(argv[++i], &seeds[n_seeds++]) != 0) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--tracer-box") && i + 1 < argc) { if (n_tboxes++ == MAX_TRACER_BOXES || parse_tracer_box(argv[++i], &seeds[n_seeds++]) != 0) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--emit") && i + 1 < argc) { if (n_emitters == MAX_EMITTERS || parse_emit(argv[++i], &emitters[n_emitters++]) != 0) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--tracers") && i + 1 < argc) tracers = argv[++i];
+    else if (!strcmp(argv[i], "--tracers-every") && i + 1 < argc) { tracers_every = atoi(argv[++i]); if (tracers_every < 1) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--tracers-show")) tracers_show = 1;
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
@@ -414,6 +501,12 @@ int main(int argc, char** argv) {
     if (fb->x0 < 1 || fb->y0 < 1 || fb->x1 > cfg.X - 2 || fb->y1 > cfg.Y - 2 || fb->x0 > fb->x1 || fb->y0 > fb->y1) { usage(argv[0]); return 1; }
   }
   forcing.nboxes = n_force_boxes;
+  for (int k = 0; k < n_seeds; ++k) {
+    const int* tb = seeds[k].box;
+    if (seeds[k].k ? (tb[0] < 1 || tb[1] < 1 || tb[2] > cfg.X - 2 || tb[3] > cfg.Y - 2 || tb[0] > tb[2] || tb[1] > tb[3]) : !cli_tracer_inside(seeds[k].x, seeds[k].y, cfg.X, cfg.Y)) { usage(argv[0]); return 1; }
+  }
+  for (int k = 0; k < n_emitters; ++k) if (!cli_tracer_inside(emitters[k].x, emitters[k].y, cfg.X, cfg.Y)) { usage(argv[0]); return 1; }
+  if (tracers_show && !fit && !view && !ppm) { usage(argv[0]); return 1; }
   const int ppm_size_given = ppm_w > 0;
   if (ppm && view) {      /* the size follows the box frame by frame (below) */
     if (ppm_mode < 0) ppm_mode = cfg.rainbow ? EULER_IMAGE_DYE : EULER_IMAGE_COVERAGE;
@@ -446,6 +539,7 @@ int main(int argc, char** argv) {
   memcpy(app.box, vbox, sizeof vbox);
   app.paint = paint;
   memcpy(app.paint_scale, paint_scale, sizeof paint_scale);
+  app.show = tracers_show;
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
@@ -453,6 +547,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }
+  if (add_seeds(app.sim, seeds, n_seeds) != 0) return 1;
   if (interactive) {
     if (enable_raw_mode() == -1) { perror("failed to enable raw mode"); return 1; }
     write_all("\x1b[2J\x1b[H", 7);      /* clear_screen_now */
@@ -467,6 +562,11 @@ int main(int argc, char** argv) {
   if (gauges && !rc_exit) {
     gauges_file = fopen(gauges, "w");
     if (!gauges_file || fputs(k_gauges_header, gauges_file) < 0 || fflush(gauges_file) != 0) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
+  }
+  FILE* tracers_file = NULL;
+  if (tracers && !rc_exit) {
+    tracers_file = fopen(tracers, "w");
+    if (!tracers_file || fputs(k_tracers_header, tracers_file) < 0 || fflush(tracers_file) != 0) { fprintf(stderr, "--tracers: cannot write %s: %s\n", tracers, strerror(errno)); rc_exit = 1; }
   }
   int32_t cap = 0;
   char* buf = NULL;
@@ -483,6 +583,7 @@ int main(int argc, char** argv) {
       if (app.failed) { rc_exit = 1; break; }
       for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == f && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;
       if (rc_exit) break;
+      if (n_emitters && emit_tracers(app.sim, emitters, n_emitters, f) != 0) { rc_exit = 1; break; }
       if (gated_step(&app) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
       if (pace && !dump) {                  /* 10 frames per second (main.c:1036, misc/time.c:17-32) */
         next.tv_nsec += 100000000L;
@@ -495,6 +596,7 @@ int main(int argc, char** argv) {
     }
     else for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == 0 && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;      /* before frame 0 is drawn */
     if (rc_exit) break;
+    if (f == 0 && n_emitters && emit_tracers(app.sim, emitters, n_emitters, 0) != 0) { rc_exit = 1; break; }
     if (g_resized) {                        /* handle_window_size_changed (main.c:1010-1014) */
       g_resized = 0;
       if (window_size(&wx, &wy) == 0) write_all("\x1b[2J\x1b[H", 7);
@@ -503,7 +605,7 @@ int main(int argc, char** argv) {
     const int* b = app.box;
     const int whole[4] = {1, 1, app.xi, app.yi};
     char* painted = NULL;      /* --paint / the key v: the frame of --fit / --view from the painted records */
-    if (app.paint >= 0 && (fit || view) && !(painted = painted_frame(&app, view ? b : whole, view, wx, wy, &len))) { rc_exit = 1; break; }
+    if ((app.paint >= 0 || app.show) && (fit || view) && !(painted = painted_frame(&app, view ? b : whole, view, wx, wy, &len))) { rc_exit = 1; break; }
 #define RENDER(out, cap) (view ? euler_render_view(app.sim, b[0], b[1], b[2], b[3], wx, wy, (out), (cap), &len) : render(app.sim, wx, wy, (out), (cap), &len))
     if (painted) {}
     else if (RENDER(NULL, 0) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; break; }
@@ -536,13 +638,15 @@ int main(int argc, char** argv) {
         while (bw / d > 1024 || bh / d > 1024) ++d;
         w = bw / d > 1 ? bw / d : 1; h = bh / d > 1 ? bh / d : 1;
       }
-      if (write_ppm_frame(app.sim, ppm, f, b, app.xi, app.yi, w, h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
-    } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, app.xi, app.yi, ppm_w, ppm_h, ppm_mode, ppm_scale, pf, ps) != 0) { rc_exit = 1; break; }
+      if (write_ppm_frame(app.sim, ppm, f, b, app.xi, app.yi, w, h, ppm_mode, ppm_scale, pf, ps, app.show, app.rainbow) != 0) { rc_exit = 1; break; }
+    } else if (ppm && f % ppm_every == 0 && write_ppm_frame(app.sim, ppm, f, NULL, app.xi, app.yi, ppm_w, ppm_h, ppm_mode, ppm_scale, pf, ps, app.show, app.rainbow) != 0) { rc_exit = 1; break; }
     if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
     if (gauges_file && f % gauges_every == 0 && write_gauge_lines(app.sim, gauges_file, gauges, f, gauge_list, n_gauges) != 0) { rc_exit = 1; break; }
+    if (tracers_file && f % tracers_every == 0 && write_tracer_lines(app.sim, tracers_file, tracers, f) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }
   if (stats_file && fclose(stats_file) != 0 && !rc_exit) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
+  if (tracers_file && fclose(tracers_file) != 0 && !rc_exit) { fprintf(stderr, "--tracers: cannot write %s: %s\n", tracers, strerror(errno)); rc_exit = 1; }
   if (gauges_file && fclose(gauges_file) != 0 && !rc_exit) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }
   euler_stats st;

@@ -275,7 +275,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   eu_rccl_release(S);
   eu_slab_release(S);
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf}) eu_devbuf_release(S, b);
+  for (eu_devbuf* b : {&S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf}) eu_devbuf_release(S, b);
   // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
   // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
   const size_t wo = S->shifted ? S->win_off : 0;
@@ -609,6 +609,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   if (rc) return rc;
   memset(&S->stats, 0, sizeof(S->stats));
   S->time = 0.0;      // (the forcing stays as set: docs/forcing.md)
+  S->n_tracers = 0;   // (the tracers belonged to the run that was replaced: docs/tracers.md)
   S->loaded = 1;
   return EULER_OK;
 }
@@ -769,7 +770,10 @@ extern "C" int euler_timestep(euler_sim* S, float frame_time_left, float* dt) {
 static int run_stage(euler_sim* S, int stage, float dt) {
   eu_vd_stage_begin(&S->vd, stage);      // (each launcher reports what it ran: eu_valid.h)
   switch (stage) {
-    case EULER_STAGE_ADVECT_MARKERS: return eu_launch_advect_markers(S, dt);
+    case EULER_STAGE_ADVECT_MARKERS: {   // the passive tracers first: they read u, v and the masks as the markers are about to (docs/tracers.md)
+      int rc = eu_launch_advect_tracers(S, dt);
+      return rc ? rc : eu_launch_advect_markers(S, dt);
+    }
     case EULER_STAGE_REFRESH_COUNTS: return eu_launch_refresh_counts(S);
     case EULER_STAGE_SOURCES: {   // with the dye: extrapolate(g_r/g/b, P) comes first (main.c:859-864)
       int rc = eu_launch_dye_extrapolate(S);

@@ -164,6 +164,10 @@ struct euler_sim {
   unsigned int force_ntiles;
   double time;            // simulated time: 0 after a load, += (double)dt behind every substep
   eu_devbuf force_buf;
+  // passive tracers (k_tracers.hip, docs/tracers.md): the store of 32-byte euler_tracer records - n_tracers of them live, the capacity is the buffer's -
+  // and the raster of euler_tracer_raster
+  eu_devbuf tracer_buf, tracer_ras_buf;
+  size_t n_tracers;
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -373,6 +377,7 @@ static inline bool eu_tile_map_on(const euler_sim* S) { return eu_vd_tile_map(&S
 // launch groups implemented in the kernel files
 int eu_launch_timestep(euler_sim* S, float frame_time_left);
 int eu_launch_advect_markers(euler_sim* S, float dt);
+int eu_launch_advect_tracers(euler_sim* S, float dt);   // k_tracers.hip: the passive tracers' one launch, in front of the marker launches of the stage (a no-op without tracers)
 int eu_launch_refresh_counts(euler_sim* S);
 int eu_launch_sources(euler_sim* S);
 int eu_launch_extrapolate(euler_sim* S);

@@ -552,3 +552,47 @@ int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_val
   out->depth = (double)rec->hi_y - (double)rec->lo_y + 1.0;
   return EULER_OK;
 }
+
+/* ---- passive tracers: the checks of euler_tracers_add that need no device, the lattice of a box, the painter (include/euler.h, docs/tracers.md) ---- */
+
+int eu_tracers_check(const float* xy, size_t n, size_t count, int32_t X, int32_t Y, char* why, size_t cap) {
+#define REFUSE(...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return EULER_EINVAL; } while (0)
+  if (n > 0 && !xy) REFUSE("%zu tracers and a null list", n);
+  if (count > EULER_TRACERS_MAX || n > EULER_TRACERS_MAX - count) REFUSE("%zu + %zu tracers (at most %u)", count, n, (unsigned)EULER_TRACERS_MAX);
+  const float xl = (float)(X - 1), yl = (float)(Y - 1);
+  for (size_t k = 0; k < n; ++k) {
+    const float x = xy[2 * k], y = xy[2 * k + 1];
+    if (!(x >= 1.f && x < xl && y >= 1.f && y < yl))      /* (a NaN fails every comparison, an infinity one of them) */
+      REFUSE("tracer %zu: (%g, %g) is not a finite position inside [1, %d) x [1, %d)", k, (double)x, (double)y, X - 1, Y - 1);
+  }
+#undef REFUSE
+  return EULER_OK;
+}
+
+size_t eu_tracer_lattice(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t K, float* xy) {
+  if ((K != 1 && K != 2 && K != 4) || x0 > x1 || y0 > y1) return 0;
+  const size_t n = (size_t)(x1 - x0 + 1) * (size_t)(y1 - y0 + 1) * (size_t)(K * K);
+  if (!xy) return n;
+  size_t m = 0;
+  for (int32_t x = x0; x <= x1; ++x)
+    for (int32_t y = y0; y <= y1; ++y)
+      for (int32_t i = 0; i < K; ++i)
+        for (int32_t j = 0; j < K; ++j) {
+          xy[2 * m] = (float)x + ((float)i + 0.5f) / (float)K;
+          xy[2 * m + 1] = (float)y + ((float)j + 0.5f) / (float)K;
+          ++m;
+        }
+  return n;
+}
+
+int euler_tracer_paint(const uint32_t* counts, euler_overview_px* px, int32_t W, int32_t H, const float fg[3], const float* bg) {
+  if (!counts || !px || !fg || W < 1 || H < 1) return EULER_EINVAL;
+  const size_t n = (size_t)W * (size_t)H;
+  for (size_t k = 0; k < n; ++k) {
+    if (!px[k].water) continue;      /* a tracer shows only on water pixels */
+    const float* col = counts[k] > 0 ? fg : bg;
+    if (!col) continue;
+    for (int c = 0; c < 3; ++c) px[k].dye[c] = (uint64_t)px[k].water * paint_q24(col[c]);
+  }
+  return EULER_OK;
+}

@@ -416,6 +416,7 @@ extern "C" int euler_load_state(euler_sim* S, const char* path) {
   memset(&S->stats, 0, sizeof S->stats);
   S->stats.frames = h0.frames; S->stats.total_substeps = h0.total_substeps; S->stats.total_pcg_iterations = h0.total_pcg_iterations;
   S->time = 0.0;      // (the clock is no part of a snapshot and the forcing stays as set: the caller restores both, docs/forcing.md)
+  S->n_tracers = 0;   // (tracers are no part of a snapshot either: docs/tracers.md)
   S->loaded = 1;
   return EULER_OK;
 }

@@ -576,6 +576,62 @@ int euler_forcing_at(const euler_forcing* f, double t, float a[2]);   /* host on
 int euler_get_time(euler_sim* sim, double* t);
 int euler_set_time(euler_sim* sim, double t);   /* EULER_EINVAL: a non-finite t */
 
+/* ---- passive tracers: device-side pathlines, streaklines and a raster (docs/tracers.md) ------------ */
+/* Where does this water go, how long does it stay, does it ever reach that corner?  A set of TRACERS lives on the device and moves with the flow by the
+ * marker's own rule; the fluid's markers cannot answer (their array order changes with every deletion, their dt is shortened by earlier markers'
+ * collisions: they are state, not instruments).  Whenever EULER_STAGE_ADVECT_MARKERS runs on a whole-grid handle with tracers - euler_step, euler_substep,
+ * euler_stage - ONE extra launch (profile class marker_advect), issued on the handle's stream BEFORE the marker launches of that stage, advects all of them.
+ * It reads the row-major u, v, count, solid and sink as they stand at that moment and the stage's dt, follows EULER_OPT_ADVECT_RK2 as the markers do, and
+ * touches no other state: a handle with tracers produces the fields, markers and RNG state of one without, and a handle that never adds one launches
+ * exactly what it launched before.  One tracer, one substep, float32 without contraction:
+ *   1. RETIRED set: nothing changes.
+ *   2. cx = (int)floorf(x), cy = (int)floorf(y); x or y not finite, cx outside [0, X-1] or cy outside [0, Y-1]: flags |= RETIRED | LOST, stop (before any grid read).
+ *   3. solid[cy*X+cx]: flags |= RETIRED | IN_SOLID, stop; else sink[..]: flags |= RETIRED | IN_SINK, stop.  The position stays.
+ *   4. wet = count[..] != 0; (x', y') = the walk of ONE marker through the substep (main.c:464-537 for an array of one marker) with the stage's full dt:
+ *      a tracer never sees the dt an earlier marker's collision shortened and never shortens anyone's.
+ *   5. path += sqrtf(dx*dx + dy*dy), dx = x' - x, dy = y' - y (sqrtf correctly rounded); age += dt; wet_time += dt only if wet; ++substeps.
+ *   6. WET becomes wet; WAS_DRY is set for good if !wet; x, y = x', y'.
+ * A tracer in air does not move (the masked velocity there is 0).  Scenario loads, the half-tank loaders and euler_load_state clear the tracers;
+ * euler_set_field, euler_set_markers, euler_edit_box, euler_set_forcing and euler_set_time leave them alone (a wall raised over a tracer retires it on
+ * its next substep).  Tracers are not part of a snapshot.  Whole-grid handles only. */
+#define EULER_TRACERS_MAX (1u << 22)
+enum { EULER_TRACER_WET = 1, EULER_TRACER_RETIRED = 2, EULER_TRACER_IN_SOLID = 4, EULER_TRACER_IN_SINK = 8,
+       EULER_TRACER_LOST = 16, EULER_TRACER_WAS_DRY = 32 };
+typedef struct euler_tracer {   /* 32 bytes, no padding */
+  float    x, y;        /* position in the markers' units (k_side_length = 1: cell (floorf(x), floorf(y))) */
+  float    path;        /* sum over its substeps of sqrtf(dx*dx + dy*dy), dx = x' - x, dy = y' - y */
+  float    age;         /* sum of the dt of its substeps */
+  float    wet_time;    /* sum of the dt of the substeps it began in a cell with count > 0 */
+  uint32_t substeps;    /* substeps it was advected in */
+  uint32_t flags;       /* EULER_TRACER_* */
+  uint32_t reserved;    /* 0 */
+} euler_tracer;
+/* Appends n tracers at (xy[2k], xy[2k+1]), all other words 0: one host-to-device copy.  Refusals, in this order: a null handle (EULER_EINVAL); a row-slab
+ * handle (EULER_ESTATE); nothing loaded (EULER_ESTATE); n > 0 with a null xy; count + n > EULER_TRACERS_MAX; a position that is not finite or outside
+ * 1 <= x < X - 1, 1 <= y < Y - 1, naming the first such index (all EULER_EINVAL).  A refused call changes and allocates nothing; n == 0 is a no-op.  A
+ * position inside a solid or sink cell is accepted and retires on its first substep.  The store is one device buffer of the handle, counted in
+ * euler_hbm_bytes, doubled on demand (the records keep their bits; EULER_ENOMEM: the handle unchanged) and released by euler_destroy. */
+int euler_tracers_add(euler_sim* sim, const float* xy, size_t n);
+int euler_tracers_count(euler_sim* sim, size_t* n);
+/* Records [first, first + n) in the order they were added: one copy and one wait.  EULER_EINVAL: first + n > count, out_bytes != n * 32; n == 0 succeeds. */
+int euler_tracers_get(euler_sim* sim, size_t first, size_t n, euler_tracer* out, size_t out_bytes);
+int euler_tracers_clear(euler_sim* sim);   /* count = 0; the buffer stays */
+/* The tracers per pixel: the box, W, H and the pixel geometry of euler_overview_box; out_bytes exactly W * H * 4 and no flag bit but
+ * EULER_TRACER_RASTER_ALL: else EULER_EINVAL.  out[py * W + px] is the number of tracers whose cell (floorf(x), floorf(y)) lies in the box and is covered
+ * by pixel (px, py); retired tracers count only with EULER_TRACER_RASTER_ALL; a tracer with a non-finite coordinate counts nowhere.  The pixel of a cell is
+ * formed in integers (column c = cx - x0 of the box: px = ((c + 1) * W - 1) / Bw; row r = y1 - cy from the top: py = ((r + 1) * H - 1) / Bh) and the
+ * counts are integer adds: they do not depend on the launch geometry (tests compare them exactly).  One pass over the records behind a clear of the
+ * raster; it reads only.  Without tracers: a raster of zeros.  EULER_ESTATE without a loaded state and on a row-slab handle. */
+enum { EULER_TRACER_RASTER_ALL = 1 };   /* also count retired tracers */
+int euler_tracer_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H,
+                        int32_t flags, uint32_t* out, size_t out_bytes);
+/* Host only, no GPU: paints a tracer raster into the dye sums of overview records of the same box and raster, as euler_flow_paint does.  Where
+ * counts[k] > 0 && px[k].water > 0: dye[c] = water * q(fg[c]) with the q of euler_overview_px; where bg is not NULL, counts[k] == 0 and water > 0:
+ * dye[c] = water * q(bg[c]); everything else stays (a tracer shows only on water pixels).  Only px[k].dye is written.  EULER_EINVAL with px unchanged:
+ * a null counts, px or fg, W < 1 or H < 1. */
+int euler_tracer_paint(const uint32_t* counts, euler_overview_px* px, int32_t W, int32_t H,
+                       const float fg[3], const float* bg /* 3 floats or NULL */);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
