@@ -275,7 +275,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   eu_rccl_release(S);
   eu_slab_release(S);
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf}) eu_devbuf_release(S, b);
+  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf}) eu_devbuf_release(S, b);
   // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
   // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
   const size_t wo = S->shifted ? S->win_off : 0;

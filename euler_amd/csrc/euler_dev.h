@@ -154,6 +154,7 @@ struct euler_sim {
   uint8_t* blockedT;       // sink | solid per cell, COLUMN-major like count32 (whole-grid handles; k_bin_markers); rebuilt when eu_vd_blocked_due
   float *uT, *vT; uint8_t *countT, *solidT;   // COLUMN-major copies of u, v (made in front of every marker advection), per cell the typed fluid properties of an interpolation's four corners (countT: k_transpose_for_markers) and of the solid grid (when eu_vd_solidT_due): whole-grid handles only
   float* dye[6];          // --rainbow only (cfg.rainbow): g_r, g_g, g_b, g_rtmp, g_gtmp, g_btmp (main.c:76-81)
+  eu_devbuf obs_stage_buf;   // row slabs: the ranks' partial records of an observer pass, rank after rank (k_observe_slab.hip): what the all-gather fills and the fold reads
   eu_devbuf ov_buf, diag_buf, vr_buf, flow_buf, gauge_buf;   // the observer passes' results on the device (k_observe.hip): euler_overview's records, euler_diagnostics' record, euler_marker_raster's
                           // raster, euler_flow_raster's records, euler_gauges' records and chunk table; each allocated by its pass's first call and grown on demand
   // euler_set_forcing (docs/forcing.md): the record and the boxes as set, whether the uniform part differs from the reference's (0, EU_G) - only then do the forced
@@ -398,10 +399,24 @@ int eu_ordered_select(euler_sim* S, const unsigned long long* mask, size_t nword
 int eu_sync_marker_state(euler_sim* S);
 int eu_marker_compact(euler_sim* S, const unsigned long long* delmask);   // k_markers.hip: swap-with-last removal of the selected deletions (S->sel_idx, ms->n_deleted); ms->n is the caller's to lower
 // the host side of a read-only observer pass (k_observe.hip, docs/observer_passes.md): enter, reserve, launch, read back
+// slab_reason: why this pass refuses a row-slab handle; null: it runs there (collective) and refuses only a slab handle without a communicator
 int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reason, const void* out, int x0, int y0, int x1, int y1);   // null argument, row-slab handle, nothing loaded, box inside the interior
 int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes);   // grow-only; a failure leaves the handle as it was
 void eu_devbuf_release(euler_sim* S, eu_devbuf* b);
 int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t bytes);   // copy to the caller and wait for it
+// the passes on a row-slab handle (k_observe_slab.hip, docs/observer_passes.md "On row slabs"): every rank reduces the rows of the box it owns into its share of the staging
+// area, the shares are all-gathered as bytes and folded on the device into the pass's own buffer - integer sums and extremes: the whole-grid record bit for bit
+enum { EU_OBS_REC_OVERVIEW = 0, EU_OBS_REC_FLOW, EU_OBS_REC_DIAG, EU_OBS_REC_GAUGE, EU_OBS_REC__COUNT };   // the record types the fold knows
+enum { EU_OBS_ROWS_NONE = 0, EU_OBS_ROWS_CELLS, EU_OBS_ROWS_FLOW, EU_OBS_ROWS_GAUGES };   // the ghost rows a pass reads (k_slab.hip eu_slab_exchange_observed)
+int eu_slab_exchange_observed(euler_sim* S, int rows);   // k_slab.hip: one grouped exchange of those rows
+size_t eu_observe_rec_bytes(int type);
+int eu_observe_slab_plan(const euler_sim* S, eu_slab_plan* P, int y0, int y1, int W, int H);   // the raster plan from the partition the communicator install agreed on
+// collective, behind the argument checks: local_rc (the pass's eu_devbuf_reserve) and the staging area's own reservation become every rank's status; then the ghost rows
+int eu_observe_slab_open(euler_sim* S, const char* who, int local_rc, size_t stage_bytes, int rows);
+static inline char* eu_observe_slab_mine(const euler_sim* S, const eu_slab_plan* P, int type) { return (char*)S->obs_stage_buf.p + (size_t)P->off[S->cfg.slab_rank] * eu_observe_rec_bytes(type); }   // this rank's share
+int eu_observe_slab_clear_mine(euler_sim* S, const eu_slab_plan* P, int type);   // zeros in this rank's share (the clipped kernels add into it)
+int eu_observe_slab_fold(euler_sim* S, const eu_slab_plan* P, int type, void* dst);   // the all-gather and the fold into dst: P->W x P->H records
+int eu_observe_slab_gather_in_place(euler_sim* S, void* base, const int64_t* off, const int64_t* cnt);   // disjoint byte ranges of one buffer (the marker raster): no fold
 // k_overview.hip: euler_overview_box behind eu_observe_enter (euler_render_view, which has entered already)
 int eu_overview_entered(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes);
 void eu_rccl_release(euler_sim* S);   // comm_rccl.hip

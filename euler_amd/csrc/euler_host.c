@@ -465,20 +465,81 @@ int eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const 
   return -1;
 }
 
-size_t eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out) {
+size_t eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out) { return eu_gauge_chunks_bands(g, n, 0, INT32_MAX, out); }
+
+size_t eu_gauge_chunks_bands(const euler_gauge* g, int32_t n, int32_t band_lo, int32_t band_hi, eu_gauge_chunk* out) {
   size_t m = 0;
   for (int32_t k = 0; k < n; ++k) {
-    const int32_t tx0 = g[k].x0 >> 6, tx1 = g[k].x1 >> 6, ty0 = g[k].y0 >> 6, ty1 = g[k].y1 >> 6;
+    const int32_t tx0 = g[k].x0 >> 6, tx1 = g[k].x1 >> 6, by0 = g[k].y0 >> 6, by1 = g[k].y1 >> 6;
+    const int32_t ty0 = by0 > band_lo ? by0 : band_lo, ty1 = by1 < band_hi - 1 ? by1 : band_hi - 1;      /* the tile rows of the box inside the bands */
+    if (ty0 > ty1) continue;
     if (!out) { m += (size_t)(tx1 - tx0 + 1) * (size_t)(ty1 - ty0 + 1); continue; }
     for (int32_t ty = ty0; ty <= ty1; ++ty)
       for (int32_t tx = tx0; tx <= tx1; ++tx) {      /* the tile clipped to the box */
         eu_gauge_chunk* c = out + m++;
         c->gauge = k; c->kind = g[k].kind;
         c->x0 = tx == tx0 ? g[k].x0 : tx << 6; c->x1 = tx == tx1 ? g[k].x1 : (tx << 6) + 63;
-        c->y0 = ty == ty0 ? g[k].y0 : ty << 6; c->y1 = ty == ty1 ? g[k].y1 : (ty << 6) + 63;
+        c->y0 = ty == by0 ? g[k].y0 : ty << 6; c->y1 = ty == by1 ? g[k].y1 : (ty << 6) + 63;
       }
   }
   return m;
+}
+
+/* ---- the observer passes on row slabs: what every rank works out alike from the band ranges (euler_host.h, docs/observer_passes.md "On row slabs") ---- */
+
+int eu_slab_clip_rows(int32_t band_lo, int32_t band_hi, int32_t Y, int32_t y0, int32_t y1, int32_t* ya, int32_t* yb) {
+  const int64_t lo = (int64_t)band_lo * 64, hi = (int64_t)band_hi * 64 < Y ? (int64_t)band_hi * 64 : Y;      /* the rank's rows [lo, hi) */
+  *ya = (int32_t)(y0 > lo ? y0 : lo);
+  *yb = (int32_t)(y1 < hi - 1 ? y1 : hi - 1);
+  if (*ya <= *yb) return 1;
+  *ya = 0; *yb = -1;
+  return 0;
+}
+
+static void slab_plan_offsets(eu_slab_plan* P) {
+  int64_t at = 0;
+  for (int32_t r = 0; r < P->nranks; ++r) {
+    P->cnt[r] = P->p_lo[r] <= P->p_hi[r] ? (int64_t)(P->p_hi[r] - P->p_lo[r] + 1) * P->W : 0;
+    P->off[r] = at;
+    at += P->cnt[r];
+  }
+  P->total = at;
+}
+
+int eu_slab_plan_raster(eu_slab_plan* P, int32_t nranks, const int32_t* band_lo, const int32_t* band_hi, int32_t Y, int32_t y0, int32_t y1, int32_t W, int32_t H) {
+  if (!P || !band_lo || !band_hi || nranks < 1 || nranks > EU_SLAB_PLAN_MAXR || Y < 1 || y0 < 0 || y1 >= Y || y0 > y1 || W < 1 || H < 1 || H > y1 - y0 + 1) return EULER_EINVAL;
+  for (int32_t r = 0; r < nranks; ++r)
+    if (band_lo[r] < 0 || band_hi[r] < band_lo[r] || band_hi[r] > (Y + 63) / 64 || (r > 0 && band_lo[r] < band_hi[r - 1])) return EULER_EINVAL;
+  memset(P, 0, sizeof *P);
+  P->nranks = nranks; P->W = W; P->H = H; P->y0 = y0; P->y1 = y1;
+  const int64_t Bh = (int64_t)y1 - y0 + 1;
+  for (int32_t r = 0; r < nranks; ++r) {
+    P->p_lo[r] = 0; P->p_hi[r] = -1;
+    if (!eu_slab_clip_rows(band_lo[r], band_hi[r], Y, y0, y1, &P->ya[r], &P->yb[r])) continue;
+    P->p_lo[r] = (int32_t)((((int64_t)y1 - P->yb[r] + 1) * H - 1) / Bh);      /* the pixel row of the rank's top row ... */
+    P->p_hi[r] = (int32_t)((((int64_t)y1 - P->ya[r] + 1) * H - 1) / Bh);      /* ... and of its bottom row */
+  }
+  slab_plan_offsets(P);
+  return EULER_OK;
+}
+
+int eu_slab_plan_flat(eu_slab_plan* P, int32_t nranks, int32_t n) {
+  if (!P || nranks < 1 || nranks > EU_SLAB_PLAN_MAXR || n < 1) return EULER_EINVAL;
+  memset(P, 0, sizeof *P);
+  P->nranks = nranks; P->W = n; P->H = 1;
+  for (int32_t r = 0; r < nranks; ++r) { P->ya[r] = 0; P->yb[r] = -1; P->p_lo[r] = P->p_hi[r] = 0; }
+  slab_plan_offsets(P);
+  return EULER_OK;
+}
+
+void eu_slab_plan_bytes(const eu_slab_plan* P, int64_t rec_bytes, int64_t* off, int64_t* cnt) {
+  for (int32_t r = 0; r < P->nranks; ++r) { off[r] = P->off[r] * rec_bytes; cnt[r] = P->cnt[r] * rec_bytes; }
+}
+
+int eu_slab_plan_contributors(const eu_slab_plan* P, int32_t py, int32_t* first, int32_t* last) {
+  if (!P || !first || !last || py < 0 || py >= P->H) return EULER_EINVAL;
+  eu_slab_row_ranks(P, py, first, last);
+  return EULER_OK;
 }
 
 /* ---- forcing: the record's defaults and its uniform part, the list checked and cut into the tile table (include/euler.h, docs/forcing.md) ---- */

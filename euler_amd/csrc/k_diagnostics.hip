@@ -120,16 +120,18 @@ static_assert(offsetof(euler_diag, fluid) == 8 && offsetof(euler_diag, ke_lo) ==
               "k_diagnostics addresses the record by these offsets");
 
 // the reduction alone, on the handle's stream, into the record of S->diag_buf (tools/diagnostics_cost.py times it through the KC_MISC class)
-static int dg_launch(euler_sim* S, int x0, int y0, int x1, int y1) {
+// (row slabs: the box is the rank's rows of the caller's box and `out` the rank's record in the staging area - the kernel needs no clip of its own: cells, mass_y and
+// the segments all follow the box it is given)
+static int dg_launch(euler_sim* S, int x0, int y0, int x1, int y1, euler_diag* out) {
   const bool vec = S->X % 4 == 0;
   DgArgs a;
   a.solid = S->solid; a.count = S->count; a.u = S->u; a.v = S->v;
   a.tiles = eu_observe_tiles(S);
-  a.X = S->X; a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1; a.out = (euler_diag*)S->diag_buf.p;
+  a.X = S->X; a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1; a.out = out;
   const int xbase = ob_xbase(vec ? 4 : 1, x0), span = DG_T * (vec ? 4 : 1);
   a.ncol = (x1 - xbase + span) / span;
   const int nseg = y1 / DG_ROWS - y0 / DG_ROWS + 1;
-  HIPCHK(hipMemsetAsync(S->diag_buf.p, 0, sizeof(euler_diag), S->stream));
+  HIPCHK(hipMemsetAsync(out, 0, sizeof(euler_diag), S->stream));
   const dim3 grid((unsigned)((long long)a.ncol * nseg));      // (a workgroup per 256 x 32 cells at the least: far below 2^31 on any grid euler_create accepts)
   if (vec) LAUNCH(S, KC_MISC, (k_diagnostics<4>), grid, dim3(DG_T), a);
   else LAUNCH(S, KC_MISC, (k_diagnostics<1>), grid, dim3(DG_T), a);
@@ -138,10 +140,19 @@ static int dg_launch(euler_sim* S, int x0, int y0, int x1, int y1) {
 }
 
 extern "C" int euler_diagnostics(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, euler_diag* out, size_t out_bytes) {
-  int rc = eu_observe_enter(S, "euler_diagnostics", "the record of a box is the sum over the slabs it crosses", out, x0, y0, x1, y1);
+  int rc = eu_observe_enter(S, "euler_diagnostics", nullptr, out, x0, y0, x1, y1);
   if (rc) return rc;
   if (out_bytes != sizeof(euler_diag)) { eu_set_error("euler_diagnostics: %zu bytes given, %zu expected", out_bytes, sizeof(euler_diag)); return EULER_EINVAL; }
   rc = eu_devbuf_reserve(S, "euler_diagnostics", "the record", &S->diag_buf, sizeof(euler_diag));
-  if (!rc) rc = dg_launch(S, x0, y0, x1, y1);
+  if (S->slab_on) {      // collective: every rank's record of its own rows of the box (zeros where it has none), gathered and folded into the record on every rank
+    eu_slab_plan plan;
+    int ya, yb;
+    const int mine = eu_slab_clip_rows(S->band_lo, S->band_hi, S->Y, y0, y1, &ya, &yb);
+    if (eu_slab_plan_flat(&plan, S->cfg.slab_nranks, 1)) { eu_set_error("euler_diagnostics: %d ranks", S->cfg.slab_nranks); return EULER_EINVAL; }
+    rc = eu_observe_slab_open(S, "euler_diagnostics", rc, (size_t)plan.total * sizeof(euler_diag), EU_OBS_ROWS_CELLS);
+    if (!rc) rc = mine ? dg_launch(S, x0, ya, x1, yb, (euler_diag*)eu_observe_slab_mine(S, &plan, EU_OBS_REC_DIAG)) : eu_observe_slab_clear_mine(S, &plan, EU_OBS_REC_DIAG);
+    if (!rc) rc = eu_observe_slab_fold(S, &plan, EU_OBS_REC_DIAG, S->diag_buf.p);
+  } else
+  if (!rc) rc = dg_launch(S, x0, y0, x1, y1, (euler_diag*)S->diag_buf.p);
   return rc ? rc : eu_observe_readback(S, out, &S->diag_buf, sizeof(euler_diag));
 }

@@ -34,6 +34,7 @@ struct FlArgs {
   ObTiles tiles;
   int X, W, H, npc, nsplit;
   int bx0, by1, Bw, Bh;     // the box: its left column, its top row, its extent in cells
+  int py0, cy0, cy1, add;   // row slabs (k_overview.hip OvArgs): the first pixel row launched, the rows of the box this rank owns, "out is zeroed: add"
   euler_flow_px* out;
 };
 
@@ -95,11 +96,13 @@ __global__ __launch_bounds__(FL_T) void k_flow(const FlArgs a) {
   const unsigned int Xi = (unsigned int)a.Bw, Yi = (unsigned int)a.Bh;
   const unsigned int groups = (unsigned int)((a.W + a.npc - 1) / a.npc), slice = blockIdx.x / groups;      // (neighbouring workgroups lie along a row)
   const int p0 = (int)(blockIdx.x % groups) * a.npc, p1 = p0 + a.npc < a.W ? p0 + a.npc : a.W;      // this workgroup's pixel columns [p0, p1)
-  const int py = (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
+  const int py = a.py0 + (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
   const int xa = a.bx0 + (int)((unsigned long long)p0 * Xi / (unsigned int)a.W), xb = a.bx0 - 1 + (int)((unsigned long long)p1 * Xi / (unsigned int)a.W);      // its columns [xa, xb]
   const int ytop = a.by1 - (int)((unsigned long long)py * Yi / (unsigned int)a.H), ybot = a.by1 + 1 - (int)((unsigned long long)(py + 1) * Yi / (unsigned int)a.H);
   const int nrows = ytop - ybot + 1;
-  const int yhi = ytop - (int)((long long)sp * nrows / a.nsplit), ylo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows yhi down to ylo
+  const int shi = ytop - (int)((long long)sp * nrows / a.nsplit), slo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows shi down to slo ...
+  const int yhi = shi < a.cy1 ? shi : a.cy1, ylo = slo > a.cy0 ? slo : a.cy0;      // ... of which this rank owns yhi down to ylo (a whole-grid handle: all)
+  if (yhi < ylo) return;      // (the whole workgroup: nothing of the slice is here)
   for (int k = tid; k < FL_NPC; k += FL_T) {
     for (int f = 0; f < 5; ++f) tab.w[f][k] = 0u;
     for (int f = 0; f < 6; ++f) tab.s[f][k] = 0ull;
@@ -207,15 +210,15 @@ __global__ __launch_bounds__(FL_T) void k_flow(const FlArgs a) {
     const int p = p0 + k;
     const unsigned int wpx = (unsigned int)((unsigned long long)(p + 1) * Xi / (unsigned int)a.W) - (unsigned int)((unsigned long long)p * Xi / (unsigned int)a.W);
     const unsigned int cells = wpx * (unsigned int)(yhi - ylo + 1);
-    euler_flow_px* o = a.out + (size_t)py * a.W + p;
-    if (a.nsplit == 1) {
+    euler_flow_px* o = a.out + (size_t)(py - a.py0) * a.W + p;
+    if (!a.add) {
       euler_flow_px r;
       r.cells = cells; r.water = tab.w[0][k]; r.nodes = tab.w[1][k]; r.nonfinite = tab.w[2][k];
       r.u_pos = tab.s[0][k]; r.u_neg = tab.s[1][k]; r.v_pos = tab.s[2][k]; r.v_neg = tab.s[3][k]; r.w_pos = tab.s[4][k]; r.w_neg = tab.s[5][k];
       r.p_sum = 0ull;
       r.max_speed2 = __uint_as_float(tab.w[3][k]); r.max_abs_w = __uint_as_float(tab.w[4][k]); r.max_p = 0.f; r.reserved = 0u;
       *o = r;
-    } else {      // a slice of the box's rows: added to the record the host zeroed (integers and maxima: exact in any order)
+    } else {      // a slice of the box's rows, or a rank's share of them: added to the record the host zeroed (integers and maxima: exact in any order)
       if (cells) atomicAdd(&o->cells, cells);
       if (tab.w[0][k]) {
         atomicAdd(&o->water, tab.w[0][k]);
@@ -244,7 +247,8 @@ struct FpArgs {
   const float *u, *v;
   int W, H;
   int bx0, by0, bx1, by1, Bw, Bh;     // the box, inclusive, and its extent
-  int band0, nbands, runs, tbase;     // the bands the box crosses; runs of FP_RUN pair-records per band, from record tbase (even) on
+  int band0, nbands, runs, tbase;     // the bands the box crosses (row slabs: of this rank's); runs of FP_RUN pair-records per band, from record tbase (even) on
+  int py0;                            // row slabs: the pixel row out starts at (0 on a whole-grid handle)
   euler_flow_px* out;
 };
 
@@ -274,7 +278,7 @@ __global__ __launch_bounds__(256) void k_flow_pressure(const FpArgs a) {
   const int y = band * 64 + l;
   if (y < a.by0 || y > a.by1) return;
   const int py = (int)(((unsigned long long)(a.by1 - y + 1) * (unsigned int)a.H - 1ull) / (unsigned int)a.Bh);      // the pixel row whose range holds y
-  euler_flow_px* orow = a.out + (size_t)py * a.W;
+  euler_flow_px* orow = a.out + (size_t)(py - a.py0) * a.W;
   const int t0 = a.tbase + run * 2 * FP_RUN;
   const double* base = a.p + ((size_t)band * a.g.TS + (size_t)t0) * 64 + 2 * l;      // (skew_index of record t0, lane l)
   const size_t rowi = (size_t)y * (size_t)a.g.X;
@@ -301,7 +305,8 @@ __global__ __launch_bounds__(256) void k_flow_pressure(const FpArgs a) {
 }
 
 // the velocity part alone, on the handle's stream, into the records of S->flow_buf (tools/flow_cost.py times it through the KC_MISC class)
-static int fl_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H) {
+// plan: row slabs - the records go to this rank's share of the staging area, the pixel rows its rows touch only
+static int fl_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H, const eu_slab_plan* plan = nullptr) {
   const int Xi = x1 - x0 + 1, Yi = y1 - y0 + 1;      // (the box's extent: npc and nsplit follow it)
   FlArgs a;
   a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
@@ -313,8 +318,17 @@ static int fl_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H)
   const long long span = ((long long)a.npc * Xi + W - 1) / W, rows_max = (Yi + H - 1) / H, rows_min = Yi / H;
   long long ns = (span * rows_max + FL_WG_CELLS - 1) / FL_WG_CELLS;      // slices of a box's rows
   a.nsplit = (int)(ns < 1 ? 1 : (ns > rows_min ? rows_min : ns));
-  if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->flow_buf.p, 0, (size_t)W * H * sizeof(euler_flow_px), S->stream));
-  const long long nwg = (long long)((W + a.npc - 1) / a.npc) * H * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
+  a.py0 = 0; a.cy0 = y0; a.cy1 = y1; a.add = a.nsplit > 1;
+  int Hl = H;      // pixel rows launched
+  if (plan) {
+    const int r = S->cfg.slab_rank;
+    int rc = eu_observe_slab_clear_mine(S, plan, EU_OBS_REC_FLOW);
+    if (rc || plan->cnt[r] == 0) return rc;      // (no row of the box is here: nothing to launch, nothing to contribute)
+    a.out = (euler_flow_px*)eu_observe_slab_mine(S, plan, EU_OBS_REC_FLOW);
+    a.py0 = plan->p_lo[r]; a.cy0 = plan->ya[r]; a.cy1 = plan->yb[r]; a.add = 1;
+    Hl = plan->p_hi[r] - plan->p_lo[r] + 1;
+  } else if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->flow_buf.p, 0, (size_t)W * H * sizeof(euler_flow_px), S->stream));
+  const long long nwg = (long long)((W + a.npc - 1) / a.npc) * Hl * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
   const dim3 grid((unsigned)nwg);
   if (S->X % 4 == 0) LAUNCH(S, KC_MISC, (k_flow<4>), grid, dim3(FL_T), a);
   else LAUNCH(S, KC_MISC, (k_flow<1>), grid, dim3(FL_T), a);
@@ -323,15 +337,23 @@ static int fl_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H)
 }
 
 // the pressure part, behind the velocity part on the same stream: adds p_sum, max_p and the cells only a NaN pressure makes nonfinite
-static int fp_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H) {
+static int fp_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H, const eu_slab_plan* plan = nullptr) {
   FpArgs a;
   a.p = S->p; a.g = S->geom;
   a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
   a.W = W; a.H = H; a.bx0 = x0; a.by0 = y0; a.bx1 = x1; a.by1 = y1; a.Bw = x1 - x0 + 1; a.Bh = y1 - y0 + 1;
   a.band0 = y0 >> 6; a.nbands = (y1 >> 6) - a.band0 + 1;
+  a.py0 = 0;
+  a.out = (euler_flow_px*)S->flow_buf.p;
+  if (plan) {      // the own bands the box crosses: the skewed p of a slab holds them (shifted by skew_off, and finished in memory)
+    const int r = S->cfg.slab_rank;
+    if (plan->cnt[r] == 0) return EULER_OK;
+    a.band0 = plan->ya[r] >> 6; a.nbands = (plan->yb[r] >> 6) - a.band0 + 1;
+    a.py0 = plan->p_lo[r];
+    a.out = (euler_flow_px*)eu_observe_slab_mine(S, plan, EU_OBS_REC_FLOW);
+  }
   a.tbase = x0 & ~1;      // records x0 ... x1 + 63 of a band hold the box's columns
   a.runs = (x1 + 63 - a.tbase) / (2 * FP_RUN) + 1;
-  a.out = (euler_flow_px*)S->flow_buf.p;
   const long long waves = (long long)a.nbands * a.runs;
   LAUNCH(S, KC_MISC, k_flow_pressure, dim3((unsigned)((waves + 3) / 4)), dim3(256), a);
   HIPCHK(hipGetLastError());
@@ -340,7 +362,7 @@ static int fp_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H)
 
 extern "C" int euler_flow_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H, int32_t flags, euler_flow_px* out, size_t out_bytes) {
   const char* who = "euler_flow_raster";
-  int rc = eu_observe_enter(S, who, "a box of cells straddles slabs", out, x0, y0, x1, y1);
+  int rc = eu_observe_enter(S, who, nullptr, out, x0, y0, x1, y1);
   if (rc) return rc;
   if (W < 1 || H < 1 || W > x1 - x0 + 1 || H > y1 - y0 + 1) { eu_set_error("%s: a raster of %d x %d for a box of %d x %d cells", who, W, H, x1 - x0 + 1, y1 - y0 + 1); return EULER_EINVAL; }
   const size_t n = (size_t)W * (size_t)H;
@@ -348,7 +370,15 @@ extern "C" int euler_flow_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x
   if (flags & ~EULER_FLOW_PRESSURE) { eu_set_error("%s: unknown flag bits %d", who, flags & ~EULER_FLOW_PRESSURE); return EULER_EINVAL; }
   rc = eu_devbuf_reserve(S, who, "the records", &S->flow_buf, out_bytes);
   if (!rc && (flags & EULER_FLOW_PRESSURE)) rc = eu_pressure_current(S);      // (k_velocity_update_para leaves the last fmadds and the clamp to whoever looks)
-  if (!rc) rc = fl_launch(S, x0, y0, x1, y1, W, H);
-  if (!rc && (flags & EULER_FLOW_PRESSURE)) rc = fp_launch(S, x0, y0, x1, y1, W, H);
+  eu_slab_plan plan;
+  const eu_slab_plan* pl = S->slab_on ? &plan : nullptr;
+  if (pl) {      // collective: the own rows into this rank's share, the shares folded into the records on every rank
+    const int rp = eu_observe_slab_plan(S, &plan, y0, y1, W, H);      // (the same on every rank)
+    if (rp) return rp;
+    rc = eu_observe_slab_open(S, who, rc, (size_t)plan.total * sizeof(euler_flow_px), EU_OBS_ROWS_FLOW);
+  }
+  if (!rc) rc = fl_launch(S, x0, y0, x1, y1, W, H, pl);
+  if (!rc && (flags & EULER_FLOW_PRESSURE)) rc = fp_launch(S, x0, y0, x1, y1, W, H, pl);
+  if (!rc && pl) rc = eu_observe_slab_fold(S, pl, EU_OBS_REC_FLOW, S->flow_buf.p);
   return rc ? rc : eu_observe_readback(S, out, &S->flow_buf, out_bytes);
 }

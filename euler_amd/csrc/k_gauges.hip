@@ -224,7 +224,7 @@ struct GaStage {      // the host's copy of what goes up: freed on every way out
 
 extern "C" int euler_gauges(euler_sim* S, const euler_gauge* g, int32_t n, euler_gauge_rec* out, size_t out_bytes) {
   const char* who = "euler_gauges";
-  int rc = eu_observe_enter(S, who, "the integer records would sum across ranks", g ? (const void*)out : nullptr, 1, 1, 1, 1);
+  int rc = eu_observe_enter(S, who, nullptr, g ? (const void*)out : nullptr, 1, 1, 1, 1);
   if (rc) return rc;
   if (n < 1 || n > EULER_GAUGES_MAX) { eu_set_error("%s: %d gauges (1 ... %d)", who, n, EULER_GAUGES_MAX); return EULER_EINVAL; }
   const size_t rec_bytes = (size_t)n * sizeof(euler_gauge_rec);
@@ -235,21 +235,29 @@ extern "C" int euler_gauges(euler_sim* S, const euler_gauge* g, int32_t n, euler
     eu_set_error("%s: gauge %d (kind %d, box [%d, %d] x [%d, %d], reserved %d): %s [1, %d] x [1, %d]", who, bad, g[bad].kind, g[bad].x0, g[bad].x1, g[bad].y0, g[bad].y1, g[bad].reserved, what, S->X - 2, S->Y - 2);
     return EULER_EINVAL;
   }
-  const size_t nchunks = eu_gauge_chunks(g, n, nullptr);
+  // (row slabs: chunks are cut along the tile grid and a slab is whole 64-row bands, so every chunk has one owner; this rank's table holds its own only)
+  const int band_lo = S->slab_on ? S->band_lo : 0, band_hi = S->slab_on ? S->band_hi : INT32_MAX;
+  const size_t nchunks = eu_gauge_chunks_bands(g, n, band_lo, band_hi, nullptr);
   if (nchunks > 0xffffffffull) { eu_set_error("%s: %zu chunks", who, nchunks); return EULER_EINVAL; }
   const size_t bytes = rec_bytes + nchunks * sizeof(eu_gauge_chunk);      // the records first (72 n bytes: the chunk table stays 8-byte aligned)
   GaStage st;
   if (!(st.p = malloc(bytes))) { eu_set_error("%s: %zu bytes of host memory for the chunk table", who, bytes); return EULER_ENOMEM; }
   euler_gauge_rec* init = (euler_gauge_rec*)st.p;
   memset(init, 0, rec_bytes);
-  bool pressure = false;
+  bool pressure = false, faces = false;
   for (int k = 0; k < n; ++k) {
     init[k].lo_x = init[k].lo_y = 0xffffffffu;
     pressure |= g[k].kind == EULER_GAUGE_PRESSURE || g[k].kind == EULER_GAUGE_FORCE;
+    faces |= g[k].kind == EULER_GAUGE_FLUX;      // (FORCE looks across a row edge too, at the solid grid: the load's, never stale)
   }
-  eu_gauge_chunks(g, n, (eu_gauge_chunk*)((char*)st.p + rec_bytes));
+  eu_gauge_chunks_bands(g, n, band_lo, band_hi, (eu_gauge_chunk*)((char*)st.p + rec_bytes));
   rc = eu_devbuf_reserve(S, who, "the records and the chunk table", &S->gauge_buf, bytes);
   if (!rc && pressure) rc = eu_pressure_current(S);      // (k_velocity_update_para leaves the last fmadds and the clamp to whoever looks)
+  eu_slab_plan plan;
+  if (S->slab_on) {      // collective: every rank's n records of its own chunks (the initial records where it has none), gathered and folded by add / min / max
+    if (eu_slab_plan_flat(&plan, S->cfg.slab_nranks, n)) { eu_set_error("%s: %d ranks", who, S->cfg.slab_nranks); return EULER_EINVAL; }
+    rc = eu_observe_slab_open(S, who, rc, (size_t)plan.total * sizeof(euler_gauge_rec), faces ? EU_OBS_ROWS_GAUGES : EU_OBS_ROWS_NONE);
+  }
   if (rc) return rc;
   st.busy = S->stream; st.in_flight = true;
   HIPCHK(hipMemcpyAsync(S->gauge_buf.p, st.p, bytes, hipMemcpyHostToDevice, S->stream));
@@ -259,7 +267,11 @@ extern "C" int euler_gauges(euler_sim* S, const euler_gauge* g, int32_t n, euler
   a.out = (euler_gauge_rec*)S->gauge_buf.p;
   a.chunks = (const eu_gauge_chunk*)((const char*)S->gauge_buf.p + rec_bytes);
   a.nchunks = (unsigned int)nchunks;
-  LAUNCH(S, KC_MISC, k_gauges, dim3((unsigned)(nchunks < GA_MAX_WG ? nchunks : GA_MAX_WG)), dim3(GA_T), a);
+  if (nchunks) LAUNCH(S, KC_MISC, k_gauges, dim3((unsigned)(nchunks < GA_MAX_WG ? nchunks : GA_MAX_WG)), dim3(GA_T), a);      // (a slab that owns no chunk launches nothing)
   HIPCHK(hipGetLastError());
+  if (S->slab_on) {
+    HIPCHK(hipMemcpyAsync(eu_observe_slab_mine(S, &plan, EU_OBS_REC_GAUGE), S->gauge_buf.p, rec_bytes, hipMemcpyDeviceToDevice, S->stream));
+    if ((rc = eu_observe_slab_fold(S, &plan, EU_OBS_REC_GAUGE, S->gauge_buf.p))) return rc;
+  }
   return eu_observe_readback(S, out, &S->gauge_buf, rec_bytes);      // (waits for the stream: the host's copy is free to go)
 }

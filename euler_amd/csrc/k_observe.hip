@@ -1,11 +1,14 @@
 // k_observe.hip — the host side that the read-only observer passes share (k_overview.hip, k_diagnostics.hip, k_viewport.hip;
-// docs/observer_passes.md): a pass enters, reserves its device buffer, launches, and reads back.  The device side is k_observe.h.
+// docs/observer_passes.md): a pass enters, reserves its device buffer, launches, and reads back.  The device side is k_observe.h; what a row-slab handle adds
+// between the launch and the read-back - the all-gather of the ranks' partial records and their fold - is k_observe_slab.hip.
 #include "euler_dev.h"
 
-// the checks every pass makes first, in this order; its own (raster, scale, byte count) come behind
+// the checks every pass makes first, in this order; its own (raster, scale, byte count) come behind.  All of them depend on the arguments and on facts every rank
+// of a row-slab job shares, so there every rank refuses alike, before any exchange
 int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reason, const void* out, int x0, int y0, int x1, int y1) {
   if (!S || !out) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (%s)", who, slab_reason); return EULER_ESTATE; }
+  if (S->slab_on && slab_reason) { eu_set_error("%s: not on a row-slab handle (%s)", who, slab_reason); return EULER_ESTATE; }
+  if (S->slab_on && !S->has_comm) { eu_set_error("%s: row-slab handle without a communicator", who); return EULER_ESTATE; }      // (a pass that runs on slabs is collective there)
   if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
   if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
     eu_set_error("%s: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", who, x0, x1, y0, y1, S->X - 2, S->Y - 2);

@@ -25,6 +25,8 @@ struct OvArgs {
   ObTiles tiles;
   int X, Y, W, H, npc, nsplit;
   int bx0, by1, Bw, Bh;     // the box: its left column, its top row, its extent in cells (the whole interior: 1, Y - 2, X - 2, Y - 2)
+  int py0, cy0, cy1, add;   // row slabs (k_observe_slab.hip): the first pixel row launched - out starts there -, the rows of the box this rank owns, and "out is zeroed: add";
+                            // a whole-grid handle: 0, the box's rows, nsplit > 1
   euler_overview_px* out;
 };
 
@@ -62,11 +64,13 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
   const unsigned int Xi = (unsigned int)a.Bw, Yi = (unsigned int)a.Bh;
   const unsigned int groups = (unsigned int)((a.W + a.npc - 1) / a.npc), slice = blockIdx.x / groups;      // (neighbouring workgroups lie along a row)
   const int p0 = (int)(blockIdx.x % groups) * a.npc, p1 = p0 + a.npc < a.W ? p0 + a.npc : a.W;      // this workgroup's pixel columns [p0, p1)
-  const int py = (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
+  const int py = a.py0 + (int)(slice / (unsigned int)a.nsplit), sp = (int)(slice % (unsigned int)a.nsplit);
   const int xa = a.bx0 + (int)((unsigned long long)p0 * Xi / (unsigned int)a.W), xb = a.bx0 - 1 + (int)((unsigned long long)p1 * Xi / (unsigned int)a.W);      // its columns [xa, xb]
   const int ytop = a.by1 - (int)((unsigned long long)py * Yi / (unsigned int)a.H), ybot = a.by1 + 1 - (int)((unsigned long long)(py + 1) * Yi / (unsigned int)a.H);
   const int nrows = ytop - ybot + 1;
-  const int yhi = ytop - (int)((long long)sp * nrows / a.nsplit), ylo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows yhi down to ylo
+  const int shi = ytop - (int)((long long)sp * nrows / a.nsplit), slo = ytop - (int)((long long)(sp + 1) * nrows / a.nsplit) + 1;      // this slice: rows shi down to slo ...
+  const int yhi = shi < a.cy1 ? shi : a.cy1, ylo = slo > a.cy0 ? slo : a.cy0;      // ... of which this rank owns yhi down to ylo (a whole-grid handle: all)
+  if (yhi < ylo) return;      // (the whole workgroup: nothing of the slice is here)
   for (int k = tid; k < OV_NPC; k += OV_T) {
     for (int f = 0; f < 5; ++f) tab.w[f][k] = 0u;
     for (int c = 0; c < 3; ++c) tab.dye[c][k] = 0ull;
@@ -140,14 +144,14 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
     const int p = p0 + k;
     const unsigned int wpx = (unsigned int)((unsigned long long)(p + 1) * Xi / (unsigned int)a.W) - (unsigned int)((unsigned long long)p * Xi / (unsigned int)a.W);
     const unsigned int cells = wpx * (unsigned int)(yhi - ylo + 1);
-    euler_overview_px* o = a.out + (size_t)py * a.W + p;
-    if (a.nsplit == 1) {
+    euler_overview_px* o = a.out + (size_t)(py - a.py0) * a.W + p;
+    if (!a.add) {
       euler_overview_px r;
       r.cells = cells; r.solid = tab.w[0][k]; r.sink = tab.w[1][k]; r.water = tab.w[2][k]; r.marks = tab.w[3][k];
       r.max_speed2 = __uint_as_float(tab.w[4][k]);
       r.dye[0] = tab.dye[0][k]; r.dye[1] = tab.dye[1][k]; r.dye[2] = tab.dye[2][k];
       *o = r;
-    } else {      // a slice of the box's rows: added to the record the host zeroed (integers and a maximum: exact in any order)
+    } else {      // a slice of the box's rows, or a rank's share of them: added to the record the host zeroed (integers and a maximum: exact in any order)
       if (cells) atomicAdd(&o->cells, cells);
       if (tab.w[0][k]) atomicAdd(&o->solid, tab.w[0][k]);
       if (tab.w[1][k]) atomicAdd(&o->sink, tab.w[1][k]);
@@ -162,7 +166,8 @@ __global__ __launch_bounds__(OV_T) void k_overview(const OvArgs a) {
 }
 
 // the reduction alone, on the handle's stream, into the records of S->ov_buf (tools/overview_cost.py times it through the KC_MISC class)
-static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H) {
+// plan: row slabs - the records go to this rank's share of the staging area, the pixel rows its rows touch only
+static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H, const eu_slab_plan* plan = nullptr) {
   const int Xi = x1 - x0 + 1, Yi = y1 - y0 + 1;      // (the box's extent: npc and nsplit follow it)
   OvArgs a;
   a.solid = S->solid; a.sink = S->sink; a.count = S->count; a.u = S->u; a.v = S->v;
@@ -175,8 +180,17 @@ static int ov_launch(euler_sim* S, int x0, int y0, int x1, int y1, int W, int H)
   const long long span = ((long long)a.npc * Xi + W - 1) / W, rows_max = (Yi + H - 1) / H, rows_min = Yi / H;
   long long ns = (span * rows_max + OV_WG_CELLS - 1) / OV_WG_CELLS;      // slices of a box's rows
   a.nsplit = (int)(ns < 1 ? 1 : (ns > rows_min ? rows_min : ns));
-  if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->ov_buf.p, 0, (size_t)W * H * sizeof(euler_overview_px), S->stream));
-  const long long nwg = (long long)((W + a.npc - 1) / a.npc) * H * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
+  a.py0 = 0; a.cy0 = y0; a.cy1 = y1; a.add = a.nsplit > 1;
+  int Hl = H;      // pixel rows launched
+  if (plan) {
+    const int r = S->cfg.slab_rank;
+    int rc = eu_observe_slab_clear_mine(S, plan, EU_OBS_REC_OVERVIEW);
+    if (rc || plan->cnt[r] == 0) return rc;      // (no row of the box is here: nothing to launch, nothing to contribute)
+    a.out = (euler_overview_px*)eu_observe_slab_mine(S, plan, EU_OBS_REC_OVERVIEW);
+    a.py0 = plan->p_lo[r]; a.cy0 = plan->ya[r]; a.cy1 = plan->yb[r]; a.add = 1;
+    Hl = plan->p_hi[r] - plan->p_lo[r] + 1;
+  } else if (a.nsplit > 1) HIPCHK(hipMemsetAsync(S->ov_buf.p, 0, (size_t)W * H * sizeof(euler_overview_px), S->stream));
+  const long long nwg = (long long)((W + a.npc - 1) / a.npc) * Hl * a.nsplit;      // (at most a workgroup per 256 cells: far below 2^31 on any grid euler_create accepts)
   const dim3 grid((unsigned)nwg);
   const bool vec = S->X % 4 == 0, dye = S->dye[0] != nullptr;
   if (vec && dye) LAUNCH(S, KC_MISC, (k_overview<4, true>), grid, dim3(OV_T), a);
@@ -193,13 +207,20 @@ int eu_overview_entered(euler_sim* S, const char* who, int x0, int y0, int x1, i
   const size_t n = (size_t)W * (size_t)H;
   if (out_bytes != n * sizeof(euler_overview_px)) { eu_set_error("%s: %zu bytes given, %zu expected", who, out_bytes, n * sizeof(euler_overview_px)); return EULER_EINVAL; }
   int rc = eu_devbuf_reserve(S, "euler_overview", "the records", &S->ov_buf, out_bytes);
-  if (!rc) rc = ov_launch(S, x0, y0, x1, y1, W, H);
+  if (S->slab_on) {      // collective: the own rows into this rank's share, the shares folded into the records on every rank
+    eu_slab_plan plan;
+    const int rp = eu_observe_slab_plan(S, &plan, y0, y1, W, H);      // (the same on every rank)
+    if (rp) return rp;
+    rc = eu_observe_slab_open(S, who, rc, (size_t)plan.total * sizeof(euler_overview_px), EU_OBS_ROWS_CELLS);
+    if (!rc) rc = ov_launch(S, x0, y0, x1, y1, W, H, &plan);
+    if (!rc) rc = eu_observe_slab_fold(S, &plan, EU_OBS_REC_OVERVIEW, S->ov_buf.p);
+  } else if (!rc) rc = ov_launch(S, x0, y0, x1, y1, W, H);
   return rc ? rc : eu_observe_readback(S, out, &S->ov_buf, out_bytes);
 }
 
 // the call behind euler_overview (the whole interior) and euler_overview_box
 static int ov_call(euler_sim* S, const char* who, int x0, int y0, int x1, int y1, int W, int H, euler_overview_px* out, size_t out_bytes) {
-  const int rc = eu_observe_enter(S, who, "a box of cells straddles slabs", out, x0, y0, x1, y1);
+  const int rc = eu_observe_enter(S, who, nullptr, out, x0, y0, x1, y1);
   return rc ? rc : eu_overview_entered(S, who, x0, y0, x1, y1, W, H, out, out_bytes);
 }
 

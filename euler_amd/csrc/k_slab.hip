@@ -209,6 +209,28 @@ int eu_slab_exchange_dye(euler_sim* S) {
   const GhostField f[3] = {{S->dye[0], 4, 1, 1}, {S->dye[1], 4, 1, 1}, {S->dye[2], 4, 1, 1}};
   return exchange_rows(S, f, 3);
 }
+// The ghost rows an observer pass reads across a row edge (k_observe_slab.hip), in ONE exchange.  u, v and the count grid are current there at every point where the
+// own rows are, except the count grid between the refresh and the sources stage; the sink grid's are stale behind a local euler_set_field(EULER_F_SINK).  Writing the
+// neighbours' current rows over them leaves no trace in the run: no stage reads the sink grid outside the own rows (k_bin_markers_slab), and the next reader of the
+// count grid's ghost rows comes behind an exchange_counts of its own
+int eu_slab_exchange_observed(euler_sim* S, int rows) {
+  if (!S->has_comm) { eu_set_error("row-slab handle without a communicator"); return EULER_ESTATE; }
+  switch (rows) {
+    case EU_OBS_ROWS_CELLS: {      // the cell-centre velocity: v one row below
+      const GhostField f[1] = {{S->v, 4, 1, 0}};
+      return exchange_rows(S, f, 1);
+    }
+    case EU_OBS_ROWS_FLOW: {       // ... and the node above a cell: u and the water bits (count, sink; the solid grid is the load's) one row above
+      const GhostField f[4] = {{S->u, 4, 0, 1}, {S->v, 4, 1, 1}, {S->count, 1, 0, 1}, {S->sink, 1, 0, 1}};
+      return exchange_rows(S, f, 4);
+    }
+    case EU_OBS_ROWS_GAUGES: {     // FLUX: the face above a cell is live through the count above it
+      const GhostField f[1] = {{S->count, 1, 1, 1}};
+      return exchange_rows(S, f, 1);
+    }
+    default: return EULER_OK;
+  }
+}
 static int exchange_vtmp(euler_sim* S) {
   const GhostField f[1] = {{S->vtmp, 4, 1, 0}};
   return exchange_rows(S, f, 1);

@@ -22,6 +22,7 @@ struct VrArgs {
   const float4* m2;           // the marker array, two markers per element
   unsigned long long n;       // markers
   float fx0, fy0, fs, fW, fH; // the box origin, the scale and the raster's extent as floats (all exact: integers <= 2^24)
+  float fylo, fyhi;           // the sub-pixel rows counted, from the box's bottom: 0 and fH; row slabs: those of the rank's own cell rows (a marker on its way to a neighbour is the neighbour's)
   int W, H;
   unsigned int* out;
 };
@@ -29,7 +30,7 @@ struct VrArgs {
 // the sub-pixel of a position; false: outside the box (a NaN fails every comparison, an infinity the upper ones)
 __device__ __forceinline__ bool vr_pixel(const VrArgs& a, float x, float y, unsigned int& pix) {
   const float sx = (x - a.fx0) * a.fs, sy = (y - a.fy0) * a.fs;
-  const bool in = sx >= 0.f && sx < a.fW && sy >= 0.f && sy < a.fH;
+  const bool in = sx >= 0.f && sx < a.fW && sy >= a.fylo && sy < a.fyhi;
   pix = in ? (unsigned int)(a.H - 1 - (int)sy) * (unsigned int)a.W + (unsigned int)(int)sx : 0u;      // (W * H <= 2^24: no wrap)
   return in;
 }
@@ -68,13 +69,14 @@ __global__ __launch_bounds__(VR_T) void k_marker_raster(const VrArgs a) {
 }
 
 // the clear and the pass alone, on the handle's stream, into the raster of S->vr_buf (tools/viewport_cost.py times the pass through the KC_MISC class)
-static int vr_launch(euler_sim* S, int x0, int y0, int scale, int W, int H) {
+// ya, yb: the cell rows counted (the box's; row slabs: the rank's own rows of it, ya > yb: none); n: the markers of the array
+static int vr_launch(euler_sim* S, int x0, int y0, int scale, int W, int H, int ya, int yb, unsigned long long n) {
   HIPCHK(hipMemsetAsync(S->vr_buf.p, 0, (size_t)W * H * sizeof(unsigned int), S->stream));
-  const unsigned long long n = S->n_markers_host;
-  if (!n) return EULER_OK;
+  if (!n || ya > yb) return EULER_OK;
   VrArgs a;
   a.m2 = reinterpret_cast<const float4*>(S->markers[S->cur]); a.n = n;
   a.fx0 = (float)x0; a.fy0 = (float)y0; a.fs = (float)scale; a.fW = (float)W; a.fH = (float)H;
+  a.fylo = (float)((ya - y0) * scale); a.fyhi = (float)((yb + 1 - y0) * scale);      // (the box's rows: 0 and fH)
   a.W = W; a.H = H; a.out = (unsigned int*)S->vr_buf.p;
   const unsigned long long nwg = (n + 2ull * VR_T - 1ull) / (2ull * VR_T);      // (at most max_markers / 512: far below 2^31 on any grid euler_create accepts)
   LAUNCH(S, KC_MISC, k_marker_raster, dim3((unsigned)nwg), dim3(VR_T), a);
@@ -90,18 +92,39 @@ static int vr_entered(euler_sim* S, int x0, int y0, int x1, int y1, int scale, u
   const size_t n = (size_t)(W * H);
   if (out_bytes != n * sizeof(uint32_t)) { eu_set_error("euler_marker_raster: %zu bytes given, %zu expected", out_bytes, n * sizeof(uint32_t)); return EULER_EINVAL; }
   int rc = eu_devbuf_reserve(S, "euler_marker_raster", "the raster", &S->vr_buf, out_bytes);
-  if (!rc) rc = vr_launch(S, x0, y0, scale, (int)W, (int)H);
+  if (S->slab_on) {      // collective: a rank counts its own markers into the raster rows of its own cell rows - disjoint between ranks -, an in-place all-gather makes the raster whole
+    int64_t off[EU_SLAB_PLAN_MAXR], cnt[EU_SLAB_PLAN_MAXR];
+    const int R = S->cfg.slab_nranks;
+    if (R > EU_SLAB_PLAN_MAXR) { eu_set_error("euler_marker_raster: %d ranks", R); return EULER_EINVAL; }
+    int ya = 0, yb = -1;
+    for (int r = 0; r < R; ++r) {      // raster row H - 1 - k holds sub-row k from the box's bottom: the rows [ya, yb] are the raster rows H - (yb + 1 - y0) scale ... H - 1 - (ya - y0) scale
+      int a0, b0;
+      const int some = eu_slab_clip_rows(S->part_lo[r], S->part_hi[r], S->Y, y0, y1, &a0, &b0);
+      off[r] = some ? (int64_t)(H - (long long)(b0 + 1 - y0) * scale) * W * (int64_t)sizeof(uint32_t) : 0;
+      cnt[r] = some ? (int64_t)(b0 - a0 + 1) * scale * W * (int64_t)sizeof(uint32_t) : 0;
+      if (r == S->cfg.slab_rank) { ya = a0; yb = b0; }
+    }
+    rc = eu_observe_slab_open(S, "euler_marker_raster", rc, 0, EU_OBS_ROWS_NONE);
+    unsigned long long n_loc = 0;      // (read here, not through eu_sync_marker_state: between two stages the host's count is the substep's, and stays)
+    if (!rc) {
+      HIPCHK(hipMemcpyAsync(&n_loc, &S->ms->n_loc, sizeof n_loc, hipMemcpyDeviceToHost, S->stream));
+      HIPCHK(hipStreamSynchronize(S->stream));
+      rc = vr_launch(S, x0, y0, scale, (int)W, (int)H, ya, yb, n_loc);
+    }
+    if (!rc) rc = eu_observe_slab_gather_in_place(S, S->vr_buf.p, off, cnt);
+  } else
+  if (!rc) rc = vr_launch(S, x0, y0, scale, (int)W, (int)H, y0, y1, S->n_markers_host);
   return rc ? rc : eu_observe_readback(S, out, &S->vr_buf, out_bytes);
 }
 
 extern "C" int euler_marker_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t scale, uint32_t* out, size_t out_bytes) {
-  const int rc = eu_observe_enter(S, "euler_marker_raster", "a slab holds the markers of its own rows only", out, x0, y0, x1, y1);
+  const int rc = eu_observe_enter(S, "euler_marker_raster", nullptr, out, x0, y0, x1, y1);
   return rc ? rc : vr_entered(S, x0, y0, x1, y1, scale, out, out_bytes);
 }
 
 extern "C" int euler_render_view(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len) {
   if (!S || !len || wx < 1 || wy < 1) { eu_set_error("euler_render_view: bad argument"); return EULER_EINVAL; }
-  int rc = eu_observe_enter(S, "euler_render_view", "a box of cells straddles slabs", len, x0, y0, x1, y1);
+  int rc = eu_observe_enter(S, "euler_render_view", nullptr, len, x0, y0, x1, y1);
   if (rc) return rc;
   const int Bw = x1 - x0 + 1, Bh = y1 - y0 + 1;
   int scale = 0;      // 0: at or below one cell per glyph

@@ -71,6 +71,8 @@ class TorchComm:
         key = (ptr, nbytes, dtype)
         t = self._cache.get(key)
         if t is None:                  # the handle's buffers never move: wrap each one once
+            if len(self._cache) >= 4096:      # (but the observer passes gather another range of their staging area for every box and raster: start afresh)
+                self._cache.clear()
             t = self.torch.as_tensor(_DevMem(ptr, nbytes), device="cuda")
             if dtype is not None:
                 t = t.view(dtype)

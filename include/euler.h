@@ -324,8 +324,10 @@ typedef struct euler_overview_px {   /* one output pixel = one box of interior c
  * picture: row py covers y = Y - 2 - floor(py * Yi / H) down to y = Y - 1 - floor((py + 1) * Yi / H).  out holds W * H records, row py at
  * out + py * W; out_bytes must be exactly W * H * sizeof(euler_overview_px).  One launch on the handle's stream that only READS the state
  * (the arrays euler_get_field returns for U, V, COUNT, SOLID, SINK, DYE_*): stepping afterwards gives the bits of a run that never called it.
- * The device buffer of the records comes with the first call and grows with W * H (EULER_ENOMEM: the handle unchanged).  Row-slab handles
- * refuse (EULER_ESTATE); a handle without a loaded state: EULER_ESTATE. */
+ * The device buffer of the records comes with the first call and grows with W * H (EULER_ENOMEM: the handle unchanged).  A handle
+ * without a loaded state: EULER_ESTATE.  On a row-slab handle the call is COLLECTIVE, as euler_render is: it needs the communicator (else EULER_ESTATE), every rank
+ * calls with the same arguments and every rank gets the same bytes - those of a whole-grid handle holding the same state (each rank reduces its own rows, the
+ * integer records are gathered and folded on the device: docs/observer_passes.md "On row slabs").  So are euler_render_fit and euler_overview_box. */
 int euler_overview(euler_sim* sim, int32_t W, int32_t H, euler_overview_px* out, size_t out_bytes);
 /* Host formatters over such records (no GPU needed).  The class of a pixel, in this order: 2 * solid >= cells: solid ('X'); else, with
  * open = cells - solid - sink: sink > 0 && sink >= open: sink ('='); else k = min(3, (marks + open - 1) / open) is the glyph index of
@@ -366,7 +368,8 @@ int euler_overview_box(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32
  * and the counts are integers that do not depend on the launch geometry (tests compare them exactly).  One pass over the marker array behind a
  * clear of the raster, on the handle's stream; it only READS the markers: stepping afterwards gives the bits of a run that never called it.
  * The raster's device buffer comes with the first call, grows on demand (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy.
- * EULER_ESTATE without a loaded state and on a row-slab handle (a slab holds its own markers only). */
+ * EULER_ESTATE without a loaded state.  On a row-slab handle the call is COLLECTIVE: it needs the communicator (else EULER_ESTATE), every rank calls with the same
+ * arguments, counts its own markers into the raster rows of its own cell rows, and every rank gets the same bytes - the whole-grid handle's. */
 int euler_marker_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                         int32_t scale, uint32_t* out, size_t out_bytes);
 /* Host formatter of a magnified view (no GPU needed).  cells: the box at ONE cell per record (Bw x Bh records, row 0 = top); raster: the
@@ -379,7 +382,8 @@ int euler_view_text(const euler_overview_px* cells, const uint32_t* raster, int3
 /* The frame of a box in a window of wx x wy glyphs (wx < 1 or wy < 1: EULER_EINVAL).  Where the window holds the box at least twice in both
  * directions (Bw * 2 <= wx and Bh * 2 <= wy): the largest scale <= 16 with Bw * scale <= wx and Bh * scale <= wy, euler_overview_box at one cell per
  * pixel, euler_marker_raster, euler_view_text.  Otherwise euler_overview_box with W = min(wx, Bw), H = min(wy, Bh), then euler_overview_text.  Coloured
- * on a handle created with euler_config.rainbow.  Sizing protocol of euler_render. */
+ * on a handle created with euler_config.rainbow.  Sizing protocol of euler_render.  On a row-slab handle the call is COLLECTIVE like the calls it is made of: it
+ * needs the communicator (else EULER_ESTATE) and returns the same bytes on every rank, the whole-grid handle's. */
 int euler_render_view(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                       int32_t wx, int32_t wy, char* out, int32_t cap, int32_t* len);
 
@@ -419,7 +423,8 @@ typedef struct euler_diag_values {   /* what a user reads off a record; all 0 wh
   double crowded_fraction;  /* crowded / fluid */
 } euler_diag_values;
 /* The box must lie in the interior, 1 <= x0 <= x1 <= X - 2 and 1 <= y0 <= y1 <= Y - 2, and out_bytes must be sizeof(euler_diag): else EULER_EINVAL.
- * EULER_ESTATE without a loaded state and on a row-slab handle (summing the records across ranks is a follow-up).  One launch on the handle's stream
+ * EULER_ESTATE without a loaded state.  On a row-slab handle the call is COLLECTIVE: it needs the communicator (else EULER_ESTATE), every rank calls with the same
+ * arguments and gets the same record, the whole-grid handle's - the ranks' records of their own rows, gathered and summed on the device.  One launch on the handle's stream
  * that only READS u, v, count, solid and the tile map: stepping afterwards gives the bits of a run that never called it.  The 88-byte device record
  * comes with the first call (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy. */
 int euler_diagnostics(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, euler_diag* out, size_t out_bytes);
@@ -456,7 +461,8 @@ typedef struct euler_flow_px {   /* 88 bytes, no padding */
   uint32_t reserved;    /* 0 */
 } euler_flow_px;
 /* The box, W and H as for euler_overview_box; out_bytes exactly W * H * sizeof(euler_flow_px) and no flag bit but EULER_FLOW_PRESSURE: else EULER_EINVAL.
- * EULER_ESTATE without a loaded state and on a row-slab handle.  Reads the state only: stepping afterwards gives the bits of a run that never
+ * EULER_ESTATE without a loaded state.  On a row-slab handle the call is COLLECTIVE: it needs the communicator (else EULER_ESTATE), every rank calls with the same
+ * arguments and gets the same bytes, the whole-grid handle's.  Reads the state only: stepping afterwards gives the bits of a run that never
  * called it (with the flag the pending pressure is first finished in memory, as euler_get_field(EULER_F_PRESSURE) does).  The records' device buffer
  * comes with the first call, grows with W * H (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy; no whole-grid staging copy is made. */
 int euler_flow_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
@@ -508,11 +514,13 @@ typedef struct euler_gauge_values {   /* what a user reads off a record; all 0 w
   double depth;       /* hi_y - lo_y + 1 */
 } euler_gauge_values;
 /* n gauges, 1 <= n <= EULER_GAUGES_MAX, into n records; gauges may overlap and repeat.  Refusals in this order: a null pointer (EULER_EINVAL), a row-slab
- * handle, nothing loaded (EULER_ESTATE); n out of range or out_bytes != n * sizeof(euler_gauge_rec) (EULER_EINVAL); then per gauge, naming its index: an
+ * handle without a communicator, nothing loaded (EULER_ESTATE); n out of range or out_bytes != n * sizeof(euler_gauge_rec) (EULER_EINVAL); then per gauge, naming its index: an
  * unknown kind, reserved != 0, a box outside the interior or with x0 > x1 or y0 > y1 (EULER_EINVAL).  A refused call allocates nothing and leaves out
  * untouched.  Reads the state only: stepping afterwards gives the bits of a run that never called it (with a PRESSURE or FORCE gauge in the list the
  * pending pressure is first finished in memory, as euler_get_field(EULER_F_PRESSURE) does).  The device buffer of the pass comes with the first call, grows
- * with the list (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy. */
+ * with the list (EULER_ENOMEM: the handle unchanged) and goes with euler_destroy.  On a row-slab handle the call is COLLECTIVE: every rank calls with the same list
+ * and gets the same records, the whole-grid handle's - each rank evaluates the tiles of the boxes in its own bands, the records are gathered and folded (sums added, extents and
+ * maxima by min / max) on the device. */
 int euler_gauges(euler_sim* sim, const euler_gauge* g, int32_t n, euler_gauge_rec* out, size_t out_bytes);
 int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_values* out);   /* host only, no GPU; EULER_EINVAL: a null pointer, an unknown kind */
 
