@@ -211,7 +211,7 @@ struct euler_sim {
   double* cc_part;                   // [chunks][3]: per tile, the sums of r over its fluid cells by coarse column (k_precond_tile)
   double* cc_y;                      // [n]: the coarse correction of the iteration (k_coarse_solve)
   double* cc_null;                   // [4][CC_MAX] + 1: the indicators of up to four fluid regions cut off from the air (null vectors of the dense level) and, last, how many (k_coarse_nullfix)
-  // EULER_PRECOND_IC0_TILE_MG (multilevel; k_mg.hip): levels 0 .. mg_levels - 1 of node grids, mg_nx[l] x mg_ny[l] nodes (level 0: a node per MG_G0 x MG_G0 = 8 x 8 cells, AT the centre of cell (8 J + 4, 8 I + 4) - k_mg.h; each level
+  // EULER_PRECOND_IC0_TILE_MG (multilevel; k_mg.hip, k_mg_cycle.hip, k_mg_split.hip; the dimensions: eu_mg_levels, euler_host.c): levels 0 .. mg_levels - 1 of node grids, mg_nx[l] x mg_ny[l] nodes (level 0: a node per MG_G0 x MG_G0 = 8 x 8 cells, AT the centre of cell (8 J + 4, 8 I + 4) - k_mg.h; each level
   // above every other node of the one below; the last level is the dense one), pooled arrays with level l at offset mg_off[l]
   int mg_levels, mg_nx[12], mg_ny[12];
   size_t mg_off[12], mg_cells;
@@ -224,7 +224,7 @@ struct euler_sim {
   double* mg_dot;                    // per-workgroup partials of x_0 . rhs_0 (+ the ticket counters behind them)
   double* mg_null0;                  // [4][mg_cells]: the indicators of cut-off regions on every level (k_mg_null_prolong)
   double* mg_m0;                     // [4][nodes of level 0] + [4]: P_0^T of those indicators on the cells, and m_0 . n_0 (the gauge of k_mg_up)
-  void* mg_split;                    // row slabs: the plan and buffers of the split cycle (k_mg.hip MgSplitState), built on first use
+  void* mg_split;                    // row slabs: the plan and buffers of the split cycle (k_mg_split.hip MgSplitState), built on first use
   double* mg_xbuf; int mg_xslot;     // row slabs: [ranks][mg_xslot] - every rank's {max |r|, dot(z,r), its share of the level-0 right-hand side}, ONE all-gather inside the G1 exchange
   // the resident solver (k_resident.hip): the tile-local PCG of a grid whose chunks all find a wave on the chip at once, in ONE persistent launch
   unsigned long long* res_gran;   // [2][3][768] 16-byte {value, generation} granules of its grid-wide reductions

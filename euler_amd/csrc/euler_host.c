@@ -542,6 +542,135 @@ int eu_slab_plan_contributors(const eu_slab_plan* P, int32_t py, int32_t* first,
   return EULER_OK;
 }
 
+/* ---- the multilevel preconditioner: its node grids and the plan of the cycle split by rows (euler_host.h, docs/solver_multilevel_row_slabs.md) ---- */
+
+int eu_mg_levels(int32_t X, int32_t nbands, int32_t* nx, int32_t* ny, size_t* off) {
+  if (!nx || !ny || !off || X < 1 || nbands < 1 || nbands > INT32_MAX / MG_RPB) return EULER_EINVAL;
+  int32_t w = (X - 1) / MG_G0 + 1, h = MG_RPB * nbands;
+  size_t at = 0;
+  for (int l = 0; l < MG_MAXLEV; ++l) {
+    nx[l] = w; ny[l] = h; off[l] = at; at += (size_t)w * (size_t)h;
+    if ((int64_t)w * h <= MG_TOP_MAX) return l + 1;
+    w = (w + 1) / 2; h = (h + 1) / 2;
+  }
+  return EULER_EINVAL;
+}
+
+static int64_t mg_nodes(const int32_t* nx, const int32_t* ny, int l) { return (int64_t)nx[l] * ny[l]; }
+
+int eu_mg_entry_level(int32_t levels, const int32_t* nx, const int32_t* ny) {
+  int l = 0;
+  while (l < levels - 1 && mg_nodes(nx, ny, l) > MG_TAIL_MAX) ++l;
+  return l;
+}
+
+int eu_mg_gather_level(int32_t levels, const int32_t* nx, const int32_t* ny, int64_t forced) {
+  const int lC = eu_mg_entry_level(levels, nx, ny);
+  if (forced < 0) return 0;
+  if (forced > 0) return (int)(forced < lC ? forced : lC);
+  if (mg_nodes(nx, ny, 0) <= MG_SMALL_LEVEL0) return 0;
+  int l = 0;
+  while (l < lC && mg_nodes(nx, ny, l) > MG_GATHER_MAX) ++l;
+  return l;
+}
+
+static void mg_clip(int32_t* r, int32_t n) { if (r[0] < 0) r[0] = 0; if (r[1] > n) r[1] = n; if (r[1] < r[0]) r[1] = r[0]; }
+/* the rows two ranges share: out = them and their number, or {0, 0} and 0 */
+static int32_t mg_meet(const int32_t* a, const int32_t* b, int32_t* out) {
+  const int32_t lo = a[0] > b[0] ? a[0] : b[0], hi = a[1] < b[1] ? a[1] : b[1];
+  out[0] = hi > lo ? lo : 0; out[1] = hi > lo ? hi : 0;
+  return out[1] - out[0];
+}
+/* what the way up of the rank with the bands [lo, hi) needs on the levels below Lg: x_l on NX, computed from the true right-hand side on NR = NX grown by a row;
+ * the next level's NX = the coarse rows around NR (mg_coarse_around, k_mg_cycle.hip) */
+static void mg_need(const int32_t* ny, int Lg, int32_t lo, int32_t hi, int32_t (*NX)[2], int32_t (*NR)[2]) {
+  int32_t x0 = MG_RPB * lo - 1, x1 = MG_RPB * hi + 1;
+  for (int l = 0; l < Lg; ++l) {
+    NX[l][0] = x0; NX[l][1] = x1; mg_clip(NX[l], ny[l]);
+    NR[l][0] = NX[l][0] - 1; NR[l][1] = NX[l][1] + 1; mg_clip(NR[l], ny[l]);
+    x0 = NR[l][0] >> 1; x1 = ((NR[l][1] - 1) >> 1) + 2;
+  }
+}
+
+int eu_mg_split_plan_fill(eu_mg_split_plan* P, int32_t levels, const int32_t* nx, const int32_t* ny, int32_t Lg, int32_t nranks, int32_t rank,
+                          const int32_t* part_lo, const int32_t* part_hi, int32_t seg_cap) {
+  if (!P || !nx || !ny || !part_lo || !part_hi || levels < 2 || levels > MG_MAXLEV || Lg < 1 || Lg > levels - 1 || nranks < 2 || nranks > MG_SPLIT_MAXR ||
+      rank < 0 || rank >= nranks || seg_cap < 0 || seg_cap > 4 * MG_MAXLEV) return EULER_EINVAL;
+  for (int l = 0; l <= Lg; ++l) if (nx[l] < 1 || ny[l] < 1) return EULER_EINVAL;
+  if (mg_nodes(nx, ny, 0) > INT32_MAX / 18) return EULER_EINVAL;      /* every count below is at most 18 x level 0's nodes */
+  for (int r = 0; r < nranks; ++r)
+    if (part_lo[r] < 0 || part_hi[r] <= part_lo[r] || part_hi[r] > ny[0] / MG_RPB || (r > 0 && part_lo[r] < part_hi[r - 1])) return EULER_EINVAL;
+  memset(P, 0, sizeof *P);
+  const int me = rank, R = nranks;
+  P->Lg = Lg; P->ranks = R; P->rank = me;
+  for (int r = 0; r < R; ++r) {
+    /* supports: a fine row f feeds the coarse rows i with |f - 2 i| <= 1, and the residual reaches one row beyond the support: ceil((a - 2) / 2) ... floor((b + 1) / 2) */
+    int32_t a = MG_RPB * part_lo[r] - 1, b = MG_RPB * part_hi[r] + 1;
+    for (int l = 0; l <= Lg; ++l) {
+      P->I[l][r][0] = a; P->I[l][r][1] = b; mg_clip(P->I[l][r], ny[l]);
+      a = P->I[l][r][0] - 2 >= 0 ? (P->I[l][r][0] - 1) / 2 : 0; b = (P->I[l][r][1] + 1) / 2 + 1;
+    }
+    /* owners */
+    a = MG_RPB * part_lo[r]; b = MG_RPB * part_hi[r];
+    for (int l = 0; l <= Lg; ++l) {
+      P->O[l][r][0] = a; P->O[l][r][1] = b;
+      if (l < Lg && b - a < MG_SETUP_HALO) P->setup_bad = 1;
+      a = (a + 1) / 2; b = (b + 1) / 2;
+    }
+    const int32_t own = P->O[Lg][r][1] - P->O[Lg][r][0], win = P->I[Lg][r][1] - P->I[Lg][r][0];
+    if (9 * own * nx[Lg] > P->aslot) P->aslot = 9 * own * nx[Lg];
+    if (win > P->win_rows) P->win_rows = win;
+  }
+  P->nsmall = 2 + P->win_rows * nx[Lg];
+  mg_need(ny, Lg, part_lo[me], part_hi[me], P->NX, P->NR);
+  /* zones: what the neighbour on either side needs of my share, what I need of its share; its need is computed as mine is */
+  for (int side = 0; side < 2; ++side) {
+    const int nb = side == 0 ? me - 1 : me + 1;
+    if (nb < 0 || nb >= R) continue;
+    int32_t nbX[MG_MAXLEV][2], nbR[MG_MAXLEV][2], offs = 0, offr = 0;
+    mg_need(ny, Lg, part_lo[nb], part_hi[nb], nbX, nbR);
+    for (int l = 0; l < Lg; ++l) {
+      P->zoff_s[side][l] = offs; P->zoff_r[side][l] = offr;
+      offs += mg_meet(P->I[l][me], nbR[l], P->zs[side][l]) * nx[l];
+      offr += mg_meet(P->I[l][nb], P->NR[l], P->zr[side][l]) * nx[l];
+    }
+    if (offs > P->zone) P->zone = offs;
+    if (offr > P->zone) P->zone = offr;
+  }
+  /* a zone may reach into the next rank only: no rank beyond may contribute to what I need (the supports ascend with the rank: the nearest such rank decides) */
+  for (int far = me - 2; far <= me + 2; far += 4)
+    for (int l = 0; l < Lg && far >= 0 && far < R; ++l) { int32_t t[2]; if (mg_meet(P->I[l][far], P->NR[l], t)) P->beyond = 1; }
+  /* the setup by owners: what this rank reads of a level must lie within its owned rows + halo */
+  for (int l = 0; l < Lg; ++l) {
+    int32_t lo = P->I[l][me][0] - 1, hi = P->I[l][me][1] + 1;                                     /* the way down: the residual one row beyond the share's support */
+    lo = P->NR[l][0] < lo ? P->NR[l][0] : lo; hi = P->NR[l][1] > hi ? P->NR[l][1] : hi;           /* the way up */
+    const int32_t c0 = 2 * P->O[l + 1][me][0] - 1, c1 = 2 * P->O[l + 1][me][1];                   /* the next level's owned rows are formed from these */
+    int32_t rd[2] = {c0 < lo ? c0 : lo, c1 > hi ? c1 : hi};
+    if (rd[0] < 0) rd[0] = 0;
+    if (rd[1] > ny[l]) rd[1] = ny[l];
+    if (rd[0] < P->O[l][me][0] - MG_SETUP_HALO || rd[1] > P->O[l][me][1] + MG_SETUP_HALO) P->setup_bad = 1;
+  }
+  /* the segment table */
+  for (int l = 0; l < Lg; ++l) {
+    int32_t run0 = -1;
+    for (int32_t row = P->NR[l][0]; row <= P->NR[l][1]; ++row) {
+      const int touched = row < P->NR[l][1] && (!(row >= P->I[l][me][0] && row < P->I[l][me][1]) || (row >= P->zr[0][l][0] && row < P->zr[0][l][1]) ||
+                                                (row >= P->zr[1][l][0] && row < P->zr[1][l][1]));
+      if (touched && run0 < 0) run0 = row;
+      if (!touched && run0 >= 0) {
+        if (P->nseg >= seg_cap) P->overflow = 1;
+        else {
+          const eu_mg_seg s = {l, run0, row, P->total};
+          P->seg[P->nseg++] = s;
+          P->total += (row - run0) * nx[l];
+        }
+        run0 = -1;
+      }
+    }
+  }
+  return EULER_OK;
+}
+
 /* ---- forcing: the record's defaults and its uniform part, the list checked and cut into the tile table (include/euler.h, docs/forcing.md) ---- */
 
 int euler_forcing_default(euler_forcing* f) {

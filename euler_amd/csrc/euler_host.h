@@ -53,6 +53,50 @@ int      eu_tracers_check(const float* xy, size_t n, size_t count, int32_t X, in
 /* the K x K lattice of a box of cells, K in {1, 2, 4}: cell x outer, cell y inner, i outer, j inner, at x + (i + 0.5f) / K, y + (j + 0.5f) / K (every term exact in
  * float32 below 2^21).  Returns the number of points, Bw * Bh * K * K; xy == NULL: the count only; 0: an empty box or another K */
 size_t   eu_tracer_lattice(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t K, float* xy);
+/* The multilevel preconditioner's node grids and the plan of its cycle split by rows (k_mg.h, k_mg_split.hip, docs/solver_multilevel_row_slabs.md): everything that
+ * follows from the grid's size and the ranks' band ranges alone.  Row ranges are half open, [lo, hi); an empty zone is {0, 0}. */
+#ifndef MG_G0
+#define MG_G0 8              /* level 0's node spacing in grid cells (k_mg.h) */
+#endif
+#define MG_RPB (64 / MG_G0)  /* node rows of level 0 per band */
+#define MG_MAXLEV 12
+#define MG_TOP_MAX 64        /* nodes of the dense top level at most (its inverse lives in LDS: 32 KB) */
+#define MG_TAIL_MAX 1024     /* nodes of the first level the one-workgroup tail of k_mg_down takes: the ENTRY level */
+#define MG_TAIL_LEVELS 4     /* stencil levels of the tail at most (1024 -> 272 -> 72 -> top would be 3) */
+#define MG_SMALL_LEVEL0 16384 /* nodes of level 0 up to which the cycle runs as two launches of the general kernels, and is never split */
+#define MG_GATHER_MAX 16384  /* the split cycle's GATHER level: the first of at most this many nodes */
+#define MG_SETUP_HALO 6      /* rows of a level's operator that travel to either neighbour in the split setup */
+#define MG_SPLIT_MAXR 64     /* ranks of a split cycle at most */
+/* level l = nx[l] x ny[l] nodes at node off[l] of the pooled arrays (arrays of MG_MAXLEV), halved until at most MG_TOP_MAX are left; returns the number of levels,
+ * EULER_EINVAL: more than MG_MAXLEV (or X, nbands < 1) */
+int      eu_mg_levels(int32_t X, int32_t nbands, int32_t* nx, int32_t* ny, size_t* off);
+int      eu_mg_entry_level(int32_t levels, const int32_t* nx, const int32_t* ny);   /* the first level of <= MG_TAIL_MAX nodes (the top level if none is) */
+/* the gather level; 0: the cycle is not split.  forced (EULER_OPT_MG_SPLIT_LEVEL) < 0: never split, > 0: that level, the entry level at most */
+int      eu_mg_gather_level(int32_t levels, const int32_t* nx, const int32_t* ny, int64_t forced);
+typedef struct eu_mg_seg { int32_t level, row0, row1, off; } eu_mg_seg;
+typedef struct eu_mg_split_plan {
+  int32_t Lg, ranks, rank;
+  int32_t I[MG_MAXLEV][MG_SPLIT_MAXR][2];   /* [level <= Lg][rank]: the node rows a rank's own tiles can contribute to (its share's support) */
+  int32_t O[MG_MAXLEV][MG_SPLIT_MAXR][2];   /* [level <= Lg][rank]: the rows it OWNS - level 0: its bands' node rows; a coarser row belongs to the owner of the fine row under it */
+  int32_t NR[MG_MAXLEV][2];                 /* [level < Lg] this rank: the node rows whose TRUE right-hand side its way up needs */
+  int32_t NX[MG_MAXLEV][2];                 /* ... and the rows of x_l it computes */
+  int32_t zs[2][MG_MAXLEV][2];              /* [side 0: the rank below / 1: above][level]: rows of this rank's share the neighbour on that side needs */
+  int32_t zr[2][MG_MAXLEV][2];              /* rows of that neighbour's share this rank needs: zs[1] of rank r IS zr[0] of rank r + 1, and the other way round */
+  int32_t zoff_s[2][MG_MAXLEV], zoff_r[2][MG_MAXLEV];   /* offsets inside a zone message, in doubles */
+  int32_t zone;                             /* doubles of this rank's longest zone message (the job uses the maximum over the ranks) */
+  int32_t beyond;                           /* 1: a rank other than the two neighbours contributes to rows this rank needs - the cycle cannot be split */
+  int32_t setup_bad;                        /* 1: a rank owns fewer than MG_SETUP_HALO rows of a level below Lg, or this rank reads beyond its owned rows + halo: operators replicated */
+  int32_t aslot;                            /* doubles per rank of the gather level's operator all-gather: 9 x the most rows a rank owns x nx[Lg] */
+  int32_t win_rows, nsmall;                 /* window rows per rank at level Lg (the most over the ranks); doubles per all-gather slot: 2 + win_rows nx[Lg] */
+  /* behind the exchange: the rows of NR whose right-hand side changes - a neighbour's share arrives, or leftovers outside the own support must go - as ascending
+   * runs that do not touch, packed at off; overflow: more runs than the table holds (they are dropped, never written past it) */
+  int32_t nseg, total, overflow;
+  eu_mg_seg seg[4 * MG_MAXLEV];
+} eu_mg_split_plan;
+/* rank's plan for gather level Lg over the partition part_lo / part_hi (bands of the ny[0] / MG_RPB; ascending, no rank empty).  EULER_EINVAL: a null pointer, Lg outside
+ * 1 ... levels - 1, nranks outside 2 ... MG_SPLIT_MAXR, such a partition, or counts beyond int32.  seg_cap: table entries to use (<= 4 MG_MAXLEV, which callers pass) */
+int      eu_mg_split_plan_fill(eu_mg_split_plan* P, int32_t levels, const int32_t* nx, const int32_t* ny, int32_t Lg, int32_t nranks, int32_t rank,
+                               const int32_t* part_lo, const int32_t* part_hi, int32_t seg_cap);
 #ifdef __cplusplus
 }
 #endif

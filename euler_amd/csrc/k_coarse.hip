@@ -1,7 +1,7 @@
 // k_coarse.hip — the coarse levels of the TWO-LEVEL and the MULTILEVEL preconditioner (EULER_PRECOND_IC0_TILE2 / _TILE_MG, include/euler.h; round 3):
 //
 //     z = M_tile^-1 r + P (P^T A P)^-1 P^T r            (two-level; the first part of this file)
-//     z = M_tile^-1 r + P_0 V(P_0^T r)                  (multilevel: "Multilevel mode" below - a V-cycle over bilinear node grids 8, 16, 32, ... cells apart (k_mg.hip) whose top level is the
+//     z = M_tile^-1 r + P_0 V(P_0^T r)                  (multilevel: "Multilevel mode" below - a V-cycle over bilinear node grids 8, 16, 32, ... cells apart (k_mg.hip, k_mg_cycle.hip) whose top level is the
 //                                                        dense level of the two-level mode; also on row slabs)
 //
 // M_tile = the tile-local IC(0) of k_tile.hip (64-row x 16-record blocks, one pass over memory); P = piecewise constants over coarse
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void k_mg_scatter0(const double* __restrict__ 
     if (I >= P.lo[r] && I < P.hi[r]) t = t + xbuf[(size_t)r * slot + 2 + (size_t)(I - P.lo[r]) * nx0 + J];
   rhs0[c] = t;
 }
-int eu_launch_coarse_pre(euler_sim* S, int force) { return eu_mg_slab_rows(S, force); }
+int eu_launch_coarse_pre(euler_sim* S, int force) { (void)force; return eu_mg_slab_rows(S); }
 int eu_launch_coarse_scatter(euler_sim* S) {
   MgParts P;
   P.n = S->bulk.nranks < 64 ? S->bulk.nranks : 64;

@@ -1,4 +1,4 @@
-// k_pcg.h — internal: what the files of the pressure solve share (k_pcg.hip, k_sweep.hip, k_tile.hip, k_search.hip; k_coarse.hip, k_mg.hip, k_resident.hip, k_slab.hip, k_grid.hip).
+// k_pcg.h — internal: what the files of the pressure solve share (k_pcg.hip, k_sweep.hip, k_tile.hip, k_search.hip; k_coarse.hip, k_mg.hip, k_mg_cycle.hip, k_mg_split.hip, k_resident.hip, k_slab.hip, k_grid.hip).
 //
 // HBM layout.  Every solver array (b, p, r, z, s, q, precon, cell mask) is private to the solver,
 // so it is stored BAND-SKEWED rather than row-major (struct SkewGeom, euler_dev.h):
@@ -298,7 +298,7 @@ struct TileArgs {
   double *zsend_lo, *zsend_hi;
   int edge_lo, edge_hi;
   int reverse;            // walk the tiles in descending order
-  double* cpart;          // two-level mode (k_coarse.hip): per tile, the sums of the (updated) r over its fluid cells by coarse column: [tile][3]; multilevel mode (k_mg.hip): [tile][MG_PART = 72] = [group][row slot][column slot] (k_mg.h)
+  double* cpart;          // two-level mode (k_coarse.hip): per tile, the sums of the (updated) r over its fluid cells by coarse column: [tile][3]; multilevel mode (k_mg_cycle.hip): [tile][MG_PART = 72] = [group][row slot][column slot] (k_mg.h)
   int cshift;             // two-level mode: log2 of the coarse cell width in grid cells (the multilevel mode's node spacing is the constant MG_G0: nothing reads this there)
   int cmode, cnx, cny;    // cmode 2: the multilevel mode's bilinear restriction onto cnx x cny nodes of level 0
   // RECOMP (k_precond_tile<16, true>): `as` is the search direction s' itself and the pass forms A s' from it.  On row slabs the rows across

@@ -47,7 +47,7 @@ __device__ __forceinline__ double pick3(int t, int tb1, int tb2, double v0, doub
   return v;
 }
 // STORE false: A s' is not stored (`out` is ignored) - k_precond_tile<16, true> forms it again from s' instead of reading it back
-// COARSE 2 (multilevel preconditioner, k_mg.hip): z + P_0 x_0 with P_0 bilinear from the level-0 nodes - the lane combines its two node rows once per run (four node columns
+// COARSE 2 (multilevel preconditioner, k_mg.hip; x_0 is the result of the cycle, k_mg_cycle.hip): z + P_0 x_0 with P_0 bilinear from the level-0 nodes - the lane combines its two node rows once per run (four node columns
 // cover the run and its window), every cell then interpolates along its row; the expression is mg_interp0's, so a cell gets the same bits whoever forms its s'.
 // ZR (SLAB 0, SA_RUN 8, the list of active chunks; k_pcg.h tile_z_recompute): z is formed again from r by the run's own tile solve (tile_solve, E^-1 from the
 // LDS table for interior chunks as in k_precond_tile) - the previous k_precond_tile stored only what the neighbouring tiles' z contributes (ZrArgs)

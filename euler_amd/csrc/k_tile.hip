@@ -207,7 +207,7 @@ __global__ __launch_bounds__(PT_THREADS, RECOMP ? PT_RECOMP_BLOCKS : 1) void k_p
       }
       if (!a.sweeps) return;
       if (W == 16 && CMODE == 2) {
-        // multilevel mode (k_mg.hip): P_0^T r of this tile, P_0 bilinear from the nodes at the cells (G0 J + G0 / 2, G0 I + G0 / 2), G0 = MG_G0 = 8.  The eight lanes of a GROUP
+        // multilevel mode (k_mg.hip; the sums are gathered by mg_gather0, k_mg.h): P_0^T r of this tile, P_0 bilinear from the nodes at the cells (G0 J + G0 / 2, G0 I + G0 / 2), G0 = MG_G0 = 8.  The eight lanes of a GROUP
         // (k_mg.h) lie between the same two node rows I0, I0 + 1; a lane's 16 columns between at most MG_NSEG + 1 node columns starting at Jb (its own), the group's between
         // MG_NSLOT = 4 starting at Jq.  A record's weight of the right-hand node is rec + b with b constant over a segment, so a lane accumulates sum rv and sum rec rv per
         // segment, turns them into its node-column sums, shifts them to the group's slots and multiplies by its two row weights (weights in 1 / G0)
@@ -418,7 +418,7 @@ int eu_launch_precond_tile(euler_sim* S, int rupd, int sweeps, int fin_dot, int 
   // row slabs + coarse correction: the pair and this rank's rows of the level-0 right-hand side travel in ONE slot of ONE all-gather inside the G1 exchange
   double* xsmall = S->pair_buf;
   int nsmall = 2;
-  bool split = false;      // multilevel mode: the cycle split by rows (k_mg.hip) - the edge rows of z go straight into its messages
+  bool split = false;      // multilevel mode: the cycle split by rows (k_mg_split.hip) - the edge rows of z go straight into its messages
   if (two_level && a.via == FIN_TO_COMM) {
     split = eu_is_mg(S) && ghost_mode(S) && eu_mg_split(S);
     nsmall = eu_coarse_comm_slots(S);

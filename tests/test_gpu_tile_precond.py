@@ -356,7 +356,7 @@ def test_two_level_mode_refuses_what_it_cannot_do():
 # ----------------------------------------------------------------------------- multilevel preconditioner (EULER_PRECOND_IC0_TILE_MG)
 @pytest.mark.parametrize("X,Y", [(100, 40), (260, 300), (1100, 200), (130, 1030), (1536, 1280)])
 def test_multilevel_preconditioner_matches_the_oracle_restatement(X, Y):
-    """z = M_tile^-1 r + P_0 V(P_0^T r) (k_mg.hip) against the oracle's restatement (eo_sim.coarse_mg, mg_build / mg_vcycle): level 0's
+    """z = M_tile^-1 r + P_0 V(P_0^T r) (k_mg.hip, k_mg_cycle.hip) against the oracle's restatement (eo_sim.coarse_mg, mg_build / mg_vcycle): level 0's
     stencil is an integer sum (exact), the coarser ones and the V-cycle use the oracle's formulas with sums folded in another order - agreement to rounding.  (a) budget capped at 5: pressures of the first substep to 1e-11 of max |p| (measured 2e-15..4e-13),
     residuals to 1e-9; (b) to the reference's tolerance: the same iteration counts within 3 % (measured: identical), pressures within 1e-6 of
     max |p|, identical cell grids.  Square, flat, tall; 1536 x 1280 has coarse_m = 2, i.e. three levels below the dense one."""
