@@ -52,6 +52,14 @@ FORCING_DTYPE = np.dtype({"names": ["gx", "gy", "shake_x", "shake_y", "shake_hz"
                           "formats": [np.float32] * 4 + [np.float64] * 2 + [np.int32] * 2 + [np.float64],
                           "offsets": [0, 4, 8, 12, 16, 24, 32, 36, 40], "itemsize": 48})
 FORCE_BOX_DTYPE = np.dtype({"names": ["x0", "y0", "x1", "y1", "fx", "fy"], "formats": [np.int32] * 4 + [np.float32] * 2, "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
+# euler_heat, euler_heat_box (include/euler.h): the record of euler_set_heat and one heat box; EULER_HEAT_FIX / _RATE
+HEAT_BOXES_MAX = 64
+HEAT_FIX, HEAT_RATE = 0, 1
+HEAT_DTYPE = np.dtype({"names": ["ambient", "beta", "kappa", "source_t", "nboxes", "reserved", "reserved2"],
+                       "formats": [np.float32] * 4 + [np.int32] * 2 + [np.float64], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+HEAT_PX_DTYPE = np.dtype({"names": ["cells", "water", "t_pos", "t_neg", "max_above", "max_below"], "formats": [np.uint32] * 2 + [np.uint64] * 2 + [np.float32] * 2,
+                          "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})      # euler_heat_px: one pixel of euler_heat_raster
+HEAT_BOX_DTYPE = np.dtype({"names": ["x0", "y0", "x1", "y1", "value", "kind"], "formats": [np.int32] * 4 + [np.float32, np.int32], "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
 # euler_tracer (include/euler.h): one passive tracer; EULER_TRACER_* flag bits; EULER_TRACER_RASTER_ALL of euler_tracer_raster
 TRACERS_MAX = 1 << 22
 TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER_WAS_DRY = 1, 2, 4, 8, 16, 32
@@ -125,6 +133,7 @@ EXPORTS = [
     "euler_flow_raster", "euler_flow_paint",
     "euler_gauges", "euler_gauge_derive",
     "euler_forcing_default", "euler_set_forcing", "euler_get_forcing", "euler_forcing_at", "euler_get_time", "euler_set_time",
+    "euler_heat_default", "euler_set_heat", "euler_get_heat", "euler_heat_get_field", "euler_heat_set_field", "euler_heat_fill", "euler_heat_raster", "euler_heat_paint",
     "euler_tracers_add", "euler_tracers_count", "euler_tracers_get", "euler_tracers_clear", "euler_tracer_raster", "euler_tracer_paint",
 ]
 
@@ -217,6 +226,14 @@ def load_library():
         "euler_forcing_at": (C.c_int, [vp, f64, C.POINTER(f32)]),
         "euler_get_time": (C.c_int, [vp, C.POINTER(f64)]),
         "euler_set_time": (C.c_int, [vp, f64]),
+        "euler_heat_default": (C.c_int, [vp]),
+        "euler_set_heat": (C.c_int, [vp, vp, vp]),
+        "euler_get_heat": (C.c_int, [vp, vp, vp, i32]),
+        "euler_heat_get_field": (C.c_int, [vp, vp, C.c_size_t]),
+        "euler_heat_set_field": (C.c_int, [vp, vp, C.c_size_t]),
+        "euler_heat_fill": (C.c_int, [vp, i32, i32, i32, i32, f32]),
+        "euler_heat_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_heat_paint": (C.c_int, [vp, vp, i32, i32, f32, f64]),
         "euler_tracers_add": (C.c_int, [vp, vp, C.c_size_t]),
         "euler_tracers_count": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
         "euler_tracers_get": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
@@ -389,6 +406,26 @@ def forcing_at(f, t):
     a = (C.c_float * 2)()
     _check_host(load_library().euler_forcing_at(f.ctypes.data, float(t), a), "euler_forcing_at")
     return np.float32(a[0]), np.float32(a[1])
+
+
+def heat_default():
+    """The default heat record (euler_heat_default): ambient, beta, kappa, source_t 0, no boxes; HEAT_DTYPE, shape ()."""
+    h = np.zeros((), HEAT_DTYPE)
+    _check_host(load_library().euler_heat_default(h.ctypes.data), "euler_heat_default")
+    return h
+
+
+def heat_paint(heat, px, ambient, scale):
+    """A painted copy of the overview records px: their dye sums show the mean temperature above (white to red) and below (white to blue) `ambient` of the
+    heat records of the same box, raster and state, saturated at `scale` (euler_heat_paint), so that overview_text / view_text with rainbow and
+    overview_rgb(IMAGE_DYE) draw it."""
+    px = _overview_records(px).copy()
+    heat = np.ascontiguousarray(heat, HEAT_PX_DTYPE)
+    if heat.shape != px.shape:
+        raise ValueError("heat_paint: heat records of shape %r for overview records of shape %r" % (heat.shape, px.shape))
+    h, w = px.shape
+    _check_host(load_library().euler_heat_paint(heat.ctypes.data, px.ctypes.data, w, h, float(ambient), float(scale)), "euler_heat_paint")
+    return px
 
 
 def tracer_lattice(box, k):
@@ -659,6 +696,61 @@ class Simulation:
     @time.setter
     def time(self, t):
         _check(self.L.euler_set_time(self.h, float(t)))
+
+    # --- temperature (docs/heat.md)
+    def set_heat(self, ambient=0.0, beta=0.0, kappa=0.0, source_t=0.0, boxes=()):
+        """Switch the temperature on, or replace beta, kappa, source_t and the boxes of a handle that has it (euler_set_heat, docs/heat.md): an advected scalar
+        that starts at `ambient`, expands with beta (0: passive), diffuses with kappa; boxes = a list of (kind, value, (x0, y0, x1, y1)) - kind HEAT_FIX or
+        HEAT_RATE - or an array of HEAT_BOX_DTYPE, applied to the fluid cells in list order."""
+        if isinstance(boxes, np.ndarray) and boxes.dtype == HEAT_BOX_DTYPE:
+            b = np.ascontiguousarray(boxes).reshape(-1)
+        else:
+            b = np.zeros(len(boxes), HEAT_BOX_DTYPE)
+            for k, (kind, value, box) in enumerate(boxes):
+                b[k] = tuple(int(t) for t in box) + (float(value), int(kind))
+        h = heat_default()
+        h["ambient"], h["beta"], h["kappa"], h["source_t"], h["nboxes"] = ambient, beta, kappa, source_t, len(b)
+        _check(self.L.euler_set_heat(self.h, h.ctypes.data, b.ctypes.data if b.size else None))
+        return self
+
+    def heat_off(self):
+        """Switch the temperature off (euler_set_heat with a null record): the handle launches what it launched before."""
+        _check(self.L.euler_set_heat(self.h, None, None))
+        return self
+
+    def heat(self):
+        """(record, boxes) as set (euler_get_heat): HEAT_DTYPE of shape () and an array of HEAT_BOX_DTYPE."""
+        h = np.zeros((), HEAT_DTYPE)
+        b = np.zeros(HEAT_BOXES_MAX, HEAT_BOX_DTYPE)
+        _check(self.L.euler_get_heat(self.h, h.ctypes.data, b.ctypes.data, HEAT_BOXES_MAX))
+        return h, b[: int(h["nboxes"])].copy()
+
+    @property
+    def temperature(self):
+        """The temperature field, float32 of shape (Y, X) (euler_heat_get_field): cells without markers hold ambient."""
+        t = np.zeros((self.Y, self.X), np.float32)
+        _check(self.L.euler_heat_get_field(self.h, t.ctypes.data, t.nbytes))
+        return t
+
+    @temperature.setter
+    def temperature(self, t):
+        a = np.ascontiguousarray(t, np.float32)
+        _check(self.L.euler_heat_set_field(self.h, a.ctypes.data, a.nbytes))
+
+    def heat_fill(self, box, value):
+        """T = value in the cells of box = (x0, y0, x1, y1), inclusive, that hold markers, now (euler_heat_fill)."""
+        x0, y0, x1, y1 = (int(t) for t in box)
+        _check(self.L.euler_heat_fill(self.h, x0, y0, x1, y1, float(value)))
+        return self
+
+    def heat_raster(self, w, h, box=None):
+        """The temperature of the whole interior, or of box = (x0, y0, x1, y1) inclusive, over the pixels of overview(w, h, box) (euler_heat_raster): signed
+        sums of T - ambient over the water cells with their maxima: an array of HEAT_PX_DTYPE, shape (h, w), row 0 = top."""
+        x0, y0, x1, y1 = (1, 1, self.X - 2, self.Y - 2) if box is None else (int(t) for t in box)
+        px = np.zeros((max(int(h), 0), max(int(w), 0)), HEAT_PX_DTYPE)
+        dst = px.ctypes.data if px.size else np.zeros(1, HEAT_PX_DTYPE).ctypes.data
+        _check(self.L.euler_heat_raster(self.h, x0, y0, x1, y1, w, h, dst, px.nbytes))
+        return px
 
     # --- passive tracers (docs/tracers.md)
     def add_tracers(self, xy):

@@ -36,6 +36,12 @@
  * velocity from blue (0) to red (S and above); the images are then written in the dye mode.  The pressure is reduced only for pressure:.  It needs --fit, --view
  * or --ppm: on its own it is a usage error.  With --view, and only with it, the key v cycles unpainted -> vorticity -> pressure -> speed at the scales given
  * or the defaults 1, 1000 and 10.
+ * --heat AMBIENT:BETA[:KAPPA] switches the temperature on (euler_set_heat, docs/heat.md), set once behind the load and the forcing: the water starts at AMBIENT,
+ * expands with BETA, diffuses with KAPPA (0 ... 2.5).  --heat-source T is what the scenario's source cells hold; --heat-box fix|rate:VALUE:X0,Y0,X1,Y1 (up to 64
+ * times, in command-line order) holds the water of a box at VALUE or changes it at VALUE per second; --heat-init VALUE:X0,Y0,X1,Y1 (repeatable) sets the water of a
+ * box to VALUE before frame 0 (euler_heat_fill).  --paint heat:S colours by the mean temperature of a pixel, from blue (AMBIENT - S) over white to red
+ * (AMBIENT + S) (euler_heat_raster + euler_heat_paint); the key v does not cycle through it.  A malformed spec, a 65th box, a value out of range, a box
+ * outside the interior, and --heat-source, --heat-box, --heat-init or --paint heat: without --heat are usage errors.  Without --heat every byte is as before.
  * --stats writes FILE (created or truncated) as CSV: a header line, then one line after every N-th frame (default 1; frame 0 included) with the frame's
  * solver figures (euler_get_stats) and the flow diagnostics of the whole interior (euler_diagnostics + euler_diag_derive, docs/diagnostics.md).
  * --gauge (up to 64 times) places an instrument on the box of interior cells [X0, X1] x [Y0, Y1]: level (extent of the fluid), pressure, force (on the solid
@@ -69,13 +75,14 @@
 #include "euler.h"
 #include "cli_gauges.h"
 #include "cli_forcing.h"
+#include "cli_heat.h"
 #include "cli_tracers.h"
 #include "euler_host.h"      /* eu_tracer_lattice */
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -122,6 +129,17 @@ static int window_size(int* wx, int* wy) {
 /* --paint: the field of the flow raster over the box (NULL: the whole interior of xi x yi cells) and raster of the records px, painted into their dye sums */
 static int paint_records(euler_sim* sim, const int* box, int xi, int yi, euler_overview_px* px, int W, int H, int field, double scale) {
   const size_t n = (size_t)W * (size_t)H;
+  if (field == CLI_PAINT_HEAT) {      /* the temperature's raster and painter (docs/heat.md) */
+    euler_heat h;
+    euler_heat_px* hp = (euler_heat_px*)malloc(n * sizeof *hp);
+    if (!hp) { fprintf(stderr, "--paint: out of memory\n"); return -1; }
+    int rh = euler_get_heat(sim, &h, NULL, 0);
+    if (rh == EULER_OK) rh = euler_heat_raster(sim, box ? box[0] : 1, box ? box[1] : 1, box ? box[2] : xi, box ? box[3] : yi, W, H, hp, n * sizeof *hp);
+    if (rh != EULER_OK) fprintf(stderr, "%s\n", euler_last_error());
+    else if ((rh = euler_heat_paint(hp, px, W, H, h.ambient, scale)) != EULER_OK) fprintf(stderr, "--paint: the heat records do not match the overview's\n");
+    free(hp);
+    return rh == EULER_OK ? 0 : -1;
+  }
   euler_flow_px* fl = (euler_flow_px*)malloc(n * sizeof *fl);
   if (!fl) { fprintf(stderr, "--paint: out of memory\n"); return -1; }
   int rc = euler_flow_raster(sim, box ? box[0] : 1, box ? box[1] : 1, box ? box[2] : xi, box ? box[3] : yi, W, H, field == EULER_PAINT_PRESSURE ? EULER_FLOW_PRESSURE : 0, fl, n * sizeof *fl);
@@ -264,15 +282,15 @@ typedef struct app {
   int xi, yi;                   /* the interior: X - 2, Y - 2 */
   int failed;                   /* a brush key's edit was refused */
   int paint;                    /* --paint / the key v: -1 unpainted, else EULER_PAINT_* */
-  double paint_scale[3];        /* the scale of each field: the one given, else 1, 1000, 10 */
+  double paint_scale[4];        /* the scale of each field: the one given, else 1, 1000, 10; [CLI_PAINT_HEAT]: 10 */
   int show;                     /* --tracers-show / the key t: the pixels that hold a live tracer are painted */
 } app_t;
 
 /* ---- --paint: the frame of --fit / --view with the flow field in place of the dye (docs/flow_raster.md) ----------------------------------- */
 static int parse_paint(const char* arg, int* field, double* scale) {
-  static const char* const fmt[3] = {"vorticity:%lf%c", "pressure:%lf%c", "speed:%lf%c"};      /* EULER_PAINT_* in their order */
+  static const char* const fmt[4] = {"vorticity:%lf%c", "pressure:%lf%c", "speed:%lf%c", "heat:%lf%c"};      /* EULER_PAINT_* in their order, then CLI_PAINT_HEAT */
   char tail;
-  for (*field = 0; *field < 3; ++*field)
+  for (*field = 0; *field < 4; ++*field)
     if (sscanf(arg, fmt[*field], scale, &tail) == 1) return *scale > 0.0 && *scale <= 1.7976931348623157e308 ? 0 : -1;
   return -1;
 }
@@ -344,7 +362,7 @@ static void view_key(app_t* a, char c) {
     zoom_axis(&b[0], &b[2], a->xi, 2 * bw < a->xi ? 2 * bw : a->xi);
     zoom_axis(&b[1], &b[3], a->yi, 2 * bh < a->yi ? 2 * bh : a->yi);
   } else if (c == '0') { b[0] = 1; b[1] = 1; b[2] = a->xi; b[3] = a->yi; }
-  else if (c == 'v') a->paint = a->paint == EULER_PAINT_SPEED ? -1 : a->paint + 1;      /* unpainted -> vorticity -> pressure -> speed -> unpainted */
+  else if (c == 'v') a->paint = a->paint >= EULER_PAINT_SPEED ? -1 : a->paint + 1;      /* unpainted -> vorticity -> pressure -> speed -> unpainted */
   else if (c == 't') a->show = !a->show;
   else if (c && strchr("XCSOWD", c)) {      /* the brush: the box shrunk about its centre to a quarter of its sides */
     static const int ops[6] = {EULER_EDIT_SOLID, EULER_EDIT_CLEAR, EULER_EDIT_SINK, EULER_EDIT_SOURCE, EULER_EDIT_FILL, EULER_EDIT_DRAIN};
@@ -392,7 +410,12 @@ int main(int argc, char** argv) {
   edit_t edits[MAX_EDITS];
   int n_edits = 0;
   int paint = -1;
-  double paint_scale[3] = {1.0, 1000.0, 10.0};
+  double paint_scale[4] = {1.0, 1000.0, 10.0, 10.0};
+  euler_heat heat;
+  euler_heat_box heat_boxes[MAX_HEAT_BOXES];
+  cli_heat_init heat_inits[MAX_HEAT_INITS];
+  int heat_given = 0, heat_extra = 0, n_heat_boxes = 0, n_heat_inits = 0;
+  euler_heat_default(&heat);
   euler_forcing forcing;
   euler_force_box force_boxes[MAX_FORCE_BOXES];
   int forcing_given = 0, n_force_boxes = 0;
@@ -472,6 +495,11 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--gravity") && i + 1 < argc) { if (parse_gravity(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--shake") && i + 1 < argc) { if (parse_shake(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--force") && i + 1 < argc) { if (n_force_boxes == MAX_FORCE_BOXES || parse_force(argv[++i], &force_boxes[n_force_boxes++]) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
+    /* temperature: the record, the source cells' value, heat boxes in command-line order, fills of the start (docs/heat.md) */
+    else if (!strcmp(argv[i], "--heat") && i + 1 < argc) { if (parse_heat(argv[++i], &heat) != 0) { usage(argv[0]); return 1; } heat_given = 1; }
+    else if (!strcmp(argv[i], "--heat-source") && i + 1 < argc) { if (parse_heat_source(argv[++i], &heat.source_t) != 0) { usage(argv[0]); return 1; } heat_extra = 1; }
+    else if (!strcmp(argv[i], "--heat-box") && i + 1 < argc) { if (n_heat_boxes == MAX_HEAT_BOXES || parse_heat_box(argv[++i], &heat_boxes[n_heat_boxes++]) != 0) { usage(argv[0]); return 1; } heat_extra = 1; }
+    else if (!strcmp(argv[i], "--heat-init") && i + 1 < argc) { if (n_heat_inits == MAX_HEAT_INITS || parse_heat_init(argv[++i], &heat_inits[n_heat_inits++]) != 0) { usage(argv[0]); return 1; } heat_extra = 1; }
     /* passive tracers: points, lattices, emitters, the CSV and the painting (docs/tracers.md) */
     else if (!strcmp(argv[i], "--tracer") && i + 1 < argc) { if (n_points++ == MAX_CLI_TRACERS || parse_tracer(argv[++i], &seeds[n_seeds++]) != 0) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--tracer-box") && i + 1 < argc) { if (n_tboxes++ == MAX_TRACER_BOXES || parse_tracer_box(argv[++i], &seeds[n_seeds++]) != 0) { usage(argv[0]); return 1; } }
@@ -501,6 +529,16 @@ int main(int argc, char** argv) {
     if (fb->x0 < 1 || fb->y0 < 1 || fb->x1 > cfg.X - 2 || fb->y1 > cfg.Y - 2 || fb->x0 > fb->x1 || fb->y0 > fb->y1) { usage(argv[0]); return 1; }
   }
   forcing.nboxes = n_force_boxes;
+  if (!heat_given && (heat_extra || paint == CLI_PAINT_HEAT)) { usage(argv[0]); return 1; }      /* --heat-source, --heat-box, --heat-init, --paint heat: only with --heat */
+  for (int k = 0; k < n_heat_boxes; ++k) {
+    const euler_heat_box* hb = &heat_boxes[k];
+    if (hb->x0 < 1 || hb->y0 < 1 || hb->x1 > cfg.X - 2 || hb->y1 > cfg.Y - 2 || hb->x0 > hb->x1 || hb->y0 > hb->y1) { usage(argv[0]); return 1; }
+  }
+  for (int k = 0; k < n_heat_inits; ++k) {
+    const int* ib = heat_inits[k].box;
+    if (ib[0] < 1 || ib[1] < 1 || ib[2] > cfg.X - 2 || ib[3] > cfg.Y - 2 || ib[0] > ib[2] || ib[1] > ib[3]) { usage(argv[0]); return 1; }
+  }
+  heat.nboxes = n_heat_boxes;
   for (int k = 0; k < n_seeds; ++k) {
     const int* tb = seeds[k].box;
     if (seeds[k].k ? (tb[0] < 1 || tb[1] < 1 || tb[2] > cfg.X - 2 || tb[3] > cfg.Y - 2 || tb[0] > tb[2] || tb[1] > tb[3]) : !cli_tracer_inside(seeds[k].x, seeds[k].y, cfg.X, cfg.Y)) { usage(argv[0]); return 1; }
@@ -543,10 +581,16 @@ int main(int argc, char** argv) {
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
-      (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK)) {
+      (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK) ||
+      (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK)) {      /* (behind the load and the forcing) */
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }
+  for (int k = 0; k < n_heat_inits; ++k)
+    if (euler_heat_fill(app.sim, heat_inits[k].box[0], heat_inits[k].box[1], heat_inits[k].box[2], heat_inits[k].box[3], heat_inits[k].value) != EULER_OK) {
+      fprintf(stderr, "%s\n", euler_last_error());
+      return 1;
+    }
   if (add_seeds(app.sim, seeds, n_seeds) != 0) return 1;
   if (interactive) {
     if (enable_raw_mode() == -1) { perror("failed to enable raw mode"); return 1; }

@@ -275,7 +275,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   eu_rccl_release(S);
   eu_slab_release(S);
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf}) eu_devbuf_release(S, b);
+  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf, &S->heat_buf, &S->heat_box_buf, &S->heat_fill_buf, &S->heat_ras_buf}) eu_devbuf_release(S, b);
   // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
   // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
   const size_t wo = S->shifted ? S->win_off : 0;
@@ -610,6 +610,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   memset(&S->stats, 0, sizeof(S->stats));
   S->time = 0.0;      // (the forcing stays as set: docs/forcing.md)
   S->n_tracers = 0;   // (the tracers belonged to the run that was replaced: docs/tracers.md)
+  if ((rc = eu_heat_reset(S))) return rc;      // (the heat record stays as set, the field starts from ambient: docs/heat.md)
   S->loaded = 1;
   return EULER_OK;
 }
@@ -779,6 +780,7 @@ static int run_stage(euler_sim* S, int stage, float dt) {
       int rc = eu_launch_dye_extrapolate(S);
       if (!rc) rc = eu_launch_sources(S);
       if (!rc) rc = eu_launch_dye_sources(S);
+      if (!rc && S->heat_on) rc = eu_launch_heat_sources(S);      // the temperature's extension and its source cells (k_heat.hip)
       return rc;
     }
     case EULER_STAGE_EXTRAPOLATE: return eu_launch_extrapolate(S);

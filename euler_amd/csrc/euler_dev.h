@@ -169,6 +169,14 @@ struct euler_sim {
   // and the raster of euler_tracer_raster
   eu_devbuf tracer_buf, tracer_ras_buf;
   size_t n_tracers;
+  // euler_set_heat (k_heat.hip, docs/heat.md): the record and the boxes as set, whether heat is on, and on the device the field with its scratch copy (heat_buf, 2 C
+  // floats: the passes that write every cell go from one half to the other, heat_cur says which half holds T), the boxes with their tile table (heat_box_buf;
+  // uploaded once per euler_set_heat) and the one-box list of euler_heat_fill (heat_fill_buf)
+  euler_heat heat;
+  euler_heat_box heat_boxes[EULER_HEAT_BOXES_MAX];
+  int heat_on, heat_cur;
+  unsigned int heat_ntiles;
+  eu_devbuf heat_buf, heat_box_buf, heat_fill_buf, heat_ras_buf;      // (heat_ras_buf: the records of euler_heat_raster)
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -390,6 +398,12 @@ int eu_resident_capacity(euler_sim* S, int f32);            // k_resident.hip: w
 int eu_launch_resident(euler_sim* S, unsigned int n_chunks);
 bool eu_resident_eligible(const euler_sim* S);               // driver.hip: this handle's configuration and grid allow the resident solver
 int eu_launch_colorize(euler_sim* S);            // k_dye.hip: no-ops without cfg.rainbow
+// k_heat.hip (euler_set_heat; callers test S->heat_on): the extension and the sources in EULER_STAGE_SOURCES; transport, boxes, diffusion and buoyancy inside
+// eu_launch_advect_velocity behind the force boxes (acc: the substep's uniform acceleration); the field back to ambient behind a load
+int eu_launch_heat_sources(euler_sim* S);
+int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]);
+int eu_heat_reset(euler_sim* S);
+int eu_heat_dry(euler_sim* S);      // behind an edit (k_edit.hip): the cells it emptied take ambient, so that the invariant holds between substeps too
 int eu_launch_dye_extrapolate(euler_sim* S);
 int eu_launch_dye_sources(euler_sim* S);
 int eu_launch_dye_advect(euler_sim* S, float dt);

@@ -452,6 +452,25 @@ int euler_flow_paint(const euler_flow_px* flow, euler_overview_px* px, int32_t W
   return EULER_OK;
 }
 
+/* the temperature's painter: the vorticity field's white - red - blue mapping over the mean difference from ambient (include/euler.h, docs/heat.md) */
+int euler_heat_paint(const euler_heat_px* heat, euler_overview_px* px, int32_t W, int32_t H, float ambient, double scale) {
+  if (!heat || !px || W < 1 || H < 1) return EULER_EINVAL;
+  if (!(scale > 0.0) || !isfinite(scale) || !isfinite(ambient)) return EULER_EINVAL;
+  const size_t n = (size_t)W * (size_t)H;
+  for (size_t k = 0; k < n; ++k)      /* the two rasters are of one box, raster and state */
+    if (heat[k].cells != px[k].cells || heat[k].water != px[k].water) return EULER_EINVAL;
+  for (size_t k = 0; k < n; ++k) {
+    const euler_heat_px* f = heat + k;
+    const double m = f->water ? ((double)f->t_pos - (double)f->t_neg) / 1048576.0 / (double)f->water : 0.0;
+    const double t = paint_clamp(m / scale, -1.0);
+    double lin[3];
+    if (t >= 0.0) { lin[0] = 1.0; lin[1] = 1.0 - t; lin[2] = 1.0 - t; }
+    else { lin[0] = 1.0 + t; lin[1] = 1.0 + t; lin[2] = 1.0; }
+    for (int c = 0; c < 3; ++c) px[k].dye[c] = (uint64_t)f->water * paint_q24((float)lin[c]);
+  }
+  return EULER_OK;
+}
+
 /* ---- batched gauges: the list checked, cut into chunks, and the values read off a record (include/euler.h, docs/gauges.md) ---- */
 
 int eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what) {
@@ -728,6 +747,54 @@ size_t eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y,
       ++m;
     }
   free(set);
+  return m;
+}
+
+/* ---- temperature: the record's defaults, the record and the list checked, the list cut into the force boxes' tile table (include/euler.h, docs/heat.md) ---- */
+
+int euler_heat_default(euler_heat* h) {
+  if (!h) return EULER_EINVAL;
+  memset(h, 0, sizeof *h);
+  return EULER_OK;
+}
+
+int eu_heat_value_ok(float x) { return force_value_ok(x); }
+
+int eu_heat_box_check(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y, char* why, size_t cap) {
+  if (x0 < 1 || y0 < 1 || x1 > X - 2 || y1 > Y - 2 || x0 > x1 || y0 > y1) {
+    if (why && cap) snprintf(why, cap, "[%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", x0, x1, y0, y1, X - 2, Y - 2);
+    return EULER_EINVAL;
+  }
+  return EULER_OK;
+}
+
+int eu_heat_check(const euler_heat* h, const euler_heat_box* boxes, int32_t X, int32_t Y, const float* live, char* why, size_t cap) {
+#define REFUSE(...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return EULER_EINVAL; } while (0)
+  if (h->reserved != 0 || h->reserved2 != 0.0) REFUSE("reserved and reserved2 must be 0");
+  if (!isfinite(h->kappa) || !force_value_ok(h->ambient) || !force_value_ok(h->beta) || !force_value_ok(h->source_t))
+    REFUSE("ambient %g, beta %g and source_t %g must be finite and at most 1e4 in size, kappa %g finite", (double)h->ambient, (double)h->beta, (double)h->source_t, (double)h->kappa);
+  if (!(h->kappa >= 0.f && h->kappa <= 2.5f)) REFUSE("kappa %g is outside [0, 2.5]", (double)h->kappa);
+  if (live && !(h->ambient == *live)) REFUSE("ambient %g is not the live one, %g (the cells without markers hold it)", (double)h->ambient, (double)*live);
+  if (h->nboxes < 0 || h->nboxes > EULER_HEAT_BOXES_MAX) REFUSE("%d boxes (0 ... %d)", h->nboxes, EULER_HEAT_BOXES_MAX);
+  if (h->nboxes > 0 && !boxes) REFUSE("%d boxes and a null list", h->nboxes);
+  for (int32_t k = 0; k < h->nboxes; ++k) {      /* the first box that fails any of its tests */
+    const euler_heat_box* b = boxes + k;
+    char place[160];
+    if (b->kind != EULER_HEAT_FIX && b->kind != EULER_HEAT_RATE) REFUSE("box %d: kind %d is neither EULER_HEAT_FIX nor EULER_HEAT_RATE", k, b->kind);
+    if (!force_value_ok(b->value)) REFUSE("box %d: value %g must be finite and at most 1e4 in size", k, (double)b->value);
+    if (eu_heat_box_check(b->x0, b->y0, b->x1, b->y1, X, Y, place, sizeof place)) REFUSE("box %d: %s", k, place);
+  }
+#undef REFUSE
+  return EULER_OK;
+}
+
+size_t eu_heat_tiles(const euler_heat_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
+  if (n < 1) return 0;
+  euler_force_box* fb = (euler_force_box*)calloc((size_t)n, sizeof *fb);
+  if (!fb) return (size_t)-1;
+  for (int32_t k = 0; k < n; ++k) { fb[k].x0 = b[k].x0; fb[k].y0 = b[k].y0; fb[k].x1 = b[k].x1; fb[k].y1 = b[k].y1; }
+  const size_t m = eu_force_tiles(fb, n, X, Y, out);
+  free(fb);
   return m;
 }
 

@@ -47,6 +47,13 @@ int      eu_slab_plan_contributors(const eu_slab_plan* P, int32_t py, int32_t* f
 typedef struct eu_force_tile { int32_t tx, ty; uint64_t boxes; } eu_force_tile;
 int      eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
 size_t   eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);   /* out == NULL: the count only; the list must have passed eu_forcing_check; (size_t)-1: no memory */
+/* euler_set_heat (k_heat.hip, docs/heat.md): refusals 4 - 9 of include/euler.h in their order - the ones that need no device; live: the ambient of a handle whose
+ * heat is on (NULL: off, any ambient passes).  The tile table of the heat boxes is the force boxes': eu_heat_tiles hands the boxes' places to eu_force_tiles */
+int      eu_heat_check(const euler_heat* h, const euler_heat_box* boxes, int32_t X, int32_t Y, const float* live, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
+size_t   eu_heat_tiles(const euler_heat_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);   /* as eu_force_tiles */
+/* the refusals of euler_heat_fill / euler_heat_set_field that need no device: the box, the value */
+int      eu_heat_box_check(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y, char* why, size_t cap);
+int      eu_heat_value_ok(float x);   /* finite and at most 1e4 in size */
 /* passive tracers (k_tracers.hip, docs/tracers.md): the refusals of euler_tracers_add that need no device, in its order - n > 0 with a null xy, count + n >
  * EULER_TRACERS_MAX, a position that is not finite or outside 1 <= x < X - 1, 1 <= y < Y - 1 (the first such index is named) */
 int      eu_tracers_check(const float* xy, size_t n, size_t count, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */

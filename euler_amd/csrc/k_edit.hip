@@ -211,6 +211,7 @@ static int ed_run(euler_sim* S, int op, const EdBox& b) {
     const size_t src_new = S->n_source_cells - (size_t)src_old + (op == EULER_EDIT_SOURCE ? (size_t)Bw * b.Bh : 0);
     if (src_new != S->n_source_cells && (rc = eu_set_source_count(S, src_new))) return rc;
   }
+  if (S->heat_on && (rc = eu_heat_dry(S))) return rc;      // (the temperature of the cells the edit emptied: ambient, as in every cell without markers - docs/heat.md)
   return eu_sync_marker_state(S);      // the host's marker count is in step again
 }
 

@@ -479,6 +479,8 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
     LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
   // the force boxes (k_forcing.hip): live faces of utmp / vtmp only, so what the advection leaves for the next pass stands as it is (docs/stage_validity.md)
   if (S->forcing.nboxes > 0) { int rc = eu_launch_force_boxes(S, dt); if (rc) return rc; }
+  // the temperature (k_heat.hip): its transport reads u, v before the diffusion extension takes them as scratch; its buoyancy acts on live faces of utmp / vtmp only
+  if (S->heat_on) { int rc = eu_launch_heat_advect(S, dt, acc); if (rc) return rc; }
   eu_vd_advected_velocity(&S->vd, S->cfg.viscosity > 0.f);      // (the diffusion extension writes utmp / vtmp behind this, with u, v as its scratch)
   // (a row-slab handle exchanges the ghost rows of utmp / vtmp between the two: eu_slab_substep calls eu_launch_diffuse itself)
   return S->slab_on ? EULER_OK : eu_launch_diffuse(S, dt);

@@ -584,6 +584,76 @@ int euler_forcing_at(const euler_forcing* f, double t, float a[2]);   /* host on
 int euler_get_time(euler_sim* sim, double* t);
 int euler_set_time(euler_sim* sim, double t);   /* EULER_EINVAL: a non-finite t */
 
+/* ---- temperature: an advected scalar with buoyancy, heaters and diffusion (docs/heat.md) ----------- */
+/* An ACTIVE scalar T, one float per cell, cell-centred like the dye: the flow carries it, boxes heat or cool it, it diffuses, and (Boussinesq) it makes water
+ * lighter or heavier.  A cell is fluid when its marker count is not 0.  INVARIANT: behind euler_set_heat, euler_heat_set_field, euler_heat_fill and every
+ * completed substep every cell without markers holds exactly `ambient`, in memory and in what euler_heat_get_field returns - so the field does not depend on
+ * launch geometry or the tile map, and water that euler_edit_box(FILL) adds starts at `ambient`.  Whole-grid handles only.  Per substep, float32 without
+ * contraction (docs/heat.md has every operation):
+ *   EULER_STAGE_SOURCES, behind the dye's work: a cell with prev_count == 0 && count != 0 takes the mean of its 3 x 3 neighbours with prev_count != 0, summed
+ *     y-major then x and divided by their number n; n == 0: `ambient`.  Then every cell with source != 0 takes source_t, whatever its count.
+ *   EULER_STAGE_ADVECT_VELOCITY, behind the velocity advection, its uniform forcing and the force boxes, in front of the viscosity extension:
+ *     a. T moves as one dye channel under the handle's transport options (reading the stage's input u, v); only fluid cells take the result.
+ *     b. for k = 0 .. nboxes - 1 in list order, every fluid cell of box k: FIX: T = value; RATE: T = fl(T + fl(value dt)).
+ *     c. kappa > 0: Jacobi from b's values, c = fl(kappa dt), T' = fl(T + fl(c acc)), acc = 0 then acc = fl(acc + fl(T_n - T)) for the left, right, lower and
+ *        upper neighbour in that order where that neighbour is fluid (solids and air are insulated).
+ *     d. cells without markers take `ambient`.
+ *     e. beta != 0, (ax, ay) the substep's uniform acceleration ((0, -10) or euler_forcing_at at the handle's clock): a live v face i (live as for the force
+ *        boxes) has Tf = fl(fl(T[i] + T[i+X]) / 2) when both cells are fluid, else the fluid cell's T; d = fl(Tf - ambient); d == 0: the face is not touched;
+ *        else vtmp[i] = fl(vtmp[i] - fl(fl(beta d) fl(ay dt))).  A live u face likewise with i + 1, ax and utmp, and only when ax != 0.  Faces that are not
+ *        live are neither read nor written.
+ * With beta == 0 the heat changes no bit of u, v, markers, counts, RNG or dye.  With any beta a field that is `ambient` everywhere changes none of them
+ * either WHERE THE TRANSPORT REPRODUCES THE CONSTANT: fl(fl(fl(1 - f) a) + fl(f a)) is a again for a = 0 and for a power of two, not for every float - with
+ * ambient = 20, say, a transported cell can come out one ulp off and the buoyancy acts on that ulp (docs/heat.md).  Choose such an ambient where this matters.  A handle that never calls
+ * euler_set_heat launches what it always launched.  Heat is no part of a snapshot: a scenario load and euler_load_state keep the record and reset the field
+ * to `ambient`. */
+#define EULER_HEAT_BOXES_MAX 64
+enum { EULER_HEAT_FIX = 0, EULER_HEAT_RATE = 1 };
+typedef struct euler_heat_box { int32_t x0, y0, x1, y1; float value; int32_t kind; } euler_heat_box;   /* 24 bytes; inclusive, inside [1, X-2] x [1, Y-2] */
+typedef struct euler_heat {        /* 32 bytes, no padding */
+  float   ambient;                 /* T0: the temperature of water nobody heated, and of every cell without markers; default 0 */
+  float   beta;                    /* expansion coefficient; 0 = a passive scalar; default 0 */
+  float   kappa;                   /* diffusivity, 0 <= kappa <= 2.5 (kappa dt / h^2 <= 0.25 for every dt <= the 0.1 s frame, h = 1); default 0 */
+  float   source_t;                /* what the scenario's source cells hold; default 0 */
+  int32_t nboxes, reserved;        /* reserved must be 0 */
+  double  reserved2;               /* must be 0 */
+} euler_heat;
+int euler_heat_default(euler_heat* h);
+/* h == NULL switches heat off: the handle launches what it launched before and keeps its buffers; the next switching-on starts from `ambient` everywhere.
+ * The first call with a record reserves the arrays (device buffers of the handle, counted in euler_hbm_bytes, grow-only, released by euler_destroy) and sets
+ * every cell to `ambient`; a later one replaces beta, kappa, source_t and the boxes and keeps the field.  Refusals, in this order: a null sim
+ * (EULER_EINVAL); a row-slab handle (EULER_ESTATE); nothing loaded (EULER_ESTATE); then EULER_EINVAL for: reserved or reserved2 not 0; a non-finite value or
+ * |ambient|, |beta|, |source_t| > 1e4; kappa outside [0, 2.5]; another ambient than the live one (the dry cells hold it); nboxes outside
+ * [0, EULER_HEAT_BOXES_MAX] or boxes == NULL with nboxes > 0; a box with an unknown kind, a non-finite value or |value| > 1e4, outside the interior or
+ * inverted, naming the first such box.  A refused call changes and allocates nothing. */
+int euler_set_heat(euler_sim* sim, const euler_heat* h, const euler_heat_box* boxes);
+int euler_get_heat(euler_sim* sim, euler_heat* h, euler_heat_box* boxes, int32_t cap);   /* EULER_ESTATE while heat is off; boxes may be NULL, else cap >= nboxes */
+/* The field, X * Y floats, row-major.  Refused: a null argument (EULER_EINVAL), a row-slab handle, nothing loaded or heat off (EULER_ESTATE), another byte
+ * count, a box outside the interior or inverted, a value that is not finite or beyond 1e4 in size (EULER_EINVAL).  euler_heat_set_field writes `ambient`
+ * over what the caller gave for cells without markers; euler_heat_fill sets T = value in the cells of the box that hold markers, now. */
+int euler_heat_get_field(euler_sim* sim, float* dst, size_t bytes);
+int euler_heat_set_field(euler_sim* sim, const float* src, size_t bytes);
+int euler_heat_fill(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, float value);
+/* The temperature per pixel: the box, the raster, the pixel edges and the definition of water (solid == 0 && sink == 0 && count != 0) are
+ * euler_overview_box's.  d = T - ambient of a water cell goes to the sum of its sign - t_pos += qv(d) for d >= 0 (-0.f too), t_neg += qv(-d) for d < 0,
+ * qv the flow raster's: min(a, 4096) * 2^20, truncated - and to the maximum of its side, taken on bit patterns; a NaN goes to neither (the cell still counts
+ * as water), an infinity is the clamp's 4096 in the sums and itself in the maxima.  Integer sums and bit-pattern maxima: the record does not depend on the
+ * launch geometry.  Refusals: a null argument (EULER_EINVAL), a row-slab handle, nothing loaded or heat off (EULER_ESTATE), a box outside the interior, W or
+ * H < 1 or above the box's extent, another byte count than W * H records (EULER_EINVAL).  Reads the state only. */
+typedef struct euler_heat_px {       /* 32 bytes */
+  uint32_t cells;                    /* cells of the pixel */
+  uint32_t water;                    /* water cells of the pixel */
+  uint64_t t_pos, t_neg;             /* the sums of qv(d) over water cells with d >= 0, and of qv(-d) over those with d < 0 */
+  float    max_above, max_below;     /* the maxima of d and of -d where positive; 0 where there is none */
+} euler_heat_px;
+int euler_heat_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H, euler_heat_px* out, size_t out_bytes);
+/* Host only, no GPU: paints heat records into the dye sums of overview records of the same box, raster and state, as euler_flow_paint paints the
+ * vorticity: m = (t_pos - t_neg) / 2^20 / water (0 without water), t = clamp(m / scale, -1, 1); t >= 0: (1, 1 - t, 1 - t), white to red; t < 0:
+ * (1 + t, 1 + t, 1), white to blue; dye[c] = water * q(colour[c]).  Only px[k].dye is written.  EULER_EINVAL with px unchanged: a null heat or px, W or
+ * H < 1, a scale that is not finite and positive, records whose cells or water differ from px's.  (`ambient` is the raster's own: the records hold
+ * differences; the argument is kept for callers that label a legend and must be finite.) */
+int euler_heat_paint(const euler_heat_px* heat, euler_overview_px* px, int32_t W, int32_t H, float ambient, double scale);
+
 /* ---- passive tracers: device-side pathlines, streaklines and a raster (docs/tracers.md) ------------ */
 /* Where does this water go, how long does it stay, does it ever reach that corner?  A set of TRACERS lives on the device and moves with the flow by the
  * marker's own rule; the fluid's markers cannot answer (their array order changes with every deletion, their dt is shortened by earlier markers'
