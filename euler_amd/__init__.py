@@ -60,6 +60,12 @@ HEAT_DTYPE = np.dtype({"names": ["ambient", "beta", "kappa", "source_t", "nboxes
 HEAT_PX_DTYPE = np.dtype({"names": ["cells", "water", "t_pos", "t_neg", "max_above", "max_below"], "formats": [np.uint32] * 2 + [np.uint64] * 2 + [np.float32] * 2,
                           "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})      # euler_heat_px: one pixel of euler_heat_raster
 HEAT_BOX_DTYPE = np.dtype({"names": ["x0", "y0", "x1", "y1", "value", "kind"], "formats": [np.int32] * 4 + [np.float32, np.int32], "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})
+# euler_body, euler_body_state (include/euler.h): one moving body of euler_set_bodies and its position at a time
+BODIES_MAX = 16
+BODY_DTYPE = np.dtype({"names": ["x", "y", "hz", "phase", "vx", "vy", "amp_x", "amp_y", "w", "h", "reserved"],
+                       "formats": [np.float64] * 4 + [np.float32] * 4 + [np.int32] * 2 + [(np.int32, 2)],
+                       "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 48, 52, 56], "itemsize": 64})
+BODY_STATE_DTYPE = np.dtype({"names": ["px", "py", "ox", "oy"], "formats": [np.float64] * 2 + [np.int32] * 2, "offsets": [0, 8, 16, 20], "itemsize": 24})
 # euler_tracer (include/euler.h): one passive tracer; EULER_TRACER_* flag bits; EULER_TRACER_RASTER_ALL of euler_tracer_raster
 TRACERS_MAX = 1 << 22
 TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER_WAS_DRY = 1, 2, 4, 8, 16, 32
@@ -134,6 +140,7 @@ EXPORTS = [
     "euler_gauges", "euler_gauge_derive",
     "euler_forcing_default", "euler_set_forcing", "euler_get_forcing", "euler_forcing_at", "euler_get_time", "euler_set_time",
     "euler_heat_default", "euler_set_heat", "euler_get_heat", "euler_heat_get_field", "euler_heat_set_field", "euler_heat_fill", "euler_heat_raster", "euler_heat_paint",
+    "euler_body_at", "euler_set_bodies", "euler_get_bodies",
     "euler_tracers_add", "euler_tracers_count", "euler_tracers_get", "euler_tracers_clear", "euler_tracer_raster", "euler_tracer_paint",
 ]
 
@@ -234,6 +241,9 @@ def load_library():
         "euler_heat_fill": (C.c_int, [vp, i32, i32, i32, i32, f32]),
         "euler_heat_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
         "euler_heat_paint": (C.c_int, [vp, vp, i32, i32, f32, f64]),
+        "euler_body_at": (C.c_int, [vp, f64, i32, i32, vp]),
+        "euler_set_bodies": (C.c_int, [vp, vp, i32]),
+        "euler_get_bodies": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
         "euler_tracers_add": (C.c_int, [vp, vp, C.c_size_t]),
         "euler_tracers_count": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
         "euler_tracers_get": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
@@ -406,6 +416,37 @@ def forcing_at(f, t):
     a = (C.c_float * 2)()
     _check_host(load_library().euler_forcing_at(f.ctypes.data, float(t), a), "euler_forcing_at")
     return np.float32(a[0]), np.float32(a[1])
+
+
+def body(size, at, velocity=(0.0, 0.0), amplitude=(0.0, 0.0), hz=0.0, phase=0.0):
+    """A moving body (BODY_DTYPE, shape ()): size = (w, h) in cells, at = the lower-left corner at t = 0, velocity in cells per second, amplitude, hz and
+    phase (radians) of the harmonic part: p(t) = at + velocity t + amplitude sin(2 pi hz t + phase)."""
+    b = np.zeros((), BODY_DTYPE)
+    b["w"], b["h"] = size
+    b["x"], b["y"] = at
+    b["vx"], b["vy"] = velocity
+    b["amp_x"], b["amp_y"] = amplitude
+    b["hz"], b["phase"] = hz, phase
+    return b
+
+
+def bodies_array(bodies):
+    """A list of body records, or of the argument tuples of body(), as one contiguous array of BODY_DTYPE."""
+    if isinstance(bodies, np.ndarray) and bodies.dtype == BODY_DTYPE:
+        return np.ascontiguousarray(bodies).reshape(-1)
+    out = np.zeros(len(bodies), BODY_DTYPE)
+    for k, b in enumerate(bodies):
+        out[k] = b if isinstance(b, np.ndarray) else body(*b)
+    return out
+
+
+def body_at(b, t, X, Y):
+    """Where body record b stands at simulated time t on an X x Y grid (euler_body_at, host only): BODY_STATE_DTYPE of shape () - the clamped continuous
+    position (px, py) and the origin (ox, oy) of its rectangle of cells."""
+    b = np.ascontiguousarray(b, BODY_DTYPE).reshape(1)
+    st = np.zeros((), BODY_STATE_DTYPE)
+    _check_host(load_library().euler_body_at(b.ctypes.data, float(t), int(X), int(Y), st.ctypes.data), "euler_body_at")
+    return st
 
 
 def heat_default():
@@ -696,6 +737,27 @@ class Simulation:
     @time.setter
     def time(self, t):
         _check(self.L.euler_set_time(self.h, float(t)))
+
+    # --- moving bodies (docs/bodies.md)
+    def set_bodies(self, bodies):
+        """Replace the handle's moving bodies (euler_set_bodies, docs/bodies.md): a list of records of body() (or of its argument tuples), or an array of
+        BODY_DTYPE, at most BODIES_MAX.  The old rectangles are cleared, the new ones made solid at the handle's present clock."""
+        b = bodies_array(bodies)
+        _check(self.L.euler_set_bodies(self.h, b.ctypes.data if b.size else None, len(b)))
+        return self
+
+    def clear_bodies(self):
+        _check(self.L.euler_set_bodies(self.h, None, 0))
+        return self
+
+    def bodies(self):
+        """(bodies, now) as set (euler_get_bodies): an array of BODY_DTYPE and one of BODY_STATE_DTYPE - the position at the handle's clock, with the origin of
+        the cells that are solid now."""
+        b = np.zeros(BODIES_MAX, BODY_DTYPE)
+        st = np.zeros(BODIES_MAX, BODY_STATE_DTYPE)
+        n = C.c_int32(0)
+        _check(self.L.euler_get_bodies(self.h, b.ctypes.data, BODIES_MAX, st.ctypes.data, C.byref(n)))
+        return b[: n.value].copy(), st[: n.value].copy()
 
     # --- temperature (docs/heat.md)
     def set_heat(self, ambient=0.0, beta=0.0, kappa=0.0, source_t=0.0, boxes=()):

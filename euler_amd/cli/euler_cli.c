@@ -13,7 +13,7 @@
  *         [--keys STRING] [--resume FILE] [--checkpoint FILE] [--fit] [--view X0,Y0,X1,Y1] [--edit F:OP:X0,Y0,X1,Y1]...
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
  *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
- *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]...
+ *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]...
  *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
@@ -53,6 +53,10 @@
  * of simulated time with the phase in degrees, and (up to 64 times) an acceleration FX,FY on the live faces of the cells of the box [X0, X1] x [Y0, Y1], in
  * command-line order.  A malformed spec, a 65th box, a box outside the interior and a value out of range (beyond 1e4 in size, not finite, HZ < 0) are usage
  * errors.  Without the three the forcing is never touched.
+ * --body (up to 16 times, in command-line order) is a solid box of W x H cells with its lower-left corner at X,Y at t = 0 that moves at VX,VY cells per second plus
+ * a harmonic part of amplitude AX,AY cells at HZ per second of simulated time with the phase in degrees, and pushes the water (euler_set_bodies, docs/bodies.md);
+ * set once behind the load, the forcing and the heat.  A malformed spec, a 17th body and a value euler_set_bodies refuses exit with status 1.  Without it every
+ * byte is as before.
  * --tracer (up to 1024 times) and --tracer-box (up to 64 times; the K x K lattice of every cell of the box, K = 1, 2 or 4) place passive tracers
  * (euler_tracers_add, docs/tracers.md), added once behind the load in command-line order.  --emit (up to 64 times) is a point that releases a tracer right before
  * the step that produces frame F whenever F % EVERY == 0 (default 1; F = 0 counts: before frame 0 is drawn) - a streakline; the emitters of a frame go in
@@ -75,6 +79,7 @@
 #include "euler.h"
 #include "cli_gauges.h"
 #include "cli_forcing.h"
+#include "cli_bodies.h"
 #include "cli_heat.h"
 #include "cli_tracers.h"
 #include "euler_host.h"      /* eu_tracer_lattice */
@@ -82,7 +87,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -420,6 +425,8 @@ int main(int argc, char** argv) {
   euler_force_box force_boxes[MAX_FORCE_BOXES];
   int forcing_given = 0, n_force_boxes = 0;
   euler_forcing_default(&forcing);
+  euler_body bodies[MAX_BODIES];
+  int n_bodies = 0;
   static cli_seed seeds[MAX_CLI_TRACERS + MAX_TRACER_BOXES];
   cli_emitter emitters[MAX_EMITTERS];
   int n_seeds = 0, n_points = 0, n_tboxes = 0, n_emitters = 0, tracers_every = 1, tracers_show = 0;
@@ -495,6 +502,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--gravity") && i + 1 < argc) { if (parse_gravity(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--shake") && i + 1 < argc) { if (parse_shake(argv[++i], &forcing) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
     else if (!strcmp(argv[i], "--force") && i + 1 < argc) { if (n_force_boxes == MAX_FORCE_BOXES || parse_force(argv[++i], &force_boxes[n_force_boxes++]) != 0) { usage(argv[0]); return 1; } forcing_given = 1; }
+    /* moving bodies (docs/bodies.md) */
+    else if (!strcmp(argv[i], "--body") && i + 1 < argc) { if (n_bodies == MAX_BODIES || parse_body(argv[++i], &bodies[n_bodies++]) != 0) { usage(argv[0]); return 1; } }
     /* temperature: the record, the source cells' value, heat boxes in command-line order, fills of the start (docs/heat.md) */
     else if (!strcmp(argv[i], "--heat") && i + 1 < argc) { if (parse_heat(argv[++i], &heat) != 0) { usage(argv[0]); return 1; } heat_given = 1; }
     else if (!strcmp(argv[i], "--heat-source") && i + 1 < argc) { if (parse_heat_source(argv[++i], &heat.source_t) != 0) { usage(argv[0]); return 1; } heat_extra = 1; }
@@ -582,7 +591,8 @@ int main(int argc, char** argv) {
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
       (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK) ||
-      (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK)) {      /* (behind the load and the forcing) */
+      (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK) ||      /* (behind the load and the forcing) */
+      (n_bodies && euler_set_bodies(app.sim, bodies, n_bodies) != EULER_OK)) {
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }

@@ -610,6 +610,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   memset(&S->stats, 0, sizeof(S->stats));
   S->time = 0.0;      // (the forcing stays as set: docs/forcing.md)
   S->n_tracers = 0;   // (the tracers belonged to the run that was replaced: docs/tracers.md)
+  S->n_bodies = 0;    // (so did the bodies: their cells are whatever the loaded masks say, docs/bodies.md)
   if ((rc = eu_heat_reset(S))) return rc;      // (the heat record stays as set, the field starts from ambient: docs/heat.md)
   S->loaded = 1;
   return EULER_OK;
@@ -772,7 +773,8 @@ static int run_stage(euler_sim* S, int stage, float dt) {
   eu_vd_stage_begin(&S->vd, stage);      // (each launcher reports what it ran: eu_valid.h)
   switch (stage) {
     case EULER_STAGE_ADVECT_MARKERS: {   // the passive tracers first: they read u, v and the masks as the markers are about to (docs/tracers.md)
-      int rc = eu_launch_advect_tracers(S, dt);
+      int rc = S->n_bodies ? eu_launch_bodies_shift(S, dt) : EULER_OK;      // the moving bodies first: the water they push is advected from where they put it (docs/bodies.md)
+      if (!rc) rc = eu_launch_advect_tracers(S, dt);
       return rc ? rc : eu_launch_advect_markers(S, dt);
     }
     case EULER_STAGE_REFRESH_COUNTS: return eu_launch_refresh_counts(S);
@@ -789,7 +791,12 @@ static int run_stage(euler_sim* S, int stage, float dt) {
       if (!rc) rc = eu_launch_advect_velocity(S, dt);
       return rc;
     }
-    case EULER_STAGE_PROJECT: return eu_launch_project(S, dt);
+    case EULER_STAGE_PROJECT: {
+      if (!S->n_bodies) return eu_launch_project(S, dt);
+      int rc = eu_launch_body_faces(S, dt, 1);      // the wall velocity stands on the bodies' wet faces for the length of the solve, and nowhere else in a substep
+      if (!rc) rc = eu_launch_project(S, dt);
+      return rc ? rc : eu_launch_body_faces(S, dt, 0);
+    }
     default: eu_set_error("unknown stage %d", stage); return EULER_EINVAL;
   }
 }

@@ -177,6 +177,10 @@ struct euler_sim {
   int heat_on, heat_cur;
   unsigned int heat_ntiles;
   eu_devbuf heat_buf, heat_box_buf, heat_fill_buf, heat_ras_buf;      // (heat_ras_buf: the records of euler_heat_raster)
+  // euler_set_bodies (k_bodies.hip, docs/bodies.md): the list as set and, per body, the REMEMBERED origin - the cells that are solid now; host state only
+  int n_bodies;
+  euler_body bodies[EULER_BODIES_MAX];
+  int32_t body_ox[EULER_BODIES_MAX], body_oy[EULER_BODIES_MAX];
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -404,6 +408,13 @@ int eu_launch_heat_sources(euler_sim* S);
 int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]);
 int eu_heat_reset(euler_sim* S);
 int eu_heat_dry(euler_sim* S);      // behind an edit (k_edit.hip): the cells it emptied take ambient, so that the invariant holds between substeps too
+// k_bodies.hip (euler_set_bodies; no-ops without bodies): the unit shifts in front of the marker stage's launches, at the handle's clock; the wall velocity on the
+// bodies' wet faces in front of eu_launch_project (impose = 1) and its withdrawal behind it (impose = 0)
+int eu_launch_bodies_shift(euler_sim* S, float dt);
+int eu_launch_body_faces(euler_sim* S, float dt, int impose);
+// k_edit.hip: the cell pass of an edit alone (SOLID, CLEAR) and the source cells of a box, for the bodies' strips
+int eu_edit_cells_box(euler_sim* S, int cls, int op, int x0, int y0, int x1, int y1);
+int eu_edit_source_census(euler_sim* S, int cls, int x0, int y0, int x1, int y1, size_t* nsrc);
 int eu_launch_dye_extrapolate(euler_sim* S);
 int eu_launch_dye_sources(euler_sim* S);
 int eu_launch_dye_advect(euler_sim* S, float dt);

@@ -750,6 +750,62 @@ size_t eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y,
   return m;
 }
 
+/* ---- moving bodies: the law of motion, the list checked, the unit shifts and their strips (include/euler.h, docs/bodies.md) ---- */
+
+static double body_clamp(double p, double lo, double hi) { return p < lo ? lo : p > hi ? hi : p; }
+
+int euler_body_at(const euler_body* b, double t, int32_t X, int32_t Y, euler_body_state* out) {
+  if (!b || !out || b->w < 1 || b->h < 1 || b->w > X - 4 || b->h > Y - 4) return EULER_EINVAL;
+  const double s = sin(2.0 * 3.14159265358979323846 * b->hz * t + b->phase);
+  const double px = b->x + (double)b->vx * t + (double)b->amp_x * s, py = b->y + (double)b->vy * t + (double)b->amp_y * s;
+  /* (a NaN fails both comparisons of the clamp: euler_set_bodies lets none in; here it is held at the lower bound so that the origin is always a cell of the grid) */
+  out->px = px == px ? body_clamp(px, 2.0, (double)(X - 2 - b->w)) : 2.0;
+  out->py = py == py ? body_clamp(py, 2.0, (double)(Y - 2 - b->h)) : 2.0;
+  out->ox = (int32_t)floor(out->px + 0.5);
+  out->oy = (int32_t)floor(out->py + 0.5);
+  return EULER_OK;
+}
+
+int eu_body_check(const euler_body* b, int32_t n, int32_t X, int32_t Y, char* why, size_t cap) {
+#define REFUSE(...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return EULER_EINVAL; } while (0)
+  if (n < 0 || n > EULER_BODIES_MAX) REFUSE("%d bodies (0 ... %d)", n, EULER_BODIES_MAX);
+  if (n > 0 && !b) REFUSE("%d bodies and a null list", n);
+  const double two_pi = 2.0 * 3.14159265358979323846;
+  for (int32_t k = 0; k < n; ++k) {      /* the first body that fails any of its tests */
+    const euler_body* q = b + k;
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) REFUSE("body %d: reserved must be 0", k);
+    if (!isfinite(q->x) || !isfinite(q->y) || !isfinite(q->hz) || !isfinite(q->phase) || !isfinite(q->vx) || !isfinite(q->vy) || !isfinite(q->amp_x) || !isfinite(q->amp_y))
+      REFUSE("body %d: a value that is not finite", k);
+    if (q->w < 1 || q->h < 1 || q->w > X - 4 || q->h > Y - 4) REFUSE("body %d: %d x %d cells do not fit [2, %d] x [2, %d]", k, q->w, q->h, X - 3, Y - 3);
+    if (q->hz < 0.0) REFUSE("body %d: hz %g must be >= 0", k, q->hz);
+    const double sx = fabs((double)q->vx) + two_pi * q->hz * fabs((double)q->amp_x), sy = fabs((double)q->vy) + two_pi * q->hz * fabs((double)q->amp_y);
+    if (sx > 10.0 || sy > 10.0) REFUSE("body %d: a speed of up to (%g, %g) cells per second, more than 10", k, sx, sy);
+  }
+#undef REFUSE
+  return EULER_OK;
+}
+
+int64_t eu_body_plan(int32_t ox, int32_t oy, int32_t tx, int32_t ty, eu_body_shift* out, int64_t cap) {
+  const int64_t nx = tx >= ox ? (int64_t)tx - ox : (int64_t)ox - tx, ny = ty >= oy ? (int64_t)ty - oy : (int64_t)oy - ty;
+  for (int64_t k = 0; out && k < nx + ny && k < cap; ++k) {
+    out[k].axis = k < nx ? 0 : 1;
+    out[k].dir = k < nx ? (tx > ox ? 1 : -1) : (ty > oy ? 1 : -1);
+  }
+  return nx + ny;
+}
+
+void eu_body_strips(int32_t ox, int32_t oy, int32_t w, int32_t h, eu_body_shift s, int32_t fill[4], int32_t clear[4]) {
+  if (s.axis == 0) {
+    const int32_t xf = s.dir > 0 ? ox + w : ox - 1, xc = s.dir > 0 ? ox : ox + w - 1;
+    fill[0] = fill[2] = xf; clear[0] = clear[2] = xc;
+    fill[1] = clear[1] = oy; fill[3] = clear[3] = oy + h - 1;
+  } else {
+    const int32_t yf = s.dir > 0 ? oy + h : oy - 1, yc = s.dir > 0 ? oy : oy + h - 1;
+    fill[1] = fill[3] = yf; clear[1] = clear[3] = yc;
+    fill[0] = clear[0] = ox; fill[2] = clear[2] = ox + w - 1;
+  }
+}
+
 /* ---- temperature: the record's defaults, the record and the list checked, the list cut into the force boxes' tile table (include/euler.h, docs/heat.md) ---- */
 
 int euler_heat_default(euler_heat* h) {

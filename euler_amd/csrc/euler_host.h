@@ -60,6 +60,33 @@ int      eu_tracers_check(const float* xy, size_t n, size_t count, int32_t X, in
 /* the K x K lattice of a box of cells, K in {1, 2, 4}: cell x outer, cell y inner, i outer, j inner, at x + (i + 0.5f) / K, y + (j + 0.5f) / K (every term exact in
  * float32 below 2^21).  Returns the number of points, Bw * Bh * K * K; xy == NULL: the count only; 0: an empty box or another K */
 size_t   eu_tracer_lattice(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t K, float* xy);
+/* moving bodies (k_bodies.hip, docs/bodies.md): the refusals of euler_set_bodies that need no device, in its order; the unit shifts that take a body from its
+ * remembered origin to its target - all x shifts first, then y -; and the faces of a rectangle's perimeter */
+int      eu_body_check(const euler_body* b, int32_t n, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
+typedef struct eu_body_shift { int32_t axis, dir; } eu_body_shift;   /* axis 0: x, 1: y; dir +1 or -1 */
+/* the number of unit shifts from (ox, oy) to (tx, ty), |tx - ox| + |ty - oy|; out (may be NULL) takes the first min(count, cap) of them */
+int64_t  eu_body_plan(int32_t ox, int32_t oy, int32_t tx, int32_t ty, eu_body_shift* out, int64_t cap);
+/* the strip a shift solidifies and the one it clears, inclusive boxes {x0, y0, x1, y1}, for a body of w x h at (ox, oy) BEFORE the shift */
+void     eu_body_strips(int32_t ox, int32_t oy, int32_t w, int32_t h, eu_body_shift s, int32_t fill[4], int32_t clear[4]);
+/* face k of the 2 h + 2 w perimeter faces of the rectangle at (ox, oy): k in [0, h): the left edge's u faces, bottom up; [h, 2 h): the right edge's;
+ * [2 h, 2 h + w): the lower edge's v faces, left to right; then the upper edge's.  (fx, fy) is the cell whose u / v sample the face is, (cx, cy) the cell OUTSIDE the
+ * body across the face */
+typedef struct eu_body_face { int32_t axis, fx, fy, cx, cy; } eu_body_face;
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int32_t eu_body_nfaces(int32_t w, int32_t h) { return 2 * h + 2 * w; }
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline eu_body_face eu_body_face_at(int32_t ox, int32_t oy, int32_t w, int32_t h, int32_t k) {
+  eu_body_face f;
+  if (k < h)              { f.axis = 0; f.fx = ox - 1;     f.fy = oy + k;           f.cx = ox - 1; f.cy = f.fy; }
+  else if (k < 2 * h)     { f.axis = 0; f.fx = ox + w - 1; f.fy = oy + k - h;       f.cx = ox + w; f.cy = f.fy; }
+  else if (k < 2 * h + w) { f.axis = 1; f.fx = ox + k - 2 * h;     f.fy = oy - 1;     f.cx = f.fx; f.cy = oy - 1; }
+  else                    { f.axis = 1; f.fx = ox + k - 2 * h - w; f.fy = oy + h - 1; f.cx = f.fx; f.cy = oy + h; }
+  return f;
+}
 /* The multilevel preconditioner's node grids and the plan of its cycle split by rows (k_mg.h, k_mg_split.hip, docs/solver_multilevel_row_slabs.md): everything that
  * follows from the grid's size and the ranks' band ranges alone.  Row ranges are half open, [lo, hi); an empty zone is {0, 0}. */
 #ifndef MG_G0

@@ -215,10 +215,47 @@ static int ed_run(euler_sim* S, int op, const EdBox& b) {
   return eu_sync_marker_state(S);      // the host's marker count is in step again
 }
 
+// ---- the moving bodies' use of the passes above (k_bodies.hip, docs/bodies.md): the cell pass of SOLID or CLEAR over a strip or a rectangle, in the profile class of
+// the stage that shifts, and the source cells a strip is about to cover.  The caller has done an edit's bookkeeping (eu_pressure_current, eu_vd_masks_changed).
+int eu_edit_cells_box(euler_sim* S, int cls, int op, int x0, int y0, int x1, int y1) {
+  const EdBox b{x0, y0, x1, y1, y1 - y0 + 1};
+  if ((S->X & 3) == 0) {
+    const int span = x1 - ob_xbase(4, x0) + 1;
+    LAUNCH(S, cls, k_edit_cells<4>, dim3((unsigned)((span + 63) / 64), (unsigned)((b.Bh + 63) / 64)), dim3(256), S->solid, S->source, S->sink, S->count, S->X, b, op, S->cellmask64);
+  } else {
+    const int span = x1 - ob_xbase(1, x0) + 1;
+    LAUNCH(S, cls, k_edit_cells<1>, dim3((unsigned)((span + 63) / 64), (unsigned)((b.Bh + 63) / 64)), dim3(256), S->solid, S->source, S->sink, S->count, S->X, b, op, S->cellmask64);
+  }
+  HIPCHK(hipGetLastError());
+  return EULER_OK;
+}
+int eu_edit_source_census(euler_sim* S, int cls, int x0, int y0, int x1, int y1, size_t* nsrc) {      // (one read-back: only handles with source cells come here)
+  const EdBox b{x0, y0, x1, y1, y1 - y0 + 1};
+  HIPCHK(hipMemsetAsync(&S->ms->n_events, 0, 2 * sizeof(unsigned int), S->stream));      // (n_events, n_actual)
+  if ((S->X & 3) == 0) {
+    const int span = x1 - ob_xbase(4, x0) + 1;
+    LAUNCH(S, cls, k_edit_census<4>, dim3((unsigned)((span + 255) / 256), (unsigned)((b.Bh + 3) / 4)), dim3(256), S->solid, S->source, S->sink, S->count, S->X, b, (int)EULER_EDIT_SOLID, S->ms);
+  } else {
+    const int span = x1 - ob_xbase(1, x0) + 1;
+    LAUNCH(S, cls, k_edit_census<1>, dim3((unsigned)((span + 63) / 64), (unsigned)((b.Bh + 3) / 4)), dim3(256), S->solid, S->source, S->sink, S->count, S->X, b, (int)EULER_EDIT_SOLID, S->ms);
+  }
+  HIPCHK(hipGetLastError());
+  int rc = eu_sync_marker_state(S);
+  if (!rc) *nsrc = (size_t)S->ms_host->n_actual;
+  return rc;
+}
+
 extern "C" int euler_edit_box(euler_sim* S, int32_t op, int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
   int rc = eu_observe_enter(S, "euler_edit_box", "solid and source cells are facts a slab only gets from a load", S, x0, y0, x1, y1);
   if (rc) return rc;
   if (op < EULER_EDIT_SOLID || op > EULER_EDIT_DRAIN) { eu_set_error("euler_edit_box: op %d: one of EULER_EDIT_*", (int)op); return EULER_EINVAL; }
+  for (int k = 0; k < S->n_bodies; ++k) {      // a moving body's cells are the body's: its next shift would undo the edit half way (docs/bodies.md)
+    const int bx = S->body_ox[k], by = S->body_oy[k];
+    if (x0 <= bx + S->bodies[k].w - 1 && x1 >= bx && y0 <= by + S->bodies[k].h - 1 && y1 >= by) {
+      eu_set_error("euler_edit_box: the box [%d, %d] x [%d, %d] intersects body %d at [%d, %d] x [%d, %d]", x0, x1, y0, y1, k, bx, bx + S->bodies[k].w - 1, by, by + S->bodies[k].h - 1);
+      return EULER_ESTATE;
+    }
+  }
   const EdBox b{x0, y0, x1, y1, y1 - y0 + 1};
   return (S->X & 3) == 0 ? ed_run<4>(S, op, b) : ed_run<1>(S, op, b);
 }

@@ -417,6 +417,7 @@ extern "C" int euler_load_state(euler_sim* S, const char* path) {
   S->stats.frames = h0.frames; S->stats.total_substeps = h0.total_substeps; S->stats.total_pcg_iterations = h0.total_pcg_iterations;
   S->time = 0.0;      // (the clock is no part of a snapshot and the forcing stays as set: the caller restores both, docs/forcing.md)
   S->n_tracers = 0;   // (tracers are no part of a snapshot either: docs/tracers.md)
+  S->n_bodies = 0;    // (nor are the moving bodies: docs/bodies.md)
   if ((rc = eu_heat_reset(S))) return rc;      // (nor is the temperature: the record stays as set, the field starts from ambient, docs/heat.md)
   S->loaded = 1;
   return EULER_OK;

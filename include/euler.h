@@ -710,6 +710,50 @@ int euler_tracer_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int3
 int euler_tracer_paint(const uint32_t* counts, euler_overview_px* px, int32_t W, int32_t H,
                        const float fg[3], const float* bg /* 3 floats or NULL */);
 
+/* ---- moving bodies: solid boxes that push water at a prescribed velocity (docs/bodies.md) ---------- */
+/* A piston, a paddle, a plunger, a sliding sluice: up to EULER_BODIES_MAX solid rectangles of whole cells that follow a prescribed path through the water.
+ * THE LAW OF MOTION is a stateless function of the handle's clock (euler_get_time), computed on the host in double: p(t) = x + vx t + amp_x sin(2 pi hz t + phase),
+ * px = clamp(p(t), 2, X - 2 - w), ox = (int)floor(px + 0.5); the same in y with h and Y.  The clamp keeps the rectangle [ox, ox + w - 1] x [oy, oy + h - 1] inside
+ * [2, X - 3] x [2, Y - 3] for all time: a body that reaches the edge stops there.  euler_body_at is that function; no sin runs on the device.
+ * PER SUBSTEP of euler_step / euler_substep with step dt at clock t, in front of the tracers' and the markers' advection (euler_stage: in
+ * EULER_STAGE_ADVECT_MARKERS; the clock does not advance there, so a repeated stage call shifts nothing twice):
+ *   1. for each body in list order the target (tx, ty) is the origin of euler_body_at(t + dt);
+ *   2. the body moves from its remembered origin (ox, oy) to the target one cell at a time, all x shifts first, then y.  A shift by +1 in x: every marker with
+ *      floorf(m.x) == ox + w and oy <= floorf(m.y) <= oy + h - 1 takes m.x = fl(m.x + 1.f) (the water is pushed ahead of the face and keeps its place in the
+ *      array); the cells of column ox + w get the masks and the count of EULER_EDIT_SOLID (solid = 1, source = sink = 0, count = 0); column ox gets
+ *      EULER_EDIT_CLEAR (a body carves what it passes through); ox += 1.  Mirrored for -1 (the markers of column ox - 1 take fl(m.x - 1.f)) and for y.  The counts of
+ *      the cells the markers land in are not updated: the refresh that follows counts them where they lie (a marker that lands in a wall is deleted there);
+ *   3. when any body shifted, every body's rectangle gets the SOLID masks and the zero counts again in list order (one body's CLEAR cannot open another).
+ * A substep in which no body shifts launches nothing here.
+ * THE WALL VELOCITY of the substep is the mean velocity over it, wx = (float)((px(t + dt) - px(t)) / (double)dt) and wy likewise (0 while the body is clamped).  At the
+ * start of EULER_STAGE_PROJECT, for the bodies in list order, a u face on the left or right edge of a body's rectangle takes utmp = wx when its outside cell has
+ * count != 0 && !solid and wx != 0.f; the v faces of the lower and upper edge take vtmp = wy likewise.  The same faces are set back to 0.f behind the stage.  The
+ * right-hand side picks the velocity up (every fluid cell reads its four faces, solid ones too); the velocity update leaves u = v = 0 on the body's faces.  A body
+ * with wx == wy == 0 is bit for bit a wall made by euler_edit_box.
+ * Bodies are not part of a snapshot: a scenario load and euler_load_state drop them (n = 0; their cells are whatever the loaded masks say).  Whole-grid handles only. */
+#define EULER_BODIES_MAX 16
+typedef struct euler_body {          /* 64 bytes, no padding */
+  double  x, y;                      /* lower-left corner at t = 0, in cells, continuous */
+  double  hz, phase;                 /* of the harmonic part; 1/s of simulated time, radians */
+  float   vx, vy;                    /* constant velocity, cells per second */
+  float   amp_x, amp_y;              /* amplitude of the harmonic part, cells */
+  int32_t w, h;                      /* size in cells, >= 1 */
+  int32_t reserved[2];               /* 0 */
+} euler_body;
+typedef struct euler_body_state { double px, py; int32_t ox, oy; } euler_body_state;   /* 24 bytes */
+/* host only, no GPU.  EULER_EINVAL: a null pointer, w or h < 1, w > X - 4 or h > Y - 4 (no place inside the clamp range) */
+int euler_body_at(const euler_body* b, double t, int32_t X, int32_t Y, euler_body_state* out);
+/* Replaces the handle's list at its present clock: the rectangles of the old list are cleared (the mask change of EULER_EDIT_CLEAR), each new body's rectangle is made
+ * solid exactly as EULER_EDIT_SOLID does (markers inside deleted), and the origin of each body is remembered.  n == 0 (bodies may be NULL) removes them.
+ * Refusals, in this order: a null sim (EULER_EINVAL); a row-slab handle (EULER_ESTATE); nothing loaded (EULER_ESTATE); then EULER_EINVAL for n outside
+ * [0, EULER_BODIES_MAX] or a null list with n > 0; per body, naming the first bad one: reserved not 0; a non-finite value; w, h < 1, w > X - 4 or h > Y - 4; hz < 0;
+ * a speed bound |vx| + 2 pi hz |amp_x| > 10 (or the same in y) cells per second - one cell per 0.1 s frame.  A refused call changes and allocates nothing.
+ * While bodies are set, euler_edit_box refuses (EULER_ESTATE) a box that intersects a body's current rectangle. */
+int euler_set_bodies(euler_sim* sim, const euler_body* bodies, int32_t n);
+/* The list as set (bodies may be NULL, else cap >= *n on return: EULER_EINVAL otherwise) and, where now is not NULL, per body the position at the handle's clock with
+ * the REMEMBERED origin in ox, oy (the cells that are solid now); *n the number of bodies. */
+int euler_get_bodies(euler_sim* sim, euler_body* bodies, int32_t cap, euler_body_state* now, int32_t* n);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
