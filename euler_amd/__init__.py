@@ -66,6 +66,10 @@ BODY_DTYPE = np.dtype({"names": ["x", "y", "hz", "phase", "vx", "vy", "amp_x", "
                        "formats": [np.float64] * 4 + [np.float32] * 4 + [np.int32] * 2 + [(np.int32, 2)],
                        "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 48, 52, 56], "itemsize": 64})
 BODY_STATE_DTYPE = np.dtype({"names": ["px", "py", "ox", "oy"], "formats": [np.float64] * 2 + [np.int32] * 2, "offsets": [0, 8, 16, 20], "itemsize": 24})
+# euler_reseed, euler_reseed_stats (include/euler.h): the marker density control's record and its totals
+RESEED_DTYPE = np.dtype({"names": ["thin_above", "fill_holes", "max_cells", "max_fill", "reserved"], "formats": [np.int32] * 4 + [(np.int32, 4)],
+                         "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+RESEED_STATS_DTYPE = np.dtype({"names": ["removed", "added", "cells_thinned", "deferred"], "formats": [np.uint64] * 4, "offsets": [0, 8, 16, 24], "itemsize": 32})
 # euler_tracer (include/euler.h): one passive tracer; EULER_TRACER_* flag bits; EULER_TRACER_RASTER_ALL of euler_tracer_raster
 TRACERS_MAX = 1 << 22
 TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER_WAS_DRY = 1, 2, 4, 8, 16, 32
@@ -141,6 +145,7 @@ EXPORTS = [
     "euler_forcing_default", "euler_set_forcing", "euler_get_forcing", "euler_forcing_at", "euler_get_time", "euler_set_time",
     "euler_heat_default", "euler_set_heat", "euler_get_heat", "euler_heat_get_field", "euler_heat_set_field", "euler_heat_fill", "euler_heat_raster", "euler_heat_paint",
     "euler_body_at", "euler_set_bodies", "euler_get_bodies",
+    "euler_set_reseed", "euler_get_reseed",
     "euler_tracers_add", "euler_tracers_count", "euler_tracers_get", "euler_tracers_clear", "euler_tracer_raster", "euler_tracer_paint",
 ]
 
@@ -244,6 +249,8 @@ def load_library():
         "euler_body_at": (C.c_int, [vp, f64, i32, i32, vp]),
         "euler_set_bodies": (C.c_int, [vp, vp, i32]),
         "euler_get_bodies": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
+        "euler_set_reseed": (C.c_int, [vp, vp]),
+        "euler_get_reseed": (C.c_int, [vp, vp, vp]),
         "euler_tracers_add": (C.c_int, [vp, vp, C.c_size_t]),
         "euler_tracers_count": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
         "euler_tracers_get": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
@@ -438,6 +445,15 @@ def bodies_array(bodies):
     for k, b in enumerate(bodies):
         out[k] = b if isinstance(b, np.ndarray) else body(*b)
     return out
+
+
+def reseed(thin_above=0, fill_holes=False, max_cells=0, max_fill=0):
+    """A record of the marker density control (RESEED_DTYPE, shape (); euler_set_reseed, docs/reseed.md): a cell whose count byte exceeds thin_above (0: no
+    thinning, else 4 ... 254) is thinned to one marker per quarter-cell square, fill_holes puts a marker into every single-cell hole in the water; max_cells and
+    max_fill bound the cells treated per pass (0: 65536)."""
+    r = np.zeros((), RESEED_DTYPE)
+    r["thin_above"], r["fill_holes"], r["max_cells"], r["max_fill"] = int(thin_above), int(fill_holes), int(max_cells), int(max_fill)
+    return r
 
 
 def body_at(b, t, X, Y):
@@ -758,6 +774,25 @@ class Simulation:
         n = C.c_int32(0)
         _check(self.L.euler_get_bodies(self.h, b.ctypes.data, BODIES_MAX, st.ctypes.data, C.byref(n)))
         return b[: n.value].copy(), st[: n.value].copy()
+
+    # --- marker density control (docs/reseed.md)
+    def set_reseed(self, record=None, **kw):
+        """Switch the marker density control on or off (euler_set_reseed, docs/reseed.md): a record of reseed(), or its keyword arguments; an all-zero record
+        switches it off.  The totals count from this call."""
+        r = np.ascontiguousarray(reseed(**kw) if record is None else record, RESEED_DTYPE).reshape(1)
+        _check(self.L.euler_set_reseed(self.h, r.ctypes.data))
+        return self
+
+    def clear_reseed(self):
+        _check(self.L.euler_set_reseed(self.h, None))
+        return self
+
+    def reseed(self):
+        """(record, totals) as set (euler_get_reseed): RESEED_DTYPE and RESEED_STATS_DTYPE of shape () - markers removed and added, cells thinned and cells
+        deferred since the last set_reseed."""
+        r, st = np.zeros((), RESEED_DTYPE), np.zeros((), RESEED_STATS_DTYPE)
+        _check(self.L.euler_get_reseed(self.h, r.ctypes.data, st.ctypes.data))
+        return r, st
 
     # --- temperature (docs/heat.md)
     def set_heat(self, ambient=0.0, beta=0.0, kappa=0.0, source_t=0.0, boxes=()):

@@ -14,6 +14,7 @@
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
  *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
  *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]...
+ *         [--reseed THIN[:fill]]
  *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
@@ -57,6 +58,10 @@
  * a harmonic part of amplitude AX,AY cells at HZ per second of simulated time with the phase in degrees, and pushes the water (euler_set_bodies, docs/bodies.md);
  * set once behind the load, the forcing and the heat.  A malformed spec, a 17th body and a value euler_set_bodies refuses exit with status 1.  Without it every
  * byte is as before.
+ * --reseed THIN[:fill] switches the marker density control on (euler_set_reseed, docs/reseed.md) behind the load and the bodies: a cell whose count exceeds THIN
+ * (4 ... 254) is thinned to one marker per quarter-cell square, with :fill a single-cell hole in the water gets a marker back; THIN = 0 with :fill fills only.  The
+ * totals - markers removed and added, cells thinned, cells deferred - go on one line to stderr at exit.  A malformed spec is a usage error, a value
+ * euler_set_reseed refuses exits with status 1.  Without it every byte is as before.
  * --tracer (up to 1024 times) and --tracer-box (up to 64 times; the K x K lattice of every cell of the box, K = 1, 2 or 4) place passive tracers
  * (euler_tracers_add, docs/tracers.md), added once behind the load in command-line order.  --emit (up to 64 times) is a point that releases a tracer right before
  * the step that produces frame F whenever F % EVERY == 0 (default 1; F = 0 counts: before frame 0 is drawn) - a streakline; the emitters of a frame go in
@@ -80,6 +85,7 @@
 #include "cli_gauges.h"
 #include "cli_forcing.h"
 #include "cli_bodies.h"
+#include "cli_reseed.h"
 #include "cli_heat.h"
 #include "cli_tracers.h"
 #include "euler_host.h"      /* eu_tracer_lattice */
@@ -87,7 +93,7 @@
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--reseed THIN[:fill]] [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -427,6 +433,8 @@ int main(int argc, char** argv) {
   euler_forcing_default(&forcing);
   euler_body bodies[MAX_BODIES];
   int n_bodies = 0;
+  euler_reseed reseed;
+  int reseed_given = 0;
   static cli_seed seeds[MAX_CLI_TRACERS + MAX_TRACER_BOXES];
   cli_emitter emitters[MAX_EMITTERS];
   int n_seeds = 0, n_points = 0, n_tboxes = 0, n_emitters = 0, tracers_every = 1, tracers_show = 0;
@@ -517,6 +525,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--tracers-every") && i + 1 < argc) { tracers_every = atoi(argv[++i]); if (tracers_every < 1) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--tracers-show")) tracers_show = 1;
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
+    /* marker density control (docs/reseed.md) */
+    else if (!strcmp(argv[i], "--reseed") && i + 1 < argc) { if (parse_reseed(argv[++i], &reseed) != 0) { usage(argv[0]); return 1; } reseed_given = 1; }
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
   }
@@ -592,7 +602,8 @@ int main(int argc, char** argv) {
       (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
       (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK) ||
       (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK) ||      /* (behind the load and the forcing) */
-      (n_bodies && euler_set_bodies(app.sim, bodies, n_bodies) != EULER_OK)) {
+      (n_bodies && euler_set_bodies(app.sim, bodies, n_bodies) != EULER_OK) ||
+      (reseed_given && euler_set_reseed(app.sim, &reseed) != EULER_OK)) {
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }
@@ -707,6 +718,8 @@ int main(int argc, char** argv) {
   if (euler_get_stats(app.sim, &st) == EULER_OK)
     fprintf(stderr, "frames %llu substeps %llu pcg_iterations %llu markers %llu\n", (unsigned long long)st.frames,
             (unsigned long long)st.total_substeps, (unsigned long long)st.total_pcg_iterations, (unsigned long long)st.n_markers);
+  euler_reseed_stats rs;
+  if (reseed_given && euler_get_reseed(app.sim, NULL, &rs) == EULER_OK) (void)print_reseed_totals(stderr, &rs);
   free(buf);
   euler_destroy(app.sim);
   return rc_exit;

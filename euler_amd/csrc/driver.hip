@@ -275,7 +275,7 @@ extern "C" void euler_destroy(euler_sim* S) {
   eu_rccl_release(S);
   eu_slab_release(S);
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf, &S->heat_buf, &S->heat_box_buf, &S->heat_fill_buf, &S->heat_ras_buf}) eu_devbuf_release(S, b);
+  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf, &S->heat_buf, &S->heat_box_buf, &S->heat_fill_buf, &S->heat_ras_buf, &S->rs_mask_buf, &S->rs_cell_buf, &S->rs_slot_buf, &S->rs_draw_buf}) eu_devbuf_release(S, b);
   // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
   // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
   const size_t wo = S->shifted ? S->win_off : 0;
@@ -596,6 +596,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   MarkerState m0;
   memset(&m0, 0, sizeof(m0));
   m0.n = n; m0.n_loc = n_loc; m0.max_markers = 4 * C; m0.rng_state = rng;     // n and the cap are the reference's GLOBAL ones
+  m0.rs_removed = S->ms_host->rs_removed; m0.rs_added = S->ms_host->rs_added; m0.rs_thinned = S->ms_host->rs_thinned; m0.rs_deferred = S->ms_host->rs_deferred;      // (totals since euler_set_reseed: a setting's, not the run's)
   HIPCHK(hipMemcpyAsync(S->ms, &m0, sizeof(m0), hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   S->n_markers_host = n_loc;
@@ -777,7 +778,10 @@ static int run_stage(euler_sim* S, int stage, float dt) {
       if (!rc) rc = eu_launch_advect_tracers(S, dt);
       return rc ? rc : eu_launch_advect_markers(S, dt);
     }
-    case EULER_STAGE_REFRESH_COUNTS: return eu_launch_refresh_counts(S);
+    case EULER_STAGE_REFRESH_COUNTS: {   // the marker density control, where it is on, on what the refresh leaves (docs/reseed.md)
+      int rc = eu_launch_refresh_counts(S);
+      return rc || !S->reseed_on ? rc : eu_launch_reseed(S);
+    }
     case EULER_STAGE_SOURCES: {   // with the dye: extrapolate(g_r/g/b, P) comes first (main.c:859-864)
       int rc = eu_launch_dye_extrapolate(S);
       if (!rc) rc = eu_launch_sources(S);

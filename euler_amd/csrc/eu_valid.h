@@ -96,6 +96,10 @@ static inline void eu_vd_refreshed(eu_valid* v) {
 }
 /* the source stage ran (k_source_place sets the tile flags of what it fills itself): the count grid changes, markers join */
 static inline void eu_vd_sources_ran(eu_valid* v) { v->uv_zb = 0; v->prebin_valid = 0; }
+/* the marker density control ran behind the refresh (k_reseed.hip, docs/reseed.md): markers leave and join, a count changes - a thinned cell stays wet, a filled
+   hole was water one refresh ago and its tile's flag is set by the pass itself, as k_source_place does.  What the source stage drops, for the same reasons; both
+   are down already behind a refresh, so the event changes nothing there: it keeps the promise where somebody calls the pass from elsewhere */
+static inline void eu_vd_reseeded(eu_valid* v) { v->uv_zb = 0; v->prebin_valid = 0; }
 /* extrapolate + zero_bounds wrote u, v (inside a substep the timestep has consumed the maxima long before) */
 static inline void eu_vd_extrapolated(eu_valid* v) {
   if (v->maxsq_state == 2) v->maxsq_state = 1;

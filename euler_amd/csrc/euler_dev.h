@@ -86,6 +86,14 @@ struct MarkerState {
   unsigned int n_recv;        // markers received from the neighbouring slabs in this substep
   unsigned int src_k_lo;      // sources: eligible cells on lower ranks (= this rank's first index into the substep's append order)
   unsigned long long rng0;    // sources: the generator's state at the start of the substep's draws (the parallel draw kernel jumps from it)
+  // marker density control (k_reseed.hip, docs/reseed.md): the words of one pass - each written before it is read -, then the totals since the last euler_set_reseed
+  unsigned int rs_crowded;    // crowded cells found (the select's total)
+  unsigned int rs_k;          // ... of which the pass lists and thins: min(rs_crowded, max_cells)
+  unsigned int rs_holes;      // holes found (the select's total)
+  unsigned int rs_fill;       // markers the pass appends: min(rs_holes, max_fill, the room left)
+  unsigned long long rs_n0;   // index of the first appended marker
+  unsigned long long rs_rng0; // the generator's state in front of the pass's draws
+  unsigned long long rs_removed, rs_added, rs_thinned, rs_deferred;
 };
 
 // Band-skewed layout of the solver's private arrays (k_pcg.h): element (x,y) lives at
@@ -181,6 +189,12 @@ struct euler_sim {
   int n_bodies;
   euler_body bodies[EULER_BODIES_MAX];
   int32_t body_ox[EULER_BODIES_MAX], body_oy[EULER_BODIES_MAX];
+  // euler_set_reseed (k_reseed.hip, docs/reseed.md): the record as set, whether the pass runs (the host flag run_stage tests), and the pass's own device memory,
+  // allocated by the first call that switches it on: the hole mask [ceil(C / 64) + 1 words], the listed cells [max_cells], their sub-cell slots [16 max_cells]
+  // and the draws [2 max_fill floats]
+  euler_reseed reseed;
+  int reseed_on;
+  eu_devbuf rs_mask_buf, rs_cell_buf, rs_slot_buf, rs_draw_buf;
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -412,6 +426,8 @@ int eu_heat_dry(euler_sim* S);      // behind an edit (k_edit.hip): the cells it
 // bodies' wet faces in front of eu_launch_project (impose = 1) and its withdrawal behind it (impose = 0)
 int eu_launch_bodies_shift(euler_sim* S, float dt);
 int eu_launch_body_faces(euler_sim* S, float dt, int impose);
+// k_reseed.hip (euler_set_reseed; callers test S->reseed_on): one pass of the marker density control, behind eu_launch_refresh_counts in EULER_STAGE_REFRESH_COUNTS
+int eu_launch_reseed(euler_sim* S);
 // k_edit.hip: the cell pass of an edit alone (SOLID, CLEAR) and the source cells of a box, for the bodies' strips
 int eu_edit_cells_box(euler_sim* S, int cls, int op, int x0, int y0, int x1, int y1);
 int eu_edit_source_census(euler_sim* S, int cls, int x0, int y0, int x1, int y1, size_t* nsrc);

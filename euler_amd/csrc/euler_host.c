@@ -806,6 +806,92 @@ void eu_body_strips(int32_t ox, int32_t oy, int32_t w, int32_t h, eu_body_shift 
   }
 }
 
+/* ---- marker density control: the record checked, one pass restated sequentially (include/euler.h, docs/reseed.md) ---- */
+
+int eu_reseed_check(const euler_reseed* r, char* why, size_t cap) {
+#define REFUSE(...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return EULER_EINVAL; } while (0)
+  for (int k = 0; k < 4; ++k)
+    if (r->reserved[k] != 0) REFUSE("reserved must be 0");
+  if (r->thin_above != 0 && (r->thin_above < 4 || r->thin_above > 254)) REFUSE("thin_above %d is neither 0 nor in [4, 254]", r->thin_above);
+  if (r->fill_holes != 0 && r->fill_holes != 1) REFUSE("fill_holes %d is neither 0 nor 1", r->fill_holes);
+  if (r->max_cells < 0 || r->max_cells > EU_RESEED_MAX_LIMIT) REFUSE("max_cells %d is outside [0, %d]", r->max_cells, EU_RESEED_MAX_LIMIT);
+  if (r->max_fill < 0 || r->max_fill > EU_RESEED_MAX_LIMIT) REFUSE("max_fill %d is outside [0, %d]", r->max_fill, EU_RESEED_MAX_LIMIT);
+#undef REFUSE
+  return EULER_OK;
+}
+
+int eu_reseed_pass(const euler_reseed* r, int32_t X, int32_t Y, float* m, uint64_t* n_io, uint64_t max_markers, uint8_t* count, const uint8_t* prev_count,
+                   const uint8_t* solid, const uint8_t* sink, const uint8_t* source, uint64_t* rng_state, euler_reseed_stats* stats) {
+  if (!r || !m || !n_io || !count || !prev_count || !solid || !sink || !source || !rng_state || X < 3 || Y < 3 || eu_reseed_check(r, NULL, 0)) return EULER_EINVAL;
+  const size_t C = (size_t)X * (size_t)Y;
+  uint64_t n = *n_io, removed = 0, added = 0, thinned = 0, deferred = 0;
+  if (r->thin_above) {
+    /* the list: slot[c] = 1 + the cell's rank in it, 0 for every other cell */
+    const uint64_t cap = (uint64_t)eu_reseed_limit(r->max_cells);
+    uint32_t* slot = (uint32_t*)calloc(C, sizeof *slot);
+    uint8_t* gone = (uint8_t*)calloc(n ? n : 1, 1);
+    uint64_t K = 0;
+    if (slot && gone)
+      for (size_t c = 0; c < C; ++c)
+        if (count[c] > r->thin_above) { if (K < cap) slot[c] = (uint32_t)++K; else ++deferred; }
+    uint8_t* seen = slot && gone ? (uint8_t*)calloc(K ? 16 * K : 1, 1) : NULL;
+    if (!seen) { free(slot); free(gone); return EULER_ENOMEM; }
+    /* the flags, before any deletion: ascending i, so the first marker met in a sub-cell is the one with the lowest index */
+    for (uint64_t i = 0; i < n; ++i) {
+      const int32_t cx = (int32_t)floorf(m[2 * i]), cy = (int32_t)floorf(m[2 * i + 1]);
+      const uint32_t k = slot[(size_t)cy * X + cx];
+      if (!k) continue;
+      uint8_t* s = seen + 16 * (size_t)(k - 1) + 4 * eu_reseed_subcell(m[2 * i + 1], cy) + eu_reseed_subcell(m[2 * i], cx);
+      if (*s) gone[i] = 1; else *s = 1;
+    }
+    /* refresh_marker_counts' loop (main.c:105-116): the last marker takes the place of a deleted one - with its flag - and is examined next */
+    for (uint64_t i = 0; i < n;) {
+      if (!gone[i]) { ++i; continue; }
+      --n; ++removed;
+      m[2 * i] = m[2 * n]; m[2 * i + 1] = m[2 * n + 1]; gone[i] = gone[n];
+    }
+    for (size_t c = 0; c < C; ++c) {
+      if (!slot[c]) continue;
+      int occ = 0;
+      for (int q = 0; q < 16; ++q) occ += seen[16 * (size_t)(slot[c] - 1) + q];
+      count[c] = (uint8_t)occ;
+    }
+    thinned = K;
+    free(slot); free(gone); free(seen);
+  }
+  if (r->fill_holes) {
+    const uint64_t cap = (uint64_t)eu_reseed_limit(r->max_fill);
+    uint8_t* hole = (uint8_t*)calloc(C, 1);      /* all of them first: a filled hole must not count as a wet neighbour of the next */
+    if (!hole) return EULER_ENOMEM;
+    for (int32_t y = 1; y < Y - 1; ++y)
+      for (int32_t x = 1; x < X - 1; ++x) {
+        const size_t c = (size_t)y * X + x;
+        if (count[c] != 0 || prev_count[c] == 0 || solid[c] || sink[c] || source[c]) continue;
+        int wet = 1;
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            const size_t q = (size_t)(y + dy) * X + (x + dx);
+            if ((dx || dy) && count[q] == 0 && !solid[q]) wet = 0;
+          }
+        hole[c] = (uint8_t)wet;
+      }
+    uint64_t listed = 0;
+    for (size_t c = 0; c < C; ++c) {
+      if (!hole[c]) continue;
+      if (listed == cap || n + 1 > max_markers - 1) { ++deferred; continue; }
+      ++listed;
+      const float ry = euler_rng_next_float(rng_state), rx = euler_rng_next_float(rng_state);
+      m[2 * n] = (float)(int32_t)(c % (size_t)X) + rx; m[2 * n + 1] = (float)(int32_t)(c / (size_t)X) + ry;
+      ++n; ++added;
+      count[c] = 1;
+    }
+    free(hole);
+  }
+  *n_io = n;
+  if (stats) { stats->removed += removed; stats->added += added; stats->cells_thinned += thinned; stats->deferred += deferred; }
+  return EULER_OK;
+}
+
 /* ---- temperature: the record's defaults, the record and the list checked, the list cut into the force boxes' tile table (include/euler.h, docs/heat.md) ---- */
 
 int euler_heat_default(euler_heat* h) {

@@ -87,6 +87,27 @@ static inline eu_body_face eu_body_face_at(int32_t ox, int32_t oy, int32_t w, in
   else                    { f.axis = 1; f.fx = ox + k - 2 * h - w; f.fy = oy + h - 1; f.cx = f.fx; f.cy = oy + h; }
   return f;
 }
+/* marker density control (k_reseed.hip, docs/reseed.md): the refusals of euler_set_reseed that need no device, in its order; the limits a record stands for; the
+ * sub-cell of a coordinate; and ONE pass restated sequentially over host arrays - what the kernels are held to */
+#define EU_RESEED_DEFAULT_LIMIT 65536
+#define EU_RESEED_MAX_LIMIT (1 << 20)
+int      eu_reseed_check(const euler_reseed* r, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why; r must not be NULL */
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int32_t eu_reseed_limit(int32_t given) { return given ? given : EU_RESEED_DEFAULT_LIMIT; }
+/* m: a coordinate, c = floorf(m) as an int.  The subtraction is exact (Sterbenz, or c = 0), the product a power of two */
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int32_t eu_reseed_subcell(float m, int32_t c) {
+  const int32_t s = (int32_t)__builtin_floorf((m - (float)c) * 4.f);
+  return s < 3 ? s : 3;
+}
+/* markers_xy holds *n markers and has room for max_markers; the totals are ADDED to stats (may be NULL).  EULER_EINVAL: a null array, a record eu_reseed_check
+ * refuses, X or Y < 3; EULER_ENOMEM: no scratch.  Markers must lie inside the grid. */
+int      eu_reseed_pass(const euler_reseed* r, int32_t X, int32_t Y, float* markers_xy, uint64_t* n, uint64_t max_markers, uint8_t* count, const uint8_t* prev_count,
+                        const uint8_t* solid, const uint8_t* sink, const uint8_t* source, uint64_t* rng_state, euler_reseed_stats* stats);
 /* The multilevel preconditioner's node grids and the plan of its cycle split by rows (k_mg.h, k_mg_split.hip, docs/solver_multilevel_row_slabs.md): everything that
  * follows from the grid's size and the ranks' band ranges alone.  Row ranges are half open, [lo, hi); an empty zone is {0, 0}. */
 #ifndef MG_G0

@@ -778,6 +778,7 @@ __global__ void k_source_draws(MarkerState* ms, const RngJump* __restrict__ J) {
 // ... and the draws themselves, in parallel: a thread jumps to its chunk of the ONE sequential stream (draw d is the generator's
 // output after d + 1 steps from rng0) and walks SRC_CHUNK cells = 2 SRC_CHUNK draws.  Round 1 walked the stream with one
 // thread: 6.9 ms per substep at 4096^2 waterfall (0.27 M source cells), 39 % of the run.
+// (k_reseed.hip keeps a copy of this draw scheme and of k_source_place's order - k_rs_draws, k_rs_place, RS_CHUNK - for the holes it fills: change them together)
 #define SRC_CHUNK 32
 __global__ __launch_bounds__(256) void k_source_fill(const MarkerState* ms, const RngJump* __restrict__ J, float* __restrict__ draws) {
   const unsigned long long n_mine = ms->n_append, k_lo = ms->src_k_lo;        // this rank's cells are k_lo .. k_lo + n_mine of the substep's order

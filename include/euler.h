@@ -754,6 +754,40 @@ int euler_set_bodies(euler_sim* sim, const euler_body* bodies, int32_t n);
  * the REMEMBERED origin in ox, oy (the cells that are solid now); *n the number of bodies. */
 int euler_get_bodies(euler_sim* sim, euler_body* bodies, int32_t cap, euler_body_state* now, int32_t* n);
 
+/* ---- marker density control: thin crowded cells, refill torn holes (docs/reseed.md) ---------- */
+/* Opt-in, whole-grid handles only; the reference has nothing like it, and a handle that never switches it on launches what it launched and gives the same bits.
+ * While it is on, one PASS runs as the tail of every EULER_STAGE_REFRESH_COUNTS - in a substep and in euler_stage, not in the refresh a load runs - on the marker
+ * array and the count grid the refresh has just left (h = 1):
+ *   thinning (thin_above != 0)
+ *     1. the crowded cells are those whose count BYTE exceeds thin_above; the first max_cells of them in row-major order are LISTED, the others add to `deferred`;
+ *     2. marker i lies in cell (cx, cy) = (floorf(x), floorf(y)) and there in sub-cell sx = min((int)floorf((x - (float)cx) * 4.f), 3), sy alike (both operations
+ *        are exact);
+ *     3. in each of the 16 sub-cells of a listed cell the marker with the lowest array index survives, every other marker of a listed cell is deleted;
+ *     4. the deletion is the reference's loop m[i--] = m[--n] (main.c:105-116) over delete flags computed before it begins, each travelling with its marker;
+ *     5. count of a listed cell becomes the number of its occupied sub-cells (>= 1); prev_count and every other grid stay.
+ *   filling (fill_holes), behind the thinning
+ *     1. a hole is an interior cell with count == 0 && prev_count != 0, neither solid nor sink nor source, whose eight neighbours all have count != 0 || solid;
+ *     2. the first max_fill holes in row-major order are listed, the others add to `deferred`;
+ *     3. listed hole k appends one marker at (x + rx, y + ry), ry = draw 2 k and rx = draw 2 k + 1 of the handle's one stream from where it stands (the order of
+ *        update_fluid_sources, main.c:288), and its count becomes 1; appending stops when the array holds max_markers - 1 markers (the holes left over add to
+ *        `deferred`; the source stage's latch is not written);
+ *     4. u, v, the dye and the temperature are untouched: the cell was water one refresh ago, its samples stand, and no extrapolation fires (prev_count != 0).
+ * Tracers and dye are not pushed.  The settings survive a scenario load and euler_load_state like the options; they are not part of a snapshot. */
+typedef struct euler_reseed {      /* 32 bytes, no padding */
+  int32_t thin_above;   /* 0: no thinning; else 4 ... 254: a cell whose count byte exceeds it is thinned */
+  int32_t fill_holes;   /* 0 / 1 */
+  int32_t max_cells;    /* crowded cells thinned per pass; 0 = 65536; at most 1 << 20 */
+  int32_t max_fill;     /* holes filled per pass;           0 = 65536; at most 1 << 20 */
+  int32_t reserved[4];  /* 0 */
+} euler_reseed;
+typedef struct euler_reseed_stats { uint64_t removed, added, cells_thinned, deferred; } euler_reseed_stats;   /* totals since the last euler_set_reseed */
+/* NULL or an all-zero record switches the pass off.  Refusals, in this order: a null sim (EULER_EINVAL); a row-slab handle (EULER_ESTATE); nothing loaded
+ * (EULER_ESTATE); then EULER_EINVAL with the field named: reserved not 0; thin_above not 0 and outside [4, 254]; fill_holes outside {0, 1}; max_cells or max_fill
+ * negative or above 1 << 20.  A refused call changes and allocates nothing.  An accepted one zeroes the totals. */
+int euler_set_reseed(euler_sim* sim, const euler_reseed* r);
+/* The record as set (all zero: off; the limits as given, 0 where the default stands) and the totals; either pointer may be NULL. */
+int euler_get_reseed(euler_sim* sim, euler_reseed* r, euler_reseed_stats* stats);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
