@@ -490,14 +490,6 @@ int  eu_launch_coarse_add_row(euler_sim* S, double* row, int yrow);   // row sla
 
 #define EU_WAVE 64
 
-struct GridRef {
-  int X, Y;
-  const uint8_t* count;   // g_fluid alias (main.c:99)
-  float ux_lim, uy_lim, vx_lim, vy_lim;
-};
-
-// typed cell property (p_property/u_property/v_property, main.c:119-138)
-__device__ __forceinline__ bool eu_prop_p(const uint8_t* g, size_t i) { return g[i] != 0; }
 // the tile map (euler_sim.tmap): no water in the tiles (ty, tx0 .. tx0 + ntx - 1), the tile to their right and the row of tiles above them - in the count grid and in the
 // previous one.  Uniform over a workgroup when its arguments are (scalar loads).  Column tnx - 1 and the rows behind the grid's last tile row are a ring of zeros.
 __device__ __forceinline__ bool eu_tiles_idle(const uint8_t* __restrict__ tmap, int tnx, int tn, int ty, int tx0, int ntx) {
@@ -518,133 +510,7 @@ __device__ __forceinline__ bool eu_tiles_idle_cur(const uint8_t* __restrict__ tm
   }
   return a == 0;
 }
-__device__ __forceinline__ bool eu_prop_u(const uint8_t* g, size_t i) { return (g[i] != 0) | (g[i + 1] != 0); }
-__device__ __forceinline__ bool eu_prop_v(const uint8_t* g, size_t i, int X) { return (g[i] != 0) | (g[i + X] != 0); }
-
-__device__ __forceinline__ float eu_lerp(float x0, float x1, float f) { return (1.f - f) * x0 + f * x1; }   // main.c:311-313
-__device__ __forceinline__ float eu_frac(float f, bool start_ok, bool end_ok) {                            // main.c:301-309
-  return !start_ok ? 1.f : (!end_ok ? 0.f : f);
-}
-__device__ __forceinline__ float eu_clampf(float lo, float x, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// interpolate(), main.c:337-364.  TYPE 0 = cell centres (P), 1 = U samples, 2 = V samples.
-// CONSUMERS of the transposed inputs (TR): uT, vT and countT are left UNWRITTEN over tiles without water (k_transpose_for_markers, lean - eu_valid.h countT_clean), so a
-// sample of q is valid only where its bit of the props byte is set; the bytes over an idle tile are the zeros an earlier full pass left, its samples are whatever was there.
-// Read a sample without its bit and the lean and the plain form stop giving the same bits.
-// TR: q and g.count are stored COLUMN-major, [x][y] (the marker stage's copies: k_markers.hip) - the same values, the strides swapped
-// PROPS: g.count does not hold counts but, per cell, the typed fluid properties of the four corners of an interpolation whose BASE cell it is (bits 0-3 U-typed, 4-7 V-typed,
-// corner order v00 v01 v10 v11; k_transpose_for_markers): one byte gather instead of six
-template <int TYPE, bool TR = false, bool PROPS = TR>
-__device__ __forceinline__ float eu_interp(const GridRef& g, const float* __restrict__ q, float ix, float iy) {
-  ix = eu_clampf(0.f, ix, TYPE == 1 ? g.ux_lim : g.vx_lim);   // P extent = (X, Y): x like V, y like U
-  iy = eu_clampf(0.f, iy, TYPE == 2 ? g.vy_lim : g.uy_lim);
-  float wx, wy;
-  const float fx = modff(ix, &wx), fy = modff(iy, &wy);
-  const int bx = (int)wx, by = (int)wy;
-  const size_t sx = TR ? (size_t)g.Y : (size_t)1, sy = TR ? (size_t)1 : (size_t)g.X;      // one step in x / in y
-  const size_t i00 = (size_t)by * sy + (size_t)bx * sx;
-  // the four samples are loaded unconditionally and next to the mask bytes (the clamps keep all of them inside the arrays,
-  // ghost rows included): one memory round trip instead of two - the kernels that interpolate are latency-bound
-  const float r00 = q[i00], r01 = q[i00 + sx], r10 = q[i00 + sy], r11 = q[i00 + sy + sx];
-  bool v00, v01, v10, v11;
-  if (PROPS && TYPE != 0) {
-    // ONE byte instead of six counts - the passes that interpolate are bound by their gather instructions and the lines each touches
-    const unsigned int nb = g.count[i00] >> (TYPE == 1 ? 0 : 4);
-    v00 = (nb & 1u) != 0; v01 = (nb & 2u) != 0; v10 = (nb & 4u) != 0; v11 = (nb & 8u) != 0;
-  } else
-  if (TYPE == 0) {
-    v00 = g.count[i00] != 0; v01 = g.count[i00 + sx] != 0;
-    v10 = g.count[i00 + sy] != 0; v11 = g.count[i00 + sy + sx] != 0;
-  } else if (TYPE == 1) {
-    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0, c2 = g.count[i00 + 2 * sx] != 0;
-    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0, d2 = g.count[i00 + sy + 2 * sx] != 0;
-    v00 = c0 | c1; v01 = c1 | c2; v10 = d0 | d1; v11 = d1 | d2;
-  } else {
-    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0;
-    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0;
-    const bool e0 = g.count[i00 + 2 * sy] != 0, e1 = g.count[i00 + 2 * sy + sx] != 0;
-    v00 = c0 | d0; v01 = c1 | d1; v10 = d0 | e0; v11 = d1 | e1;
-  }
-  const float q00 = v00 ? r00 : 0.f, q01 = v01 ? r01 : 0.f;
-  const float q10 = v10 ? r10 : 0.f, q11 = v11 ? r11 : 0.f;
-  const float lf = eu_frac(fy, v00, v10), rf = eu_frac(fy, v01, v11);
-  const float lv = eu_lerp(q00, q10, lf), rv = eu_lerp(q01, q11, rf);
-  const float hf = eu_frac(fx, v00 | v10, v01 | v11);
-  return eu_lerp(lv, rv, hf);
-}
-
-// EULER_OPT_ADVECT_MACCORMACK (docs/advection_maccormack.md): eu_interp<TYPE> over row-major q with the count masks - the same value, the same expression forms - that
-// also reports whether any corner is valid and, with LIM, the min (lo) and max (hi) of q over the valid corners, folded in the order 00, 01, 10, 11 with strict compares
-template <int TYPE, bool LIM>
-__device__ __forceinline__ float eu_interp_mc(const GridRef& g, const float* __restrict__ q, float ix, float iy, bool& any, float& lo, float& hi) {
-  ix = eu_clampf(0.f, ix, TYPE == 1 ? g.ux_lim : g.vx_lim);
-  iy = eu_clampf(0.f, iy, TYPE == 2 ? g.vy_lim : g.uy_lim);
-  float wx, wy;
-  const float fx = modff(ix, &wx), fy = modff(iy, &wy);
-  const int bx = (int)wx, by = (int)wy;
-  const size_t sx = 1, sy = (size_t)g.X;
-  const size_t i00 = (size_t)by * sy + (size_t)bx * sx;
-  const float r00 = q[i00], r01 = q[i00 + sx], r10 = q[i00 + sy], r11 = q[i00 + sy + sx];
-  bool v00, v01, v10, v11;
-  if (TYPE == 0) {
-    v00 = g.count[i00] != 0; v01 = g.count[i00 + sx] != 0;
-    v10 = g.count[i00 + sy] != 0; v11 = g.count[i00 + sy + sx] != 0;
-  } else if (TYPE == 1) {
-    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0, c2 = g.count[i00 + 2 * sx] != 0;
-    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0, d2 = g.count[i00 + sy + 2 * sx] != 0;
-    v00 = c0 | c1; v01 = c1 | c2; v10 = d0 | d1; v11 = d1 | d2;
-  } else {
-    const bool c0 = g.count[i00] != 0, c1 = g.count[i00 + sx] != 0;
-    const bool d0 = g.count[i00 + sy] != 0, d1 = g.count[i00 + sy + sx] != 0;
-    const bool e0 = g.count[i00 + 2 * sy] != 0, e1 = g.count[i00 + 2 * sy + sx] != 0;
-    v00 = c0 | d0; v01 = c1 | d1; v10 = d0 | e0; v11 = d1 | e1;
-  }
-  any = v00 | v01 | v10 | v11;
-  if (LIM) {
-    lo = __builtin_inff(); hi = -__builtin_inff();
-    if (v00) { lo = r00 < lo ? r00 : lo; hi = r00 > hi ? r00 : hi; }
-    if (v01) { lo = r01 < lo ? r01 : lo; hi = r01 > hi ? r01 : hi; }
-    if (v10) { lo = r10 < lo ? r10 : lo; hi = r10 > hi ? r10 : hi; }
-    if (v11) { lo = r11 < lo ? r11 : lo; hi = r11 > hi ? r11 : hi; }
-  }
-  const float q00 = v00 ? r00 : 0.f, q01 = v01 ? r01 : 0.f;
-  const float q10 = v10 ? r10 : 0.f, q11 = v11 ? r11 : 0.f;
-  const float lf = eu_frac(fy, v00, v10), rf = eu_frac(fy, v01, v11);
-  const float lv = eu_lerp(q00, q10, lf), rv = eu_lerp(q01, q11, rf);
-  const float hf = eu_frac(fx, v00 | v10, v01 | v11);
-  return eu_lerp(lv, rv, hf);
-}
-// out = f + 0.5 (q0 - b), clamped to [lo, hi]; f alone where the forward or the backward interpolation had no valid corner
-__device__ __forceinline__ float eu_mc_correct(float f, float q0, float b, bool a1, bool a2, float lo, float hi) {
-  if (!(a1 && a2)) return f;
-  const float out = f + 0.5f * (q0 - b);
-  return out < lo ? lo : (out > hi ? hi : out);
-}
-
-// EULER_OPT_ADVECT_RK2 (docs/advection_rk2.md): the midpoint rule.  The start-point velocity (d0x, d0y) at index (x, y) of the given index space is carried half a step,
-// hdt = 0.5f * dt, back; the velocity interpolated there replaces it in the unchanged back-trace.  Index spaces (EU_H = 1): a position maps to u index pos - (1, 0.5),
-// v index pos - (0.5, 1), p index pos - (0.5, 0.5).  The two gathers of each helper do not depend on each other: they are issued together.
-template <bool TR = false>
-__device__ __forceinline__ float2 eu_mid_vel_uidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
-  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
-  return make_float2(eu_interp<1, TR>(g, u, mx, my), eu_interp<2, TR>(g, v, mx + 0.5f, my - 0.5f));      // (vidx_from_u)
-}
-template <bool TR = false>
-__device__ __forceinline__ float2 eu_mid_vel_vidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
-  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
-  return make_float2(eu_interp<1, TR>(g, u, mx - 0.5f, my + 0.5f), eu_interp<2, TR>(g, v, mx, my));      // (uidx_from_v)
-}
-template <bool TR = false>
-__device__ __forceinline__ float2 eu_mid_vel_pidx(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float x, float y, float d0x, float d0y, float hdt) {
-  const float mx = x - d0x * hdt / EU_H, my = y - d0y * hdt / EU_H;
-  return make_float2(eu_interp<1, TR>(g, u, mx - 0.5f, my), eu_interp<2, TR>(g, v, mx, my - 0.5f));
-}
-// a marker: velocity_at (main.c:440-449) half a step FORWARD from position (px, py)
-template <bool TR = false>
-__device__ __forceinline__ float2 eu_mid_vel_pos(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v, float px, float py, float v0x, float v0y, float hdt) {
-  const float mx = px + hdt * v0x, my = py + hdt * v0y;
-  return make_float2(eu_interp<1, TR>(g, u, mx / EU_H - 1.f, my / EU_H - 0.5f), eu_interp<2, TR>(g, v, mx / EU_H - 0.5f, my / EU_H - 1.f));
-}
+// (the interpolation, the midpoint rule, the back-trace and GridRef: k_transport.h)
 
 // xorshift64* (misc/rng.c:5-20) jump-ahead.  The state update x ^= x >> 12; x ^= x << 25; x ^= x >> 27 is linear over GF(2):
 // one step is a 64 x 64 bit matrix M, k steps are M^k.  jump[i][b] = M^(2^i) e_b (the image of bit b), filled once on the

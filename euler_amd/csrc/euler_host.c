@@ -473,12 +473,14 @@ int euler_heat_paint(const euler_heat_px* heat, euler_overview_px* px, int32_t W
 
 /* ---- batched gauges: the list checked, cut into chunks, and the values read off a record (include/euler.h, docs/gauges.md) ---- */
 
+int eu_interior_box_ok(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y) { return !(x0 < 1 || y0 < 1 || x1 > X - 2 || y1 > Y - 2 || x0 > x1 || y0 > y1); }
+
 int eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what) {
   for (int32_t k = 0; k < n; ++k) {
     const char* w = NULL;
     if (g[k].kind < EULER_GAUGE_LEVEL || g[k].kind > EULER_GAUGE_FLUX) w = "an unknown kind";
     else if (g[k].reserved != 0) w = "reserved is not 0";
-    else if (g[k].x0 < 1 || g[k].y0 < 1 || g[k].x1 > X - 2 || g[k].y1 > Y - 2 || g[k].x0 > g[k].x1 || g[k].y0 > g[k].y1) w = "its box is not inside the interior";
+    else if (!eu_interior_box_ok(g[k].x0, g[k].y0, g[k].x1, g[k].y1, X, Y)) w = "its box is not inside the interior";
     if (w) { if (what) *what = w; return k; }
   }
   return -1;
@@ -721,7 +723,7 @@ int eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32
     if (!force_value_ok(boxes[k].fx) || !force_value_ok(boxes[k].fy)) REFUSE("box %d: force (%g, %g) must be finite and at most 1e4 in size", k, (double)boxes[k].fx, (double)boxes[k].fy);
   for (int32_t k = 0; k < f->nboxes; ++k) {
     const euler_force_box* b = boxes + k;
-    if (b->x0 < 1 || b->y0 < 1 || b->x1 > X - 2 || b->y1 > Y - 2 || b->x0 > b->x1 || b->y0 > b->y1)
+    if (!eu_interior_box_ok(b->x0, b->y0, b->x1, b->y1, X, Y))
       REFUSE("box %d: [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", k, b->x0, b->x1, b->y0, b->y1, X - 2, Y - 2);
   }
 #undef REFUSE
@@ -730,14 +732,16 @@ int eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32
 
 /* (eu_gauge_chunks cuts every box for itself, a tile that n boxes touch n times; here a tile comes once and carries its boxes, so the tiles' bit sets are formed
  * over the tile grid and the touched ones listed row by row) */
-size_t eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
+size_t eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
   if (n < 1) return 0;
   const int32_t tnx = (X + 63) >> 6, tny = (Y + 63) >> 6;
   uint64_t* set = (uint64_t*)calloc((size_t)tnx * (size_t)tny, sizeof(uint64_t));
   if (!set) return (size_t)-1;
-  for (int32_t k = 0; k < n; ++k)
-    for (int32_t ty = b[k].y0 >> 6; ty <= b[k].y1 >> 6; ++ty)
-      for (int32_t tx = b[k].x0 >> 6; tx <= b[k].x1 >> 6; ++tx) set[(size_t)ty * tnx + tx] |= 1ull << k;
+  for (int32_t k = 0; k < n; ++k) {
+    const int32_t* r = (const int32_t*)((const char*)boxes + (size_t)k * stride);      /* x0, y0, x1, y1 */
+    for (int32_t ty = r[1] >> 6; ty <= r[3] >> 6; ++ty)
+      for (int32_t tx = r[0] >> 6; tx <= r[2] >> 6; ++tx) set[(size_t)ty * tnx + tx] |= 1ull << k;
+  }
   size_t m = 0;
   for (int32_t ty = 0; ty < tny; ++ty)
     for (int32_t tx = 0; tx < tnx; ++tx) {
@@ -892,7 +896,7 @@ int eu_reseed_pass(const euler_reseed* r, int32_t X, int32_t Y, float* m, uint64
   return EULER_OK;
 }
 
-/* ---- temperature: the record's defaults, the record and the list checked, the list cut into the force boxes' tile table (include/euler.h, docs/heat.md) ---- */
+/* ---- temperature: the record's defaults, the record and the list checked, the boxes' tile table is eu_force_tiles' (include/euler.h, docs/heat.md) ---- */
 
 int euler_heat_default(euler_heat* h) {
   if (!h) return EULER_EINVAL;
@@ -903,7 +907,7 @@ int euler_heat_default(euler_heat* h) {
 int eu_heat_value_ok(float x) { return force_value_ok(x); }
 
 int eu_heat_box_check(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y, char* why, size_t cap) {
-  if (x0 < 1 || y0 < 1 || x1 > X - 2 || y1 > Y - 2 || x0 > x1 || y0 > y1) {
+  if (!eu_interior_box_ok(x0, y0, x1, y1, X, Y)) {
     if (why && cap) snprintf(why, cap, "[%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", x0, x1, y0, y1, X - 2, Y - 2);
     return EULER_EINVAL;
   }
@@ -928,16 +932,6 @@ int eu_heat_check(const euler_heat* h, const euler_heat_box* boxes, int32_t X, i
   }
 #undef REFUSE
   return EULER_OK;
-}
-
-size_t eu_heat_tiles(const euler_heat_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
-  if (n < 1) return 0;
-  euler_force_box* fb = (euler_force_box*)calloc((size_t)n, sizeof *fb);
-  if (!fb) return (size_t)-1;
-  for (int32_t k = 0; k < n; ++k) { fb[k].x0 = b[k].x0; fb[k].y0 = b[k].y0; fb[k].x1 = b[k].x1; fb[k].y1 = b[k].y1; }
-  const size_t m = eu_force_tiles(fb, n, X, Y, out);
-  free(fb);
-  return m;
 }
 
 int euler_gauge_derive(const euler_gauge_rec* rec, int32_t kind, euler_gauge_values* out) {

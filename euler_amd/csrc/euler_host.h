@@ -15,6 +15,7 @@ int      euler_seed_markers_rows(const uint8_t* fluid, int32_t X, int32_t Y, int
 #define EULER_RNG_SEED 0x9bd185c449534b91ull /* main.c:204 */
 /* euler_gauges (k_gauges.hip, docs/gauges.md): the list checked and cut along the 64 x 64 tile grid.  A chunk lies in one tile, hence in one band of the skewed arrays */
 typedef struct eu_gauge_chunk { int32_t gauge, kind, x0, y0, x1, y1; } eu_gauge_chunk;
+int      eu_interior_box_ok(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y);   /* 1 <= x0 <= x1 <= X - 2 and 1 <= y0 <= y1 <= Y - 2: the test behind every box a caller hands in */
 int      eu_gauge_check(const euler_gauge* g, int32_t n, int32_t X, int32_t Y, const char** what);   /* the index of the first gauge refused (what: why), -1: none */
 size_t   eu_gauge_chunks(const euler_gauge* g, int32_t n, eu_gauge_chunk* out);   /* out == NULL: the count only; the list must have passed eu_gauge_check */
 /* ... and only the chunks of the 64-row bands [band_lo, band_hi), in the order eu_gauge_chunks lists them: a chunk lies in one band, so over the ranks of a
@@ -46,11 +47,12 @@ int      eu_slab_plan_contributors(const eu_slab_plan* P, int32_t py, int32_t* f
  * tile that any box touches, with the boxes that touch it as a bit set - bit k = box k, walked from bit 0 up: the ascending list (at most 64 boxes) */
 typedef struct eu_force_tile { int32_t tx, ty; uint64_t boxes; } eu_force_tile;
 int      eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
-size_t   eu_force_tiles(const euler_force_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);   /* out == NULL: the count only; the list must have passed eu_forcing_check; (size_t)-1: no memory */
+/* boxes: n records `stride` bytes apart that begin with x0, y0, x1, y1 as four int32_t (euler_force_box, euler_heat_box); out == NULL: the count only; the list must
+ * have passed its check; (size_t)-1: no memory */
+size_t   eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);
 /* euler_set_heat (k_heat.hip, docs/heat.md): refusals 4 - 9 of include/euler.h in their order - the ones that need no device; live: the ambient of a handle whose
- * heat is on (NULL: off, any ambient passes).  The tile table of the heat boxes is the force boxes': eu_heat_tiles hands the boxes' places to eu_force_tiles */
+ * heat is on (NULL: off, any ambient passes).  The tile table of the heat boxes is the force boxes': eu_force_tiles with the stride of euler_heat_box */
 int      eu_heat_check(const euler_heat* h, const euler_heat_box* boxes, int32_t X, int32_t Y, const float* live, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
-size_t   eu_heat_tiles(const euler_heat_box* b, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);   /* as eu_force_tiles */
 /* the refusals of euler_heat_fill / euler_heat_set_field that need no device: the box, the value */
 int      eu_heat_box_check(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t X, int32_t Y, char* why, size_t cap);
 int      eu_heat_value_ok(float x);   /* finite and at most 1e4 in size */

@@ -3,6 +3,7 @@
 // k_markers.hip's; here a caller gets the marker's new position and the collision it would report (theta, delta, events).
 #pragma once
 #include "euler_dev.h"
+#include "k_transport.h"
 
 #include <float.h>
 
@@ -20,7 +21,7 @@ __device__ __forceinline__ float time_to(float p0, float p1, float vel) {   // m
 // <= 0.375 cells from p and the displacement stays <= 0.75 cells: still at most one boundary per axis.  With TR, uT / vT are not refreshed in tiles the last copy left
 // alone (k_transpose_for_markers, lean): such stale samples are never read here either - eu_interp<.., TR> uses a sample only where its corner bit in countT is set, and
 // that bit belongs to the sample's cell, not to the query point, so a midpoint lookup sees exactly the live samples a start-point lookup there would.
-// (The rule for any new reader of uT / vT / countT: euler_dev.h eu_interp, docs/stage_validity.md.)
+// (The rule for any new reader of uT / vT / countT: k_transport.h eu_interp, docs/stage_validity.md.)
 template <bool TR, bool RK2>
 __device__ __forceinline__ AdvectOut advect_one(const GridRef& g, const float* __restrict__ u, const float* __restrict__ v,
                                                 const uint8_t* __restrict__ solid, float px, float py, float dt, float dt_mid) {

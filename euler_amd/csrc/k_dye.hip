@@ -4,6 +4,7 @@
 // (advect_p + the whole-array memcpy, main.c:424-438, 873-882).  Cosmetic: nothing here feeds back
 // into the flow.  Element-wise gathers over row-major arrays, the three channels share one launch.
 #include "euler_dev.h"
+#include "k_transport.h"
 
 // misc/color.h:16-34: period 6, values in [0, 1]
 __device__ __forceinline__ float hsv_basis(float t) {
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void k_dye_sources(float* r, float* g, float* 
 }
 
 // advect_p (main.c:424-438) for the three channels; only fluid cells of the outputs are written.  RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the
-// velocity at the midpoint of the face average (euler_dev.h eu_mid_vel_pidx)
+// velocity at the midpoint of the face average (k_transport.h eu_trace)
 template <bool RK2>
 __global__ __launch_bounds__(256) void k_advect_dye(const float* __restrict__ r, const float* __restrict__ g,
                                                     const float* __restrict__ b, float* __restrict__ rout,
@@ -75,13 +76,12 @@ __global__ __launch_bounds__(256) void k_advect_dye(const float* __restrict__ r,
   if (x >= X || y >= y1) return;
   const size_t i = (size_t)y * X + x;
   if (!gr.count[i]) return;                     // never fluid on the border ring (all sink): i - X, i - 1 exist
-  float dy = (v[i] + v[i - X]) / 2;
-  float dx = (u[i] + u[i - 1]) / 2;
-  if (RK2) { const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
-  const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
-  rout[i] = eu_interp<0>(gr, r, px, py);
-  gout[i] = eu_interp<0>(gr, g, px, py);
-  bout[i] = eu_interp<0>(gr, b, px, py);
+  const float dy = (v[i] + v[i - X]) / 2;
+  const float dx = (u[i] + u[i - 1]) / 2;
+  const EuTrace t = eu_trace<EU_SPACE_P, RK2, false>(gr, u, v, (float)x, (float)y, dx, dy, dt);
+  rout[i] = eu_interp<0>(gr, r, t.px, t.py);
+  gout[i] = eu_interp<0>(gr, g, t.px, t.py);
+  bout[i] = eu_interp<0>(gr, b, t.px, t.py);
 }
 
 // EULER_OPT_ADVECT_MACCORMACK, the correction pass of one or two channels (q1 null: one) behind k_advect_dye<RK2> (docs/advection_maccormack.md): per fluid cell the forward
@@ -101,28 +101,11 @@ __global__ __launch_bounds__(256) void k_mc_correct_dye(const float* __restrict_
     if (q1) out1[i] = qf1[i];
     return;
   }
-  const float dy0 = (v[i] + v[i - X]) / 2;
-  const float dx0 = (u[i] + u[i - 1]) / 2;
-  const float bdt = -dt;
-  float fdx = dx0, fdy = dy0, bdx = dx0, bdy = dy0;
-  if (RK2) {
-    const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * dt); fdx = m.x; fdy = m.y;
-    const float2 n = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * bdt); bdx = n.x; bdy = n.y;
-  }
-  const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
-  const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
-  bool a1, a2;
-  float lo, hi;
-  {
-    const float f = eu_interp_mc<0, true>(gr, q0, px, py, a1, lo, hi);
-    const float b = eu_interp_mc<0, false>(gr, qf0, qx, qy, a2, lo, hi);
-    out0[i] = eu_mc_correct(f, q0[i], b, a1, a2, lo, hi);
-  }
-  if (q1) {
-    const float f = eu_interp_mc<0, true>(gr, q1, px, py, a1, lo, hi);
-    const float b = eu_interp_mc<0, false>(gr, qf1, qx, qy, a2, lo, hi);
-    out1[i] = eu_mc_correct(f, q1[i], b, a1, a2, lo, hi);
-  }
+  const float dy = (v[i] + v[i - X]) / 2;
+  const float dx = (u[i] + u[i - 1]) / 2;
+  const EuTrace t = eu_trace<EU_SPACE_P, RK2, true>(gr, u, v, (float)x, (float)y, dx, dy, dt);
+  out0[i] = eu_mc_value<0>(gr, q0, qf0, q0[i], t);
+  if (q1) out1[i] = eu_mc_value<0>(gr, q1, qf1, q1[i], t);
 }
 
 static inline dim3 cell_grid(const euler_sim* S) { return dim3((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4); }   // this rank's rows (all of them without slabs)
@@ -150,29 +133,24 @@ int eu_launch_dye_sources(euler_sim* S) {
 
 int eu_launch_dye_advect(euler_sim* S, float dt) {
   if (!S->dye[0]) return EULER_OK;
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
-  if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye<true>, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
+  const GridRef g = eu_grid_ref(S);
+  const bool rk2 = S->opt[EULER_OPT_ADVECT_RK2] != 0;      // (never on a row slab: euler_set_option refuses it there)
+  eu_flag(rk2, [&](auto R) {
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye<decltype(R)::value>, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
            S->u, S->v, g, dt, S->row_lo, S->row_hi);
-  else
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_dye<false>, cell_grid(S), dim3(256), S->dye[0], S->dye[1], S->dye[2], S->dye[3], S->dye[4], S->dye[5],
-           S->u, S->v, g, dt, S->row_lo, S->row_hi);
+  });
   // memcpy(g_r, g_rtmp, sizeof(g_r)) x3 (main.c:875,878,881): the WHOLE scratch array, stale non-fluid entries included (a row slab: its own rows)
   const size_t o = (size_t)S->row_lo * S->X, n = (size_t)(S->row_hi - S->row_lo) * S->X;
   if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (a whole-grid handle): the corrected r, g into the velocity scratch, copied over the old ones; then b the same way
     float* sc[2] = {S->mc_u, S->mc_v};
-    if (S->opt[EULER_OPT_ADVECT_RK2]) {
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<true>, cell_grid(S), dim3(256), S->dye[0], S->dye[3], sc[0], S->dye[1], S->dye[4], sc[1], S->u, S->v, g, dt, S->row_lo, S->row_hi);
-    } else {
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<false>, cell_grid(S), dim3(256), S->dye[0], S->dye[3], sc[0], S->dye[1], S->dye[4], sc[1], S->u, S->v, g, dt, S->row_lo, S->row_hi);
-    }
+    auto correct = [&](const float* q0, const float* qf0, float* out0, const float* q1, const float* qf1, float* out1) {
+      eu_flag(rk2, [&](auto R) {
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<decltype(R)::value>, cell_grid(S), dim3(256), q0, qf0, out0, q1, qf1, out1, S->u, S->v, g, dt, S->row_lo, S->row_hi);
+      });
+    };
+    correct(S->dye[0], S->dye[3], sc[0], S->dye[1], S->dye[4], sc[1]);
     for (int k = 0; k < 2; ++k) HIPCHK(hipMemcpyAsync(S->dye[k] + o, sc[k] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
-    const float* none = nullptr;
-    if (S->opt[EULER_OPT_ADVECT_RK2]) {
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<true>, cell_grid(S), dim3(256), S->dye[2], S->dye[5], sc[0], none, none, (float*)nullptr, S->u, S->v, g, dt, S->row_lo, S->row_hi);
-    } else {
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_dye<false>, cell_grid(S), dim3(256), S->dye[2], S->dye[5], sc[0], none, none, (float*)nullptr, S->u, S->v, g, dt, S->row_lo, S->row_hi);
-    }
+    correct(S->dye[2], S->dye[5], sc[0], nullptr, nullptr, nullptr);
     HIPCHK(hipMemcpyAsync(S->dye[2] + o, sc[0] + o, n * sizeof(float), hipMemcpyDeviceToDevice, S->stream));
     return EULER_OK;
   }

@@ -14,6 +14,7 @@
 // nothing else is written - no validity flag changes (docs/stage_validity.md).  With the tile map a tile leaves at once when it, the tile right of it and the tile
 // above it are dry: then no cell of it has a live face.
 #include "k_observe.h"
+#include "k_boxes.h"
 #include "euler_host.h"
 
 #include <math.h>
@@ -37,13 +38,7 @@ __global__ __launch_bounds__(FO_T) void k_force_boxes(float* __restrict__ utmp, 
   const int x = t.tx * 64 + (int)(threadIdx.x & 63);
   for (int r = 0; r < 64 / (FO_T / 64); ++r) {
     const int y = t.ty * 64 + r * (FO_T / 64) + (int)(threadIdx.x >> 6);
-    // the cell lies in some box of the tile: only then is it inside the interior and may anything be read
-    bool in = false;
-    for (unsigned long long m = t.boxes; m; m &= m - 1) {
-      const euler_force_box b = boxes[__ffsll((long long)m) - 1];
-      in |= x >= b.x0 && x <= b.x1 && y >= b.y0 && y <= b.y1;
-    }
-    if (!in) continue;
+    if (!eu_boxes_hold(boxes, t.boxes, x, y)) continue;
     const size_t i = (size_t)y * (size_t)X + (size_t)x;
     const bool cn = count[i] != 0, so = solid[i] != 0;
     const bool live_u = (cn | (count[i + 1] != 0)) && !(so | (solid[i + 1] != 0));
@@ -78,24 +73,10 @@ extern "C" int euler_set_forcing(euler_sim* S, const euler_forcing* f, const eul
   char why[256];
   if (eu_forcing_check(f, boxes, S->X, S->Y, why, sizeof why)) { eu_set_error("%s: %s", who, why); return EULER_EINVAL; }
   if (f->nboxes > 0) {
-    const size_t ntiles = eu_force_tiles(boxes, f->nboxes, S->X, S->Y, nullptr);
-    const size_t bytes = FO_BOX_BYTES + (ntiles == (size_t)-1 ? 0 : ntiles) * sizeof(eu_force_tile);
-    char* st = ntiles == (size_t)-1 ? nullptr : (char*)calloc(1, bytes);
-    if (!st || eu_force_tiles(boxes, f->nboxes, S->X, S->Y, (eu_force_tile*)(st + FO_BOX_BYTES)) != ntiles) {
-      free(st);
-      eu_set_error("%s: host memory for the tile table", who);
-      return EULER_ENOMEM;
-    }
-    memcpy(st, boxes, (size_t)f->nboxes * sizeof(euler_force_box));
-    int rc = eu_devbuf_reserve(S, who, "the boxes and the tile table", &S->force_buf, bytes);
-    // (the copy queues behind the substeps that still read the old table; the host's copy is freed once it has gone up)
-    if (!rc) {
-      const hipError_t e1 = hipMemcpyAsync(S->force_buf.p, st, bytes, hipMemcpyHostToDevice, S->stream), e2 = hipStreamSynchronize(S->stream);
-      if (e1 != hipSuccess || e2 != hipSuccess) rc = eu_hip_fail(e1 != hipSuccess ? e1 : e2, "the copy of the boxes and the tile table", __FILE__, __LINE__);
-    }
-    free(st);
+    unsigned int ntiles = 0;
+    const int rc = eu_box_table_upload(S, who, &S->force_buf, boxes, f->nboxes, sizeof(euler_force_box), EULER_FORCE_BOXES_MAX, &ntiles);
     if (rc) return rc;
-    S->force_ntiles = (unsigned int)ntiles;
+    S->force_ntiles = ntiles;
     memcpy(S->force_boxes, boxes, (size_t)f->nboxes * sizeof(euler_force_box));
   } else S->force_ntiles = 0;
   S->forcing = *f;

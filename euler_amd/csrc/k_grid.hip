@@ -3,6 +3,7 @@
 // assembly and the post-solve velocity update.  All are embarrassingly parallel gathers with
 // coalesced row-major access; none has a floating-point reduction except the exact max.
 #include "k_pcg.h"
+#include "k_transport.h"
 
 #include <stdlib.h>
 
@@ -248,7 +249,7 @@ int eu_launch_extrapolate(euler_sim* S) {
 // outputs (main.c:888-889), fused: what reaches utmp/vtmp equals the reference's arrays after its
 // second zero_bounds pair (non-fluid or solid faces are 0, so the reference's stale entries and the
 // gravity it adds to non-fluid faces never survive).
-// RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the midpoint velocity (euler_dev.h eu_mid_vel_*); everything else as it stands
+// RK2 (EULER_OPT_ADVECT_RK2): the back-trace starts from the midpoint velocity (k_transport.h eu_trace); everything else as it stands
 // MC (EULER_OPT_ADVECT_MACCORMACK): the forward pass - the same values without gravity, into the scratch grids that k_mc_correct_velocity reads
 // FORCED (euler_set_forcing, docs/forcing.md): the uniform acceleration (ax, ay) of the substep stands where EU_G stands; a u face is touched only when ax != 0.f
 // (x + 0.f is not x for x = -0.f).  The kernels below are the body under the names and signatures they always had, and under new ones that take (ax, ay).
@@ -271,11 +272,10 @@ __device__ __forceinline__ void advect_velocity_body(const float* __restrict__ u
     if (x < X - 1) {
       float out = 0.f;
       if (eu_prop_u(g.count, i) && !eu_prop_u(solid, i)) {
-        float dx = u[i];
-        float dy = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);                // vidx_from_u, main.c:378-380
-        if (RK2) { const float2 m = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
-        const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;     // main.c:392-393
-        out = eu_interp<1>(g, u, px, py);
+        const float dx = u[i];
+        const float dy = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);          // vidx_from_u, main.c:378-380
+        const EuTrace t = eu_trace<EU_SPACE_U, RK2, false>(g, u, v, (float)x, (float)y, dx, dy, dt);      // main.c:392-393
+        out = eu_interp<1>(g, u, t.px, t.py);
         if (FORCED && !MC && ax != 0.f) out += ax * dt;
       }
       uout[i] = out;
@@ -283,11 +283,10 @@ __device__ __forceinline__ void advect_velocity_body(const float* __restrict__ u
     if (y < Y - 1) {
       float out = 0.f;
       if (eu_prop_v(g.count, i, X) && !eu_prop_v(solid, i, X)) {
-        float dy = v[i];
-        float dx = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);                // uidx_from_v, main.c:401-403
-        if (RK2) { const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
-        const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
-        out = eu_interp<2>(g, v, px, py);
+        const float dy = v[i];
+        const float dx = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);          // uidx_from_v, main.c:401-403
+        const EuTrace t = eu_trace<EU_SPACE_V, RK2, false>(g, u, v, (float)x, (float)y, dx, dy, dt);
+        out = eu_interp<2>(g, v, t.px, t.py);
         if (!MC) out += (FORCED ? ay : EU_G) * dt;                        // main.c:542
       }
       vout[i] = out;
@@ -322,7 +321,6 @@ __device__ __forceinline__ void mc_correct_velocity_body(const float* __restrict
   if (tmap && eu_tiles_idle(tmap, tnx, tn, (y0 + (int)blockIdx.y * 4 * rep) >> 6, (int)blockIdx.x, 1)) return;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   if (x >= X) return;
-  const float bdt = -dt;
   for (int r = 0; r < rep; ++r) {
     const int y = y0 + ((int)blockIdx.y * rep + r) * 4 + (int)(threadIdx.x >> 6);
     if (y >= y1) return;
@@ -332,18 +330,7 @@ __device__ __forceinline__ void mc_correct_velocity_body(const float* __restrict
       if (eu_prop_u(g.count, i) && !eu_prop_u(solid, i)) {
         const float u0 = u[i];
         const float dy0 = eu_interp<2>(g, v, x + 0.5f, y - 0.5f);
-        float fdx = u0, fdy = dy0, bdx = u0, bdy = dy0;
-        if (RK2) {
-          const float2 m = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, u0, dy0, 0.5f * dt); fdx = m.x; fdy = m.y;
-          const float2 n = eu_mid_vel_uidx(g, u, v, (float)x, (float)y, u0, dy0, 0.5f * bdt); bdx = n.x; bdy = n.y;
-        }
-        const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
-        const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
-        bool a1, a2;
-        float lo, hi;
-        const float f = eu_interp_mc<1, true>(g, u, px, py, a1, lo, hi);
-        const float b = eu_interp_mc<1, false>(g, uf, qx, qy, a2, lo, hi);
-        out = eu_mc_correct(f, u0, b, a1, a2, lo, hi);
+        out = eu_mc_value<1>(g, u, uf, u0, eu_trace<EU_SPACE_U, RK2, true>(g, u, v, (float)x, (float)y, u0, dy0, dt));
         if (FORCED && ax != 0.f) out += ax * dt;                          // after the clamp, as gravity
       }
       uout[i] = out;
@@ -353,18 +340,7 @@ __device__ __forceinline__ void mc_correct_velocity_body(const float* __restrict
       if (eu_prop_v(g.count, i, X) && !eu_prop_v(solid, i, X)) {
         const float v0 = v[i];
         const float dx0 = eu_interp<1>(g, u, x - 0.5f, y + 0.5f);
-        float fdx = dx0, fdy = v0, bdx = dx0, bdy = v0;
-        if (RK2) {
-          const float2 m = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx0, v0, 0.5f * dt); fdx = m.x; fdy = m.y;
-          const float2 n = eu_mid_vel_vidx(g, u, v, (float)x, (float)y, dx0, v0, 0.5f * bdt); bdx = n.x; bdy = n.y;
-        }
-        const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
-        const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
-        bool a1, a2;
-        float lo, hi;
-        const float f = eu_interp_mc<2, true>(g, v, px, py, a1, lo, hi);
-        const float b = eu_interp_mc<2, false>(g, vf, qx, qy, a2, lo, hi);
-        out = eu_mc_correct(f, v0, b, a1, a2, lo, hi);
+        out = eu_mc_value<2>(g, v, vf, v0, eu_trace<EU_SPACE_V, RK2, true>(g, u, v, (float)x, (float)y, dx0, v0, dt));
         out += (FORCED ? ay : EU_G) * dt;                                 // main.c:542, after the clamp
       }
       vout[i] = out;
@@ -438,7 +414,7 @@ __global__ __launch_bounds__(256) void k_copy_typed(const float* __restrict__ u,
 }
 
 int eu_launch_advect_velocity(euler_sim* S, float dt) {
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   dim3 grid((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4);
   // (the tile map: utmp / vtmp must be what this kernel left one refresh ago, and nothing but the refresh may have touched the count grids since)
   const bool lean = eu_vd_lean_advect(&S->vd, eu_tile_map_on(S), S->cfg.viscosity > 0.f);
@@ -450,33 +426,22 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   // holds the default record launches what it always launched
   float acc[2] = {0.f, EU_G};
   if (S->force_uniform) (void)euler_forcing_at(&S->forcing, S->time, acc);
-  if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (never on a row slab either; the forward pass skips the same tiles: no mask reads the scratch there)
-    if (S->opt[EULER_OPT_ADVECT_RK2]) {
-      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<true, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-      if (S->force_uniform)
-        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity_forced<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+  const bool mc = S->opt[EULER_OPT_ADVECT_MACCORMACK] != 0, forced = S->force_uniform != 0;
+  eu_flag(S->opt[EULER_OPT_ADVECT_RK2] != 0, [&](auto R) {      // (RK2, MacCormack: never on a row slab - euler_set_option refuses them there)
+    constexpr bool RK2 = decltype(R)::value;
+    if (mc) {      // the forward pass into the scratch grids (it skips the same tiles: no mask reads the scratch there), then the correction
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<RK2, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+      if (forced)
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity_forced<RK2>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
                S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
       else
-        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<true>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
+        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<RK2>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
                S->tmap_nx, S->tmap_n, rep);
-    } else {
-      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<false, true>), grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-      if (S->force_uniform)
-        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity_forced<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
-               S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
-      else
-        LAUNCH(S, KC_ADVECT_VELOCITY, k_mc_correct_velocity<false>, grid, dim3(256), S->u, S->v, S->mc_u, S->mc_v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm,
-               S->tmap_nx, S->tmap_n, rep);
-    }
-  } else if (S->force_uniform) {
-    if (S->opt[EULER_OPT_ADVECT_RK2])
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity_forced<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
+    } else if (forced)
+      LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity_forced<RK2>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
     else
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity_forced<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep, acc[0], acc[1]);
-  } else if (S->opt[EULER_OPT_ADVECT_RK2])      // (never on a row slab: euler_set_option refuses it there)
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<true>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
-  else
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_advect_velocity<false>, grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_advect_velocity<RK2, false>), grid, dim3(256), S->u, S->v, S->utmp, S->vtmp, S->solid, g, dt, S->row_lo, S->row_hi, tm, S->tmap_nx, S->tmap_n, rep);
+  });
   // the force boxes (k_forcing.hip): live faces of utmp / vtmp only, so what the advection leaves for the next pass stands as it is (docs/stage_validity.md)
   if (S->forcing.nboxes > 0) { int rc = eu_launch_force_boxes(S, dt); if (rc) return rc; }
   // the temperature (k_heat.hip): its transport reads u, v before the diffusion extension takes them as scratch; its buoyancy acts on live faces of utmp / vtmp only

@@ -16,6 +16,8 @@
 // Boxes and diffusion touch fluid cells and read fluid neighbours only, so the dry cells' ambient may come with the transport.  No pass here consults the tile map:
 // EULER_OPT_NO_TILE_MAP cannot change a bit.
 #include "k_observe.h"
+#include "k_transport.h"
+#include "k_boxes.h"
 #include "euler_host.h"
 
 #include <math.h>
@@ -80,11 +82,10 @@ __global__ __launch_bounds__(256) void k_heat_advect(const float* __restrict__ t
     if (!FWD) tout[i] = ambient;
     return;
   }
-  float dy = (v[i] + v[i - X]) / 2;
-  float dx = (u[i] + u[i - 1]) / 2;
-  if (RK2) { const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx, dy, 0.5f * dt); dx = m.x; dy = m.y; }
-  const float px = x - dx * dt / EU_H, py = y - dy * dt / EU_H;
-  tout[i] = eu_interp<0>(gr, tin, px, py);
+  const float dy = (v[i] + v[i - X]) / 2;
+  const float dx = (u[i] + u[i - 1]) / 2;
+  const EuTrace t = eu_trace<EU_SPACE_P, RK2, false>(gr, u, v, (float)x, (float)y, dx, dy, dt);
+  tout[i] = eu_interp<0>(gr, tin, t.px, t.py);
 }
 
 // k_mc_correct_dye for T: q the field, qf its forward result; dry cells take ambient
@@ -97,21 +98,10 @@ __global__ __launch_bounds__(256) void k_heat_correct(const float* __restrict__ 
   if (x >= X || y >= gr.Y) return;
   const size_t i = (size_t)y * X + x;
   if (!gr.count[i]) { out[i] = ambient; return; }
-  const float dy0 = (v[i] + v[i - X]) / 2;
-  const float dx0 = (u[i] + u[i - 1]) / 2;
-  const float bdt = -dt;
-  float fdx = dx0, fdy = dy0, bdx = dx0, bdy = dy0;
-  if (RK2) {
-    const float2 m = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * dt); fdx = m.x; fdy = m.y;
-    const float2 n = eu_mid_vel_pidx(gr, u, v, (float)x, (float)y, dx0, dy0, 0.5f * bdt); bdx = n.x; bdy = n.y;
-  }
-  const float px = x - fdx * dt / EU_H, py = y - fdy * dt / EU_H;
-  const float qx = x - bdx * bdt / EU_H, qy = y - bdy * bdt / EU_H;
-  bool a1, a2;
-  float lo, hi;
-  const float f = eu_interp_mc<0, true>(gr, q, px, py, a1, lo, hi);
-  const float b = eu_interp_mc<0, false>(gr, qf, qx, qy, a2, lo, hi);
-  out[i] = eu_mc_correct(f, q[i], b, a1, a2, lo, hi);
+  const float dy = (v[i] + v[i - X]) / 2;
+  const float dx = (u[i] + u[i - 1]) / 2;
+  const EuTrace t = eu_trace<EU_SPACE_P, RK2, true>(gr, u, v, (float)x, (float)y, dx, dy, dt);
+  out[i] = eu_mc_value<0>(gr, q, qf, q[i], t);
 }
 
 // the boxes: one workgroup per table entry, a thread owns its column's every fourth row of the tile.  A cell in some box of the tile lies in the interior
@@ -121,12 +111,7 @@ __global__ __launch_bounds__(256) void k_heat_boxes(float* __restrict__ t, const
   const int x = e.tx * 64 + (int)(threadIdx.x & 63);
   for (int r = 0; r < 16; ++r) {
     const int y = e.ty * 64 + r * 4 + (int)(threadIdx.x >> 6);
-    bool in = false;
-    for (unsigned long long m = e.boxes; m; m &= m - 1) {
-      const euler_heat_box b = boxes[__ffsll((long long)m) - 1];
-      in |= x >= b.x0 && x <= b.x1 && y >= b.y0 && y <= b.y1;
-    }
-    if (!in) continue;
+    if (!eu_boxes_hold(boxes, e.boxes, x, y)) continue;
     const size_t i = (size_t)y * (size_t)X + (size_t)x;
     if (!count[i]) continue;
     float q = t[i];
@@ -257,21 +242,16 @@ static int heat_launch_boxes(euler_sim* S, int cls, const eu_devbuf* buf, unsign
 }
 
 int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]) {
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   const float amb = S->heat.ambient;
-  const bool rk2 = S->opt[EULER_OPT_ADVECT_RK2] != 0;
-  if (S->opt[EULER_OPT_ADVECT_MACCORMACK]) {      // (mc_u came with the option)
-    if (rk2) {
-      LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<true, true>), heat_grid(S), dim3(256), heat_t(S), S->mc_u, S->u, S->v, g, dt, amb);
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_correct<true>, heat_grid(S), dim3(256), heat_t(S), S->mc_u, heat_other(S), S->u, S->v, g, dt, amb);
-    } else {
-      LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<false, true>), heat_grid(S), dim3(256), heat_t(S), S->mc_u, S->u, S->v, g, dt, amb);
-      LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_correct<false>, heat_grid(S), dim3(256), heat_t(S), S->mc_u, heat_other(S), S->u, S->v, g, dt, amb);
-    }
-  } else if (rk2)
-    LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<true, false>), heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->u, S->v, g, dt, amb);
-  else
-    LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<false, false>), heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->u, S->v, g, dt, amb);
+  // MacCormack: the forward result into mc_u (it came with the option), then the correction; else the one pass into the other half
+  eu_flag(S->opt[EULER_OPT_ADVECT_RK2] != 0, [&](auto R) {
+    eu_flag(S->opt[EULER_OPT_ADVECT_MACCORMACK] != 0, [&](auto M) {
+      constexpr bool RK2 = decltype(R)::value, MC = decltype(M)::value;
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<RK2, MC>), heat_grid(S), dim3(256), heat_t(S), MC ? S->mc_u : heat_other(S), S->u, S->v, g, dt, amb);
+      if (MC) LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_correct<RK2>, heat_grid(S), dim3(256), heat_t(S), S->mc_u, heat_other(S), S->u, S->v, g, dt, amb);
+    });
+  });
   S->heat_cur ^= 1;
   if (S->heat.nboxes > 0 && S->heat_ntiles) { int rc = heat_launch_boxes(S, KC_ADVECT_VELOCITY, &S->heat_box_buf, S->heat_ntiles, dt); if (rc) return rc; }
   if (S->heat.kappa > 0.f) {
@@ -286,27 +266,6 @@ int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]) {
 }
 
 // ------------------------------------------------------------------------------------------ the entry points
-// boxes + their tile table into buf (grown on demand), the copy waited for; *ntiles: the table's entries
-static int heat_upload_boxes(euler_sim* S, const char* who, eu_devbuf* buf, const euler_heat_box* boxes, int32_t n, unsigned int* ntiles) {
-  const size_t nt = eu_heat_tiles(boxes, n, S->X, S->Y, nullptr);
-  const size_t bytes = HE_BOX_BYTES + (nt == (size_t)-1 ? 0 : nt) * sizeof(eu_force_tile);
-  char* st = nt == (size_t)-1 ? nullptr : (char*)calloc(1, bytes);
-  if (!st || eu_heat_tiles(boxes, n, S->X, S->Y, (eu_force_tile*)(st + HE_BOX_BYTES)) != nt) {
-    free(st);
-    eu_set_error("%s: host memory for the tile table", who);
-    return EULER_ENOMEM;
-  }
-  memcpy(st, boxes, (size_t)n * sizeof(euler_heat_box));
-  int rc = eu_devbuf_reserve(S, who, "the boxes and the tile table", buf, bytes);
-  if (!rc) {      // (the copy queues behind the substeps that still read the old table; the host's copy is freed once it has gone up)
-    const hipError_t e1 = hipMemcpyAsync(buf->p, st, bytes, hipMemcpyHostToDevice, S->stream), e2 = hipStreamSynchronize(S->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess) rc = eu_hip_fail(e1 != hipSuccess ? e1 : e2, "the copy of the boxes and the tile table", __FILE__, __LINE__);
-  }
-  free(st);
-  if (!rc) *ntiles = (unsigned int)nt;
-  return rc;
-}
-
 extern "C" int euler_set_heat(euler_sim* S, const euler_heat* h, const euler_heat_box* boxes) {
   const char* who = "euler_set_heat";
   if (!S) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
@@ -318,7 +277,7 @@ extern "C" int euler_set_heat(euler_sim* S, const euler_heat* h, const euler_hea
   int rc = eu_devbuf_reserve(S, who, "the temperature and its scratch copy", &S->heat_buf, 2 * S->C * sizeof(float));
   if (rc) return rc;
   unsigned int ntiles = 0;
-  if (h->nboxes > 0 && (rc = heat_upload_boxes(S, who, &S->heat_box_buf, boxes, h->nboxes, &ntiles))) return rc;
+  if (h->nboxes > 0 && (rc = eu_box_table_upload(S, who, &S->heat_box_buf, boxes, h->nboxes, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, &ntiles))) return rc;
   const int was_on = S->heat_on;
   S->heat = *h;
   S->heat_ntiles = ntiles;
@@ -380,7 +339,7 @@ extern "C" int euler_heat_fill(euler_sim* S, int32_t x0, int32_t y0, int32_t x1,
   if (!eu_heat_value_ok(value)) { eu_set_error("%s: value %g must be finite and at most 1e4 in size", who, (double)value); return EULER_EINVAL; }
   const euler_heat_box b = {x0, y0, x1, y1, value, EULER_HEAT_FIX};      // the boxes' kernel on a one-box list
   unsigned int ntiles = 0;
-  if ((rc = heat_upload_boxes(S, who, &S->heat_fill_buf, &b, 1, &ntiles))) return rc;
+  if ((rc = eu_box_table_upload(S, who, &S->heat_fill_buf, &b, 1, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, &ntiles))) return rc;
   if ((rc = heat_launch_boxes(S, KC_MISC, &S->heat_fill_buf, ntiles, 0.f))) return rc;      // (outside a substep: the class of k_colorize, not one a cost tool sums)
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;

@@ -6,6 +6,7 @@
 // changes the array (swap-with-last deletion main.c:112, source appends main.c:288) reproduces
 // the reference's order exactly, in parallel.
 #include "euler_dev.h"
+#include "k_transport.h"
 #include "k_advect_one.h"
 
 #include <stdlib.h>
@@ -504,7 +505,7 @@ static int eu_count32_clean(euler_sim* S) {
 template <bool RK2>
 static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
   const unsigned long long n = S->n_markers_host;
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   const float2* in = S->markers[S->cur];
   float2* out = S->markers[S->cur ^ 1];
   const unsigned nb = eu_blocks((size_t)n, 256), nb_b = eu_blocks((size_t)n, 256, 4096);
@@ -546,7 +547,9 @@ static int eu_launch_advect_markers_t(euler_sim* S, float dt) {
   return EULER_OK;
 }
 int eu_launch_advect_markers(euler_sim* S, float dt) {      // (never RK2 on a row slab: euler_set_option refuses it there)
-  return S->opt[EULER_OPT_ADVECT_RK2] ? eu_launch_advect_markers_t<true>(S, dt) : eu_launch_advect_markers_t<false>(S, dt);
+  int rc = EULER_OK;
+  eu_flag(S->opt[EULER_OPT_ADVECT_RK2] != 0, [&](auto R) { rc = eu_launch_advect_markers_t<decltype(R)::value>(S, dt); });
+  return rc;
 }
 
 // ==========================================================================================
@@ -705,13 +708,13 @@ int eu_marker_narrow_counts(euler_sim* S) {
   return EULER_OK;
 }
 int eu_marker_advect_a(euler_sim* S, float dt, unsigned long long n) {
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_a<false, false>), dim3(eu_blocks((size_t)n, 256)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, dt, n,
          S->evmask, S->ev_theta, S->ev_delta, S->ms);
   return eu_ordered_select(S, S->evmask, (size_t)((n + 63) / 64), S->sel_idx, &S->ms->n_events);
 }
 int eu_marker_advect_b(euler_sim* S, unsigned long long n, const unsigned int* keys) {
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   LAUNCH(S, KC_MARKER_ADVECT, (k_advect_markers_b<false, false, false>), dim3(eu_blocks((size_t)n, 256, 4096)), dim3(256), S->markers[S->cur], S->markers[S->cur ^ 1], S->u, S->v, S->solid, g, n,
          S->act_idx, S->act_dt, S->ms, keys, (const uint8_t*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, 0, (uint8_t*)nullptr, 0, 0.f);      // (RK1: dt_sub unread)
   return EULER_OK;

@@ -2,6 +2,10 @@
 // docs/observer_passes.md): a pass enters, reserves its device buffer, launches, and reads back.  The device side is k_observe.h; what a row-slab handle adds
 // between the launch and the read-back - the all-gather of the ranks' partial records and their fold - is k_observe_slab.hip.
 #include "euler_dev.h"
+#include "k_boxes.h"
+
+#include <stdlib.h>
+#include <string.h>
 
 // the checks every pass makes first, in this order; its own (raster, scale, byte count) come behind.  All of them depend on the arguments and on facts every rank
 // of a row-slab job shares, so there every rank refuses alike, before any exchange
@@ -10,7 +14,7 @@ int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reaso
   if (S->slab_on && slab_reason) { eu_set_error("%s: not on a row-slab handle (%s)", who, slab_reason); return EULER_ESTATE; }
   if (S->slab_on && !S->has_comm) { eu_set_error("%s: row-slab handle without a communicator", who); return EULER_ESTATE; }      // (a pass that runs on slabs is collective there)
   if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
-  if (x0 < 1 || y0 < 1 || x1 > S->X - 2 || y1 > S->Y - 2 || x0 > x1 || y0 > y1) {
+  if (!eu_interior_box_ok(x0, y0, x1, y1, S->X, S->Y)) {
     eu_set_error("%s: box [%d, %d] x [%d, %d] is not inside the interior [1, %d] x [1, %d]", who, x0, x1, y0, y1, S->X - 2, S->Y - 2);
     return EULER_EINVAL;
   }
@@ -43,4 +47,26 @@ int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t byte
   HIPCHK(hipMemcpyAsync(out, b->p, bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;
+}
+
+// a list of boxes with its tile table (k_boxes.h): built on the host, then up in one copy
+int eu_box_table_upload(euler_sim* S, const char* who, eu_devbuf* buf, const void* boxes, int32_t n, size_t box_bytes, int32_t max_boxes, unsigned int* ntiles) {
+  const size_t head = (size_t)max_boxes * box_bytes;      // (1536 bytes for either list: the table stays 8-byte aligned)
+  const size_t nt = eu_force_tiles(boxes, box_bytes, n, S->X, S->Y, nullptr);
+  const size_t bytes = head + (nt == (size_t)-1 ? 0 : nt) * sizeof(eu_force_tile);
+  char* st = nt == (size_t)-1 ? nullptr : (char*)calloc(1, bytes);
+  if (!st || eu_force_tiles(boxes, box_bytes, n, S->X, S->Y, (eu_force_tile*)(st + head)) != nt) {
+    free(st);
+    eu_set_error("%s: host memory for the tile table", who);
+    return EULER_ENOMEM;
+  }
+  memcpy(st, boxes, (size_t)n * box_bytes);
+  int rc = eu_devbuf_reserve(S, who, "the boxes and the tile table", buf, bytes);
+  if (!rc) {      // (the copy queues behind the substeps that still read the old table; the host's copy is freed once it has gone up)
+    const hipError_t e1 = hipMemcpyAsync(buf->p, st, bytes, hipMemcpyHostToDevice, S->stream), e2 = hipStreamSynchronize(S->stream);
+    if (e1 != hipSuccess || e2 != hipSuccess) rc = eu_hip_fail(e1 != hipSuccess ? e1 : e2, "the copy of the boxes and the tile table", __FILE__, __LINE__);
+  }
+  free(st);
+  if (!rc) *ntiles = (unsigned int)nt;
+  return rc;
 }

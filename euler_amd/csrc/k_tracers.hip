@@ -6,6 +6,7 @@
 // chain of the fluid's markers shortened and never shortens anyone's; it reads the row-major u, v, count, solid and sink as they stand in front of the
 // marker launches - no column-major copy, no tile map - and touches none of the handle's validity flags.
 #include "euler_dev.h"
+#include "k_transport.h"
 #include "k_advect_one.h"
 
 #include <stdlib.h>
@@ -61,10 +62,11 @@ __global__ __launch_bounds__(TR_T) void k_advect_tracers(euler_tracer* __restric
 int eu_launch_advect_tracers(euler_sim* S, float dt) {
   const unsigned int n = (unsigned int)S->n_tracers;      // (<= EULER_TRACERS_MAX = 2^22)
   if (!n) return EULER_OK;
-  GridRef g{S->X, S->Y, S->count, S->interp_lim[0], S->interp_lim[1], S->interp_lim[2], S->interp_lim[3]};
+  const GridRef g = eu_grid_ref(S);
   euler_tracer* rec = (euler_tracer*)S->tracer_buf.p;
-  if (S->opt[EULER_OPT_ADVECT_RK2]) LAUNCH(S, KC_MARKER_ADVECT, (k_advect_tracers<true>), dim3(eu_blocks(n, TR_T)), dim3(TR_T), rec, n, S->u, S->v, S->solid, S->sink, g, dt);
-  else LAUNCH(S, KC_MARKER_ADVECT, (k_advect_tracers<false>), dim3(eu_blocks(n, TR_T)), dim3(TR_T), rec, n, S->u, S->v, S->solid, S->sink, g, dt);
+  eu_flag(S->opt[EULER_OPT_ADVECT_RK2] != 0, [&](auto R) {
+    LAUNCH(S, KC_MARKER_ADVECT, k_advect_tracers<decltype(R)::value>, dim3(eu_blocks(n, TR_T)), dim3(TR_T), rec, n, S->u, S->v, S->solid, S->sink, g, dt);
+  });
   return EULER_OK;
 }
 

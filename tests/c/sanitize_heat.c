@@ -21,10 +21,10 @@ static int tiles_case(const euler_heat_box* b, int n, int X, int Y) {
   CHECK(euler_heat_default(&h) == EULER_OK);
   h.nboxes = n;
   CHECK(eu_heat_check(&h, b, X, Y, NULL, why, sizeof why) == EULER_OK && why[0] == 0);
-  const size_t m = eu_heat_tiles(b, n, X, Y, NULL);
+  const size_t m = eu_force_tiles(b, sizeof(euler_heat_box), n, X, Y, NULL);
   CHECK(m != (size_t)-1 && (n == 0) == (m == 0));
   eu_force_tile* t = malloc((m ? m : 1) * sizeof *t);      /* exactly the count: one entry too many is a heap overflow the sanitizer reports */
-  CHECK(t && eu_heat_tiles(b, n, X, Y, t) == m);
+  CHECK(t && eu_force_tiles(b, sizeof(euler_heat_box), n, X, Y, t) == m);
   const int tnx = (X + 63) / 64, tny = (Y + 63) / 64;
   size_t at = 0;
   for (int ty = 0; ty < tny; ++ty)
@@ -58,12 +58,12 @@ int main(void) {
                                 {X - 2, Y - 2, X - 2, Y - 2, 3.f, EULER_HEAT_FIX}, {1, 1, X - 2, Y - 2, 0.5f, EULER_HEAT_RATE},      /* the last cell; the whole interior */
                                 {200, 1, X - 2, 63, 1.f, EULER_HEAT_FIX}, {60, 60, 70, 70, 1.f, EULER_HEAT_FIX}};                    /* touching X - 2; a repeat */
     for (int n = 0; n <= (int)(sizeof b / sizeof *b); ++n) if (tiles_case(b, n, X, Y)) return 1;
-    CHECK(eu_heat_tiles(b, 1, X, Y, NULL) == 4 && eu_heat_tiles(b, 7, X, Y, NULL) == 5 * 3);
+    CHECK(eu_force_tiles(b, sizeof(euler_heat_box), 1, X, Y, NULL) == 4 && eu_force_tiles(b, sizeof(euler_heat_box), 7, X, Y, NULL) == 5 * 3);
     euler_heat_box many[EULER_HEAT_BOXES_MAX];      /* 64 boxes on one tile */
     for (int k = 0; k < EULER_HEAT_BOXES_MAX; ++k) { many[k].x0 = 64 + k % 8; many[k].x1 = 64 + k % 8 + k / 8; many[k].y0 = 64 + k / 8; many[k].y1 = 64 + 7; many[k].value = (float)k; many[k].kind = k & 1; }
     if (tiles_case(many, EULER_HEAT_BOXES_MAX, X, Y)) return 1;
     eu_force_tile one;
-    CHECK(eu_heat_tiles(many, EULER_HEAT_BOXES_MAX, X, Y, &one) == 1 && one.tx == 1 && one.ty == 1 && one.boxes == 0xffffffffffffffffull);
+    CHECK(eu_force_tiles(many, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, X, Y, &one) == 1 && one.tx == 1 && one.ty == 1 && one.boxes == 0xffffffffffffffffull);
     /* random lists on grids whose sides are and are not multiples of the tile */
     const int sizes[][2] = {{8, 8}, {66, 65}, {128, 64}, {129, 193}, {1031, 70}};
     uint64_t rng = EULER_RNG_SEED;
