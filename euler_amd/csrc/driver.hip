@@ -18,6 +18,7 @@ int eu_unskew_fluid(euler_sim* S, const double* skew, double* rowmajor);
 double* eu_current_search_direction(euler_sim* S);
 int eu_launch_tile_table(euler_sim* S);
 int eu_skew(euler_sim* S, const void* rowmajor, void* skew, int elem_bytes);
+int eu_set_source_count(euler_sim* S, size_t nsrc);
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -192,16 +193,12 @@ extern "C" int euler_set_option(euler_sim* S, int32_t key, int64_t value) {
   if (key == EULER_OPT_ADVECT_MACCORMACK && value == 1 && !S->mc_u) {      // the forward results of u, v (and the dye's corrected channels): allocated on first use
     float *a = nullptr, *b = nullptr;
     const size_t bytes = S->C * sizeof(float);
-    if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess || hipMemset(a, 0, bytes) != hipSuccess ||
-        hipMemset(b, 0, bytes) != hipSuccess) {
-      if (a) (void)hipFree(a);
-      if (b) (void)hipFree(b);
-      (void)hipGetLastError();
+    if (eu_dalloc(S, &a, S->C, EU_MEM_HANDLE, EU_MEM_ZERO | EU_DEV_QUIET) || eu_dalloc(S, &b, S->C, EU_MEM_HANDLE, EU_MEM_ZERO | EU_DEV_QUIET)) {
+      (void)eu_dev_free(S, a);
       eu_set_error("euler_set_option: EULER_OPT_ADVECT_MACCORMACK needs %zu bytes of scratch", 2 * bytes);
       return EULER_ENOMEM;
     }
     S->mc_u = a; S->mc_v = b;
-    S->hbm_bytes += 2 * bytes;
   }
   if (key == EULER_OPT_P_STEPS || key == EULER_OPT_SA_RUN) {      // the ring is about to be forgotten: the pressure the last velocity update left unfinished in memory is finished from it first
     int rcp = eu_pressure_current(S);
@@ -258,56 +255,22 @@ extern "C" int euler_set_solver(euler_sim* S, int32_t max_iterations, double tol
   return EULER_OK;
 }
 
-static thread_local size_t g_alloc_bytes = 0;      // what the handle under construction has allocated (euler_hbm_bytes)
-template <typename T>
-static int dalloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-  g_alloc_bytes += n * sizeof(T);
-  HIPCHK(hipMemset(*p, 0, n * sizeof(T)));
-  return EULER_OK;
-}
-#define DALLOC(p, n) do { int _rc = dalloc(&(p), (n)); if (_rc) { euler_destroy(S); return _rc; } } while (0)
+// every block euler_create gives the handle: recorded in the ledger (mem.hip), zeroed before anybody reads it
+#define DALLOC(p, n) do { int _rc = eu_dalloc(S, &(p), (n), EU_MEM_HANDLE, EU_MEM_ZERO); if (_rc) { euler_destroy(S); return _rc; } } while (0)
 
+// a finished handle and one that failed half-way through euler_create take the same path: the ledger knows what the handle holds (docs/handle_memory.md)
 extern "C" void euler_destroy(euler_sim* S) {
   if (!S) return;
   if (S->stream) (void)hipStreamSynchronize(S->stream);
   eu_p2p_release(S);
   eu_rccl_release(S);
-  eu_slab_release(S);
+  eu_slab_release(S);      // (the slab's and the split cycle's host-side records go with their groups)
   eu_coarse_release(S);
-  for (eu_devbuf* b : {&S->obs_stage_buf, &S->ov_buf, &S->diag_buf, &S->vr_buf, &S->flow_buf, &S->gauge_buf, &S->force_buf, &S->tracer_buf, &S->tracer_ras_buf, &S->heat_buf, &S->heat_box_buf, &S->heat_fill_buf, &S->heat_ras_buf, &S->rs_mask_buf, &S->rs_cell_buf, &S->rs_slot_buf, &S->rs_draw_buf}) eu_devbuf_release(S, b);
-  // row-major arrays are held by base pointers shifted to global (x, y) indexing: allocation = pointer + win_off
-  // (a handle that failed half-way through euler_create still holds the raw allocations: S->shifted)
-  const size_t wo = S->shifted ? S->win_off : 0;
-  for (float* f : {S->u, S->v, S->utmp, S->vtmp}) if (f) (void)hipFree(f + wo);
-  for (uint8_t* g : {S->solid, S->source, S->sink, S->count, S->prev_count}) if (g) (void)hipFree(g + wo);
-  if (S->count32) (void)hipFree(S->count32);
-  if (S->blockedT) (void)hipFree(S->blockedT);
-  if (S->tmap) (void)hipFree(S->tmap);
-  if (S->uT) (void)hipFree(S->uT);
-  if (S->vT) (void)hipFree(S->vT);
-  if (S->countT) (void)hipFree(S->countT);
-  if (S->solidT) (void)hipFree(S->solidT);
-  if (S->sys_m) (void)hipFree(S->sys_m);
-  if (S->sys_div) (void)hipFree(S->sys_div);
-  void* dev[] = {S->markers[0], S->markers[1], S->keys[0], S->keys[1], S->ms, S->evmask, S->delmask, S->ev_theta, S->ev_delta, S->sel_idx, S->act_idx,
-                 S->act_dt, S->cellmask64, S->draws, S->sel.block_sums, S->sc, S->partial, S->red_counter, S->granules, S->ticket, S->sweep_timeline, S->halo_buf, S->band_ranges, S->partial2, S->pair_buf, S->xrows, S->alpha_buf, S->rng_jump, S->chunk_flag, S->chunk_prev, S->chunk_part, S->tile_table, S->chunk_bits, S->chunk_list, S->zhalo, S->zrows,
-                 S->rowmajor_tmp, S->mc_u, S->mc_v};
-  for (void* p : dev) if (p) (void)hipFree(p);
-  for (float* d : S->dye) if (d) (void)hipFree(d + wo);
-  // band-skewed arrays: shifted to global element indexing as well (skew_off), behind EU_SKEW_SLACK elements of slack
-  const size_t so = S->shifted ? S->skew_off : 0, sl = S->shifted ? (size_t)EU_SKEW_SLACK : 0;
-  (void)so; (void)sl;
-  for (void* d : S->s_ring_alloc) if (d) (void)hipFree(d);
-  for (void* d : S->skew_alloc) if (d) (void)hipFree(d);      // (the raw allocations: s / s2 swap during solves, and each array has its own stagger)
-  const size_t fb_off = S->shifted ? (size_t)S->ab_lo * S->fb_stride * 64 : 0;
-  if (S->fbits_fwd) (void)hipFree(S->fbits_fwd + fb_off);
-  if (S->fbits_bwd) (void)hipFree(S->fbits_bwd + fb_off);
+  eu_dev_free_all(S);
   if (S->ms_host) (void)hipHostFree(S->ms_host);
   if (S->sc_host) (void)hipHostFree(S->sc_host);
   if (S->poll_host) (void)hipHostFree(S->poll_host);
   if (S->res_err) (void)hipHostFree(S->res_err);
-  if (S->res_gran) (void)hipFree(S->res_gran);
   for (hipEvent_t e : S->poll_event) if (e) (void)hipEventDestroy(e);
   if (S->ev_pool) { for (int k = 0; k < S->ev_cap; ++k) if (S->ev_pool[k]) (void)hipEventDestroy(S->ev_pool[k]); free(S->ev_pool); }
   free(S->ev_cls); free(S->ev_solve); free(S->ev_iter);
@@ -337,7 +300,6 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
   euler_sim* S = (euler_sim*)calloc(1, sizeof(euler_sim));
   if (S) { S->opt[EULER_OPT_P_STEPS] = 8; S->opt[EULER_OPT_TILE_REVERSE] = 1; S->opt[EULER_OPT_GRID4_MIN_CELLS] = 1ll << 22; S->opt[EULER_OPT_SA_RUN] = 8; S->opt[EULER_OPT_PROFILE_STRIDE] = 1; }      // (euler_set_option's defaults)
   if (!S) return EULER_ENOMEM;
-  g_alloc_bytes = 0;
   S->cfg = *cfg;
   (void)euler_forcing_default(&S->forcing);      // (the reference's gravity until euler_set_forcing says otherwise)
   if (S->cfg.max_iterations <= 0) S->cfg.max_iterations = 100;
@@ -402,7 +364,7 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
   CREATECHK(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
   S->own_stream = 1;
 
-  // (allocated un-shifted; all base pointers are shifted together once every allocation has succeeded: S->shifted)
+  // (allocated un-shifted; all base pointers are shifted together once every allocation has succeeded)
   DALLOC(S->u, Cw); DALLOC(S->v, Cw); DALLOC(S->utmp, Cw); DALLOC(S->vtmp, Cw);
   DALLOC(S->solid, Cw); DALLOC(S->source, Cw); DALLOC(S->sink, Cw); DALLOC(S->count, Cw); DALLOC(S->prev_count, Cw);
   DALLOC(S->count32, Cw);
@@ -439,12 +401,10 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
     int k = 0;
     for (double** d : {&S->b, &S->p, &S->r, &S->z, &S->s, &S->s2, &S->q, &S->precon}) {
       DALLOC(*d, SS + EU_SKEW_SLACK + 8 * stagger / 8);
-      S->skew_alloc[k] = *d;
       *d += (size_t)k * stagger / 8;
       ++k;
     }
     DALLOC(S->cellmask, SS + EU_SKEW_SLACK);
-    S->skew_alloc[8] = S->cellmask;
   }
   S->fb_stride = 12 * (((S->geom.T + 7) / 8 + 11) / 12) + 4;   // whole groups of 3 and of 4 blocks + the blocks the prefetch runs ahead
   DALLOC(S->fbits_fwd, (size_t)(S->ab_hi - S->ab_lo) * S->fb_stride * 64);
@@ -478,7 +438,7 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
         for (int k = 0; k < 64; ++k) if ((x >> k) & 1) y ^= J->col[i - 1][k];
         J->col[i][b] = y;
       }
-    int rc = dalloc(&S->rng_jump, 1);
+    int rc = eu_dalloc(S, &S->rng_jump, 1, EU_MEM_HANDLE, EU_MEM_ZERO);
     if (!rc && hipMemcpy(S->rng_jump, J, sizeof(RngJump), hipMemcpyHostToDevice) != hipSuccess) rc = EULER_EHIP;
     free(J);
     if (rc) { euler_destroy(S); return rc; }
@@ -497,7 +457,6 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
   for (double** d : {&S->b, &S->p, &S->r, &S->z, &S->s, &S->s2, &S->q, &S->precon}) *d += EU_SKEW_SLACK - S->skew_off;
   S->cellmask += EU_SKEW_SLACK - S->skew_off;
   S->fbits_fwd -= (size_t)S->ab_lo * S->fb_stride * 64; S->fbits_bwd -= (size_t)S->ab_lo * S->fb_stride * 64;
-  S->shifted = 1;
   CREATECHK(hipHostMalloc((void**)&S->ms_host, sizeof(MarkerState), hipHostMallocDefault));
   CREATECHK(hipHostMalloc((void**)&S->sc_host, sizeof(PcgScalars), hipHostMallocDefault));
   CREATECHK(hipHostMalloc((void**)&S->poll_host, 2 * sizeof(PcgScalars), hipHostMallocDefault));
@@ -531,7 +490,6 @@ extern "C" int euler_create(const euler_config* cfg, euler_sim** out) {
     int rc = eu_coarse_alloc(S, S->cfg.precond == EULER_PRECOND_IC0_TILE_MG);
     if (rc) { euler_destroy(S); return rc; }
   }
-  S->hbm_bytes = g_alloc_bytes + (S->slab_on ? eu_slab_bytes(S) : 0);
   eu_launch_tile_table(S);      // E^-1 of an interior tile (k_tile.hip), once per handle
   if (S->cfg.pcg_precision != EULER_PCG_F64 && S->cfg.pcg_precision != EULER_PCG_F32) { eu_set_error("euler_create: pcg_precision %d", S->cfg.pcg_precision); euler_destroy(S); return EULER_EINVAL; }
   if (S->cfg.pcg_precision == EULER_PCG_F32 && !eu_resident_eligible(S)) {
@@ -574,9 +532,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   if (rc) return rc;
   size_t nsrc = 0;
   for (size_t i = (size_t)S->row_lo * S->X; i < (size_t)S->row_hi * S->X; ++i) nsrc += source[i] != 0;
-  S->n_source_cells = nsrc;
-  if (S->draws) { (void)hipFree(S->draws); S->draws = nullptr; }
-  if (nsrc) HIPCHK(hipMalloc((void**)&S->draws, 2 * nsrc * sizeof(float)));
+  if ((rc = eu_set_source_count(S, nsrc))) return rc;
 
   hipStream_t st = S->stream;
   const size_t wo = S->win_off, Cw = S->Cw;            // the window's rows of the static grids
@@ -932,8 +888,8 @@ static bool field_is_skewed(int f) {
   return f == EULER_F_PRECON || f == EULER_F_PRESSURE || (f >= EULER_F_PCG_B && f <= EULER_F_PCG_Q) || f == EULER_F_CELLMASK;
 }
 static int ensure_rowmajor_tmp(euler_sim* S) {
-  if (!S->rowmajor_tmp) HIPCHK(hipMalloc((void**)&S->rowmajor_tmp, (size_t)(S->row_hi - S->row_lo) * S->X * sizeof(double)));
-  return EULER_OK;
+  if (S->rowmajor_tmp) return EULER_OK;      // uncounted: transfer scratch of euler_get_field / euler_set_field, not something the simulation holds
+  return eu_dalloc(S, &S->rowmajor_tmp, (size_t)(S->row_hi - S->row_lo) * S->X, EU_MEM_HANDLE, EU_MEM_UNCOUNTED);
 }
 
 extern "C" int euler_get_field(euler_sim* S, int32_t f, void* dst, size_t dst_bytes) {
@@ -964,9 +920,10 @@ extern "C" int euler_get_field(euler_sim* S, int32_t f, void* dst, size_t dst_by
 // the source cells of the own rows changed: the buffer of their random draws follows (k_source_fill)
 int eu_set_source_count(euler_sim* S, size_t nsrc) {
   S->n_source_cells = nsrc;
-  if (S->draws) { (void)hipFree(S->draws); S->draws = nullptr; }
-  if (nsrc) HIPCHK(hipMalloc((void**)&S->draws, 2 * nsrc * sizeof(float)));
-  return EULER_OK;
+  (void)eu_dev_free(S, S->draws);
+  S->draws = nullptr;
+  // uncounted: its size follows the scene's source cells, which euler_edit_box may change - euler_hbm_bytes does not move with an edit
+  return nsrc ? eu_dalloc(S, &S->draws, 2 * nsrc, EU_MEM_HANDLE, EU_MEM_UNCOUNTED) : EULER_OK;
 }
 
 extern "C" int euler_set_field(euler_sim* S, int32_t f, const void* src, size_t src_bytes) {
@@ -1196,7 +1153,7 @@ extern "C" int euler_sweep_timeline(euler_sim* S, uint64_t* out, int32_t cap_ban
   return n;
 }
 
-extern "C" uint64_t euler_hbm_bytes(const euler_sim* S) { return S ? (uint64_t)S->hbm_bytes : 0; }
+extern "C" uint64_t euler_hbm_bytes(const euler_sim* S) { return S ? (uint64_t)eu_mem_counted(&S->mem) : 0; }
 
 extern "C" int euler_device_name(euler_sim* S, char* out, int32_t cap) {
   if (!S || !out || cap < 1) return EULER_EINVAL;

@@ -9,6 +9,7 @@
 #include "euler.h"
 #include "euler_host.h"
 #include "eu_valid.h"
+#include "eu_mem.h"
 
 // ------------------------------------------------------------------------------------------
 // reference constants (main.c:58-60)
@@ -135,7 +136,7 @@ struct SelectScratch {
   size_t capacity_blocks;
 };
 
-struct eu_devbuf { void* p; size_t bytes; };   // a grow-only device buffer of a handle (eu_devbuf_reserve), counted in hbm_bytes
+struct eu_devbuf { void* p; size_t bytes; };   // a grow-only device buffer of a handle (eu_devbuf_reserve): a block of the ledger's EU_MEM_HANDLE group, counted (docs/handle_memory.md)
 
 struct euler_sim {
   euler_config cfg;
@@ -220,7 +221,6 @@ struct euler_sim {
   SkewGeom geom;
   double *b, *p, *r, *z, *s, *q, *precon;
   double* s2;             // second search-direction array (k_search_apply ping-pongs s / s2)
-  void* skew_alloc[9];    // the raw allocations behind b p r z s s2 q precon cellmask (each array is staggered inside its own)
   uint8_t* cellmask;
   uint8_t* sys_m; float* sys_div;   // row-major scratch of the assembly (k_cell_system -> k_build_system): mask byte and float divergence per cell of the window, indexed i - win_off
   unsigned int* fbits_fwd; unsigned int* fbits_bwd;   // fluid flags of the sweeps, 8 steps to a dword (k_pack_fbits)
@@ -263,7 +263,7 @@ struct euler_sim {
   int pcg_fields_resident;        // the last solve ran in the resident kernel: S->z / S->s / S->q hold published halo cells only (euler_get_field refuses them)
   int tile_w;             // EULER_PRECOND_IC0_TILE: records per tile (include/euler.h precond_tile_records)
   double* s_ring[8];                // the search directions' ring (k_pcg.hip p_steps): [0], [1] = s, s2 as the solve found them, the others allocated when first needed
-  void* s_ring_alloc[8];            // raw allocations of [2..]
+  void* s_ring_alloc[8];            // the un-shifted bases of [2..] that ring_begin indexes from (the ledger's EU_MEM_RING group owns the blocks)
   double* s_base[2];                // the handle's own two search arrays (S->s / S->s2 point into the ring while a solve runs)
   int s_ring_n;                     // arrays of the current / last solve's ring
   int s_launched;                   // iterations the last solve LAUNCHED (launches behind convergence return at once but still turn the ring)
@@ -278,7 +278,7 @@ struct euler_sim {
   uint8_t* chunk_flag;    // this solve: the chunk holds fluid
   uint8_t* chunk_prev;    // the previous solve's flags (k_build_system<true>: where stale masks / p / r may sit)
   uint8_t* chunk_part;    // this solve: some cell of the chunk is not CM_INTERIOR (the listed entry of an interior chunk carries EU_CHUNK_INTERIOR)
-  size_t hbm_bytes;       // device memory this handle allocated: at creation, plus the search directions' ring when the first multi-kernel solve needs it (euler_hbm_bytes)
+  eu_mem mem;             // the ledger of every device block this handle holds (eu_mem.h, docs/handle_memory.md): allocated through eu_dalloc, freed and counted (euler_hbm_bytes) there only
   double* zhalo;          // tile-local mode on one GPU (k_pcg.h tile_z_recompute): [band][T / 16][2][64] - records 0 and 15 of every tile's z; allocated by the first solve that needs them
   double* zrows;          // [band][2][X]: lane 0's / lane 63's z by column (with zhalo)
   int z_halo_last;        // the solve's last k_precond_tile left z as its halo only: the next k_search_apply forms z again (ZR)
@@ -324,7 +324,7 @@ struct euler_sim {
   // EU_GHOST_HI above (clipped to the grid) and is addressed with GLOBAL (x, y): the base pointers are shifted by
   // -win_lo * X (win_off).  The band-skewed arrays hold the own bands + one band either side, shifted likewise (skew_off).
   // Without slabs the window is the whole grid and both offsets are 0.
-  int slab_on, shifted;
+  int slab_on;
   int row_lo, row_hi, win_lo, win_hi;
   size_t win_off, Cw, skew_off, Sw;
   int ab_lo, ab_hi;           // bands the skewed arrays hold
@@ -381,11 +381,21 @@ __device__ __forceinline__ size_t eu_xcd_block() {
   return b < full ? (size_t)(b & 7) * (full >> 3) + (b >> 3) : (size_t)b;
 }
 
+// The handle's device memory (mem.hip over eu_mem.h; docs/handle_memory.md): EVERY persistent device block of a handle comes from eu_dalloc / eu_dev_alloc, which
+// records it in S->mem under its group; nothing else calls hipMalloc or hipFree for a handle.  flags: EU_MEM_ZERO (a synchronous hipMemset), EU_MEM_UNCOUNTED (not
+// part of euler_hbm_bytes), EU_DEV_QUIET (the caller has its own fall-back or message: no error text is set).  A failed call leaves *p and the ledger as they were.
+enum { EU_DEV_QUIET = 1 << 8 };
+int  eu_dev_alloc(euler_sim* S, void** p, size_t bytes, int group, int flags);
+int  eu_dev_free(euler_sim* S, void* raw);           // one block by the pointer eu_dev_alloc returned (null: nothing to do); a pointer the ledger does not hold is refused
+void eu_dev_free_group(euler_sim* S, int group);     // the release functions: free my group, then null my fields
+void eu_dev_free_all(euler_sim* S);                  // euler_destroy
+template <typename T>
+static inline int eu_dalloc(euler_sim* S, T** p, size_t n, int group, int flags = 0) { return eu_dev_alloc(S, (void**)p, n * sizeof(T), group, flags); }
+
 #define EU_GHOST_LO 1   // ghost rows below / above a slab: u, v need 1 / 1, the count grids 1 / 2, vtmp 1 / 0
 #define EU_GHOST_HI 2
 // slab mode (k_slab.hip)
 int  eu_slab_alloc(euler_sim* S);
-size_t eu_slab_bytes(const euler_sim* S);   // device memory of the slab exchange buffers
 void eu_slab_release(euler_sim* S);
 int  eu_slab_substep(euler_sim* S, float dt);
 int  eu_slab_stage(euler_sim* S, int stage, float dt);   // euler_stage on a row-slab handle (collective): the stage with its exchanges
@@ -442,8 +452,7 @@ int eu_marker_compact(euler_sim* S, const unsigned long long* delmask);   // k_m
 // the host side of a read-only observer pass (k_observe.hip, docs/observer_passes.md): enter, reserve, launch, read back
 // slab_reason: why this pass refuses a row-slab handle; null: it runs there (collective) and refuses only a slab handle without a communicator
 int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reason, const void* out, int x0, int y0, int x1, int y1);   // null argument, row-slab handle, nothing loaded, box inside the interior
-int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes);   // grow-only; a failure leaves the handle as it was
-void eu_devbuf_release(euler_sim* S, eu_devbuf* b);
+int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes, size_t keep = 0);   // grow-only; the first `keep` bytes move over; a failure leaves the handle as it was
 int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t bytes);   // copy to the caller and wait for it
 // the passes on a row-slab handle (k_observe_slab.hip, docs/observer_passes.md "On row slabs"): every rank reduces the rows of the box it owns into its share of the staging
 // area, the shares are all-gathered as bytes and folded on the device into the pass's own buffer - integer sums and extremes: the whole-grid record bit for bit

@@ -40,24 +40,21 @@ int eu_coarse_alloc(euler_sim* S, bool mg) {
   S->coarse_ny = (S->geom.nbands + m - 1) / m;
   S->coarse_n = S->coarse_nx * S->coarse_ny;
   const size_t n = (size_t)S->coarse_n, nn = n > MG_TOP_MAX ? n : MG_TOP_MAX;      // (the multilevel mode's dense level has its own size: at most MG_TOP_MAX nodes)
-  HIPCHK(hipMalloc((void**)&S->cc_diag, 4 * nn * sizeof(int)));      // diagonal, right, up; pinned[n] (k_coarse_factor)
+  int rc;
+  if ((rc = eu_dalloc(S, &S->cc_diag, 4 * nn, EU_MEM_COARSE))) return rc;      // diagonal, right, up; pinned[n] (k_coarse_factor)
   S->cc_right = S->cc_diag + nn; S->cc_up = S->cc_diag + 2 * nn; S->cc_pinned = S->cc_diag + 3 * nn;
-  HIPCHK(hipMalloc((void**)&S->cc_sten, 5 * nn * sizeof(double)));    // the two-level mode's stencil as doubles: d, e, n, ne, nw (k_coarse_factor's input)
-  HIPCHK(hipMalloc((void**)&S->cc_fac, nn * nn * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&S->cc_inv, nn * nn * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&S->cc_part, (S->chunk_cap + 64) * 3 * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&S->cc_y, (2 * CC_MAX + 1) * sizeof(double)));      // y [CC_MAX], r_c [CC_MAX], the ticket counter of k_coarse_solve
-  HIPCHK(hipMemset(S->cc_part, 0, (S->chunk_cap + 64) * 3 * sizeof(double)));
-  HIPCHK(hipMemset(S->cc_y, 0, (2 * CC_MAX + 1) * sizeof(double)));
-  HIPCHK(hipMalloc((void**)&S->cc_null, CC_NULL_TOTAL * sizeof(double)));      // indicators, their number, the sums / partials / ticket of k_null_sums
-  HIPCHK(hipMemset(S->cc_null, 0, CC_NULL_TOTAL * sizeof(double)));
+  if ((rc = eu_dalloc(S, &S->cc_sten, 5 * nn, EU_MEM_COARSE))) return rc;    // the two-level mode's stencil as doubles: d, e, n, ne, nw (k_coarse_factor's input)
+  if ((rc = eu_dalloc(S, &S->cc_fac, nn * nn, EU_MEM_COARSE))) return rc;
+  if ((rc = eu_dalloc(S, &S->cc_inv, nn * nn, EU_MEM_COARSE))) return rc;
+  if ((rc = eu_dalloc(S, &S->cc_part, (S->chunk_cap + 64) * 3, EU_MEM_COARSE, EU_MEM_ZERO))) return rc;
+  if ((rc = eu_dalloc(S, &S->cc_y, 2 * CC_MAX + 1, EU_MEM_COARSE, EU_MEM_ZERO))) return rc;      // y [CC_MAX], r_c [CC_MAX], the ticket counter of k_coarse_solve
+  if ((rc = eu_dalloc(S, &S->cc_null, CC_NULL_TOTAL, EU_MEM_COARSE, EU_MEM_ZERO))) return rc;      // indicators, their number, the sums / partials / ticket of k_null_sums
   if (mg) return eu_mg_alloc(S);
   return EULER_OK;
 }
 
 void eu_coarse_release(euler_sim* S) {
-  if (S->cc_diag) (void)hipFree(S->cc_diag);
-  for (double* d : {S->cc_fac, S->cc_inv, S->cc_part, S->cc_y, S->cc_null, S->cc_sten}) if (d) (void)hipFree(d);
+  eu_dev_free_group(S, EU_MEM_COARSE);
   S->cc_diag = S->cc_right = S->cc_up = S->cc_pinned = nullptr;
   S->cc_fac = S->cc_inv = S->cc_part = S->cc_y = S->cc_null = S->cc_sten = nullptr;
   eu_mg_release(S);
@@ -419,8 +416,8 @@ int eu_coarse_comm_slots(euler_sim* S) {
   for (int r = 0; r < S->bulk.nranks && r < 64; ++r) rows = MG_RPB * (S->part_hi[r] - S->part_lo[r]) + 2 > rows ? MG_RPB * (S->part_hi[r] - S->part_lo[r]) + 2 : rows;
   const int slot = eu_mg_split(S) ? eu_mg_split_nsmall(S) : 2 + rows * S->mg_nx[0];      // (the split cycle: a window of the gather level instead of level 0's rows)
   if (slot != S->mg_xslot || !S->mg_xbuf) {
-    if (S->mg_xbuf) { if (hipStreamSynchronize(S->stream) != hipSuccess || hipFree(S->mg_xbuf) != hipSuccess) return -1; S->mg_xbuf = nullptr; }
-    if (hipMalloc((void**)&S->mg_xbuf, (size_t)slot * S->bulk.nranks * sizeof(double)) != hipSuccess) { eu_set_error("hipMalloc of the multilevel exchange buffer failed"); return -1; }
+    if (S->mg_xbuf) { if (hipStreamSynchronize(S->stream) != hipSuccess || eu_dev_free(S, S->mg_xbuf)) return -1; S->mg_xbuf = nullptr; }
+    if (eu_dalloc(S, &S->mg_xbuf, (size_t)slot * S->bulk.nranks, EU_MEM_MG, EU_DEV_QUIET)) { eu_set_error("hipMalloc of the multilevel exchange buffer failed"); return -1; }
     if (hipMemsetAsync(S->mg_xbuf, 0, (size_t)slot * S->bulk.nranks * sizeof(double), S->stream) != hipSuccess) return -1;
     S->mg_xslot = slot;
   }

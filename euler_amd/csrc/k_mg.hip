@@ -32,7 +32,7 @@
 #include "k_pcg.h"
 
 // (a failed allocation gives back what the attempt already holds: the next attempt starts from nothing - ADVICE r5)
-#define MGCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { eu_mg_release(S); return eu_hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
+#define MGALLOC(p, n, flags) do { int _rc = eu_dalloc(S, &(p), (n), EU_MEM_MG, (flags)); if (_rc) { eu_mg_release(S); return _rc; } } while (0)
 int eu_mg_check_tail(const euler_sim* S, const char* why) {
   const int behind = S->mg_levels - 1 - eu_mg_entry_level(S->mg_levels, S->mg_nx, S->mg_ny);
   if (behind <= MG_TAIL_LEVELS) return EULER_OK;
@@ -54,18 +54,13 @@ int eu_mg_alloc(euler_sim* S) {
   const size_t n0 = (size_t)S->mg_nx[0] * S->mg_ny[0];
   // the limits of the cycle's launches, checked where the mode is SELECTED (euler_create, euler_set_precond) - not inside a solve, behind the substep's marker stages
   if (eu_mg_check_tail(S, ": the grid is too large for this mode") || eu_mg_check_tiles0(S, ": the grid is too large for this mode")) { S->mg_levels = 0; return EULER_EINVAL; }
-  MGCHK(hipMalloc((void**)&S->mg_a, 9 * S->mg_cells * sizeof(double)));
-  MGCHK(hipMalloc((void**)&S->mg_a0i, 9 * n0 * sizeof(unsigned long long)));
-  MGCHK(hipMalloc((void**)&S->mg_rhs, 3 * S->mg_cells * sizeof(double)));
+  MGALLOC(S->mg_a, 9 * S->mg_cells, EU_MEM_ZERO);
+  MGALLOC(S->mg_a0i, 9 * n0, 0);
+  MGALLOC(S->mg_rhs, 3 * S->mg_cells, EU_MEM_ZERO);
   S->mg_x = S->mg_rhs + S->mg_cells; S->mg_wd = S->mg_rhs + 2 * S->mg_cells;
-  MGCHK(hipMalloc((void**)&S->mg_part, (S->chunk_cap + 64) * MG_PART * sizeof(double)));
-  MGCHK(hipMalloc((void**)&S->mg_null0, (size_t)MG_NULL_MAX * S->mg_cells * sizeof(double)));      // the indicators of cut-off regions on every level (k_mg_null_prolong)
-  MGCHK(hipMemset(S->mg_a, 0, 9 * S->mg_cells * sizeof(double)));
-  MGCHK(hipMemset(S->mg_rhs, 0, 3 * S->mg_cells * sizeof(double)));
-  MGCHK(hipMemset(S->mg_part, 0, (S->chunk_cap + 64) * MG_PART * sizeof(double)));
-  MGCHK(hipMemset(S->mg_null0, 0, (size_t)MG_NULL_MAX * S->mg_cells * sizeof(double)));
-  MGCHK(hipMalloc((void**)&S->mg_inner0, n0));
-  MGCHK(hipMemset(S->mg_inner0, 0, n0));
+  MGALLOC(S->mg_part, (S->chunk_cap + 64) * MG_PART, EU_MEM_ZERO);
+  MGALLOC(S->mg_null0, (size_t)MG_NULL_MAX * S->mg_cells, EU_MEM_ZERO);      // the indicators of cut-off regions on every level (k_mg_null_prolong)
+  MGALLOC(S->mg_inner0, n0, EU_MEM_ZERO);
   {      // level 0's stencil under deep water: A_0 = K (x) M + M (x) K with the 1-D mass and stiffness sums of the hats (multiples of 1 / G0^2: exact)
     double M[3] = {0, 0, 0}, K[3] = {-1.0 / MG_G0, 2.0 / MG_G0, -1.0 / MG_G0};
     for (int k = -(MG_G0 - 1); k <= MG_G0 - 1; ++k) { const double w = 1.0 - (k < 0 ? -k : k) / (double)MG_G0; M[1] += w * w; }
@@ -73,19 +68,14 @@ int eu_mg_alloc(euler_sim* S) {
     M[2] = M[0];
     for (int q = 0; q < 9; ++q) S->mg_ic[q] = K[q % 3] * M[q / 3] + M[q % 3] * K[q / 3];
   }
-  MGCHK(hipMalloc((void**)&S->mg_m0, (MG_NULL_MAX * n0 + MG_NULL_MAX) * sizeof(double)));
-  MGCHK(hipMemset(S->mg_m0, 0, (MG_NULL_MAX * n0 + MG_NULL_MAX) * sizeof(double)));
-  MGCHK(hipMalloc((void**)&S->mg_dot, ((1 + MG_NULL_MAX) * MG_DOT_BLOCKS + 2) * sizeof(double)));      // per-workgroup partials of x_0 . rhs_0 and of the gauge sums, then the tickets of k_mg_up and k_mg_down
-  MGCHK(hipMemset(S->mg_dot, 0, ((1 + MG_NULL_MAX) * MG_DOT_BLOCKS + 2) * sizeof(double)));
-  S->hbm_bytes += (9 * S->mg_cells + 3 * S->mg_cells + (size_t)MG_NULL_MAX * S->mg_cells) * sizeof(double) + 9 * n0 * 8 + (S->chunk_cap + 64) * MG_PART * sizeof(double);
+  MGALLOC(S->mg_m0, MG_NULL_MAX * n0 + MG_NULL_MAX, EU_MEM_ZERO);
+  MGALLOC(S->mg_dot, (1 + MG_NULL_MAX) * MG_DOT_BLOCKS + 2, EU_MEM_ZERO);      // per-workgroup partials of x_0 . rhs_0 and of the gauge sums, then the tickets of k_mg_up and k_mg_down
   return EULER_OK;
 }
-#undef MGCHK
+#undef MGALLOC
 void eu_mg_release(euler_sim* S) {
   eu_mg_split_release(S);
-  for (double* d : {S->mg_a, S->mg_rhs, S->mg_part, S->mg_dot, S->mg_xbuf, S->mg_null0, S->mg_m0}) if (d) (void)hipFree(d);
-  if (S->mg_a0i) (void)hipFree(S->mg_a0i);
-  if (S->mg_inner0) (void)hipFree(S->mg_inner0);
+  eu_dev_free_group(S, EU_MEM_MG);
   S->mg_inner0 = nullptr;
   S->mg_wd = nullptr;
   S->mg_a = S->mg_rhs = S->mg_x = S->mg_part = S->mg_dot = S->mg_xbuf = S->mg_null0 = S->mg_m0 = nullptr;

@@ -38,8 +38,9 @@ struct MgSplitState {
 };
 static inline MgSplitState* mg_split_state(const euler_sim* S) { return static_cast<MgSplitState*>(S->mg_split); }
 
-static void mg_split_free(MgSplitState* st) {
-  for (double** b : {&st->msg, &st->gc, &st->sbuf, &st->abuf}) { if (*b) (void)hipFree(*b); *b = nullptr; }
+static void mg_split_free(euler_sim* S, MgSplitState* st) {
+  eu_dev_free_group(S, EU_MEM_SPLIT);
+  st->msg = st->gc = st->sbuf = st->abuf = nullptr;
 }
 // the sum over the ranks of n doubles, through the scratch of the cycle's partials (rewritten by the next cycle)
 static bool mg_split_agree(euler_sim* S, double* v, int n) {
@@ -80,10 +81,10 @@ static const eu_mg_split_plan* mg_split_plan(euler_sim* S) {
   for (int r = 0; r < R; ++r) { W.lo[r] = P.I[Lg][r][0]; W.hi[r] = P.I[Lg][r][1]; }
   int local_fail = P.overflow;      // what can fail on ONE rank (the segment table, the allocations): settled by a second all-reduce, so that every rank runs the same cycle
   const size_t mlen = (size_t)X + st->zone_doubles;
-  if (hipMalloc((void**)&st->msg, 4 * mlen * sizeof(double)) != hipSuccess || hipMalloc((void**)&st->gc, (size_t)R * (1 + MG_NULL_MAX) * sizeof(double)) != hipSuccess ||
+  if (eu_dalloc(S, &st->msg, 4 * mlen, EU_MEM_SPLIT, EU_DEV_QUIET) || eu_dalloc(S, &st->gc, (size_t)R * (1 + MG_NULL_MAX), EU_MEM_SPLIT, EU_DEV_QUIET) ||
       hipMemsetAsync(st->msg, 0, 4 * mlen * sizeof(double), S->stream) != hipSuccess || hipMemsetAsync(st->gc, 0, (size_t)R * (1 + MG_NULL_MAX) * sizeof(double), S->stream) != hipSuccess ||
-      (st->setup_ok && (hipMalloc((void**)&st->sbuf, 4 * (size_t)9 * (MG_SETUP_HALO + 1) * S->mg_nx[0] * sizeof(double)) != hipSuccess ||
-                        hipMalloc((void**)&st->abuf, (size_t)R * P.aslot * sizeof(double)) != hipSuccess ||
+      (st->setup_ok && (eu_dalloc(S, &st->sbuf, 4 * (size_t)9 * (MG_SETUP_HALO + 1) * S->mg_nx[0], EU_MEM_SPLIT, EU_DEV_QUIET) ||
+                        eu_dalloc(S, &st->abuf, (size_t)R * P.aslot, EU_MEM_SPLIT, EU_DEV_QUIET) ||
                         hipMemsetAsync(st->sbuf, 0, 4 * (size_t)9 * (MG_SETUP_HALO + 1) * S->mg_nx[0] * sizeof(double), S->stream) != hipSuccess ||
                         hipMemsetAsync(st->abuf, 0, (size_t)R * P.aslot * sizeof(double), S->stream) != hipSuccess))) {
     local_fail = 1;
@@ -94,7 +95,7 @@ static const eu_mg_split_plan* mg_split_plan(euler_sim* S) {
   if (!mg_split_agree(S, &lf, 1)) lf = 1.0;
   if (lf != 0.0) {
     if (local_fail) eu_set_error("the split cycle's segment table or message buffers could not be set up on this rank; every rank falls back to the replicated cycle");
-    mg_split_free(st);
+    mg_split_free(S, st);
     return nullptr;
   }
   st->valid = 1;
@@ -110,7 +111,7 @@ double* eu_mg_split_gc(euler_sim* S) { return mg_split_state(S)->gc; }
 void eu_mg_split_release(euler_sim* S) {
   MgSplitState* st = mg_split_state(S);
   if (!st) return;
-  mg_split_free(st);
+  mg_split_free(S, st);
   delete st;
   S->mg_split = nullptr;
   S->opt[EULER_OPT_MG_SPLIT_ACTIVE] = 0;

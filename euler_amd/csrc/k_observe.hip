@@ -21,26 +21,27 @@ int eu_observe_enter(const euler_sim* S, const char* who, const char* slab_reaso
   return EULER_OK;
 }
 
-// room for `bytes`: allocated by the first call, grown on demand and never shrunk; the old buffer is freed behind whatever of the stream still reads it
-int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes) {
+// room for `bytes`: allocated by the first call, grown on demand and never shrunk; the first `keep` bytes of the old buffer move over bit for bit, and the old buffer
+// is freed behind whatever of the stream still reads it.  The new block is recorded before the old one goes: a failure leaves buffer and ledger as they were
+int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf* b, size_t bytes, size_t keep) {
   if (bytes <= b->bytes) return EULER_OK;
   void* nb = nullptr;
-  if (hipMalloc(&nb, bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  if (eu_dev_alloc(S, &nb, bytes, EU_MEM_HANDLE, EU_DEV_QUIET)) {
     eu_set_error("%s: %zu bytes of device memory for %s", who, bytes, what);
     return EULER_ENOMEM;
   }
-  if (b->p) HIPCHK(hipStreamSynchronize(S->stream));
-  eu_devbuf_release(S, b);
+  if (keep && hipMemcpyAsync(nb, b->p, keep, hipMemcpyDeviceToDevice, S->stream) != hipSuccess) {
+    (void)hipGetLastError(); (void)eu_dev_free(S, nb);
+    eu_set_error("%s: the records could not be moved", who);
+    return EULER_EHIP;
+  }
+  if (b->p) {
+    const hipError_t e = hipStreamSynchronize(S->stream);
+    if (e != hipSuccess) { (void)eu_dev_free(S, nb); return eu_hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__); }
+  }
+  (void)eu_dev_free(S, b->p);
   b->p = nb; b->bytes = bytes;
-  S->hbm_bytes += bytes;
   return EULER_OK;
-}
-
-void eu_devbuf_release(euler_sim* S, eu_devbuf* b) {
-  if (b->p) (void)hipFree(b->p);
-  S->hbm_bytes -= b->bytes;
-  b->p = nullptr; b->bytes = 0;
 }
 
 int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t bytes) {

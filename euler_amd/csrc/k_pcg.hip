@@ -415,9 +415,8 @@ static bool tile_z_begin(euler_sim* S) {
   if (!tile_z_recompute(S)) return false;
   if (!S->zhalo) {
     const size_t nh = (size_t)S->geom.nbands * (S->geom.T / 16) * 128, nr = (size_t)S->geom.nbands * 2 * S->X;
-    if (hipMalloc(&S->zhalo, nh * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); S->zhalo = nullptr; return false; }
-    if (hipMalloc(&S->zrows, nr * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(S->zhalo); S->zhalo = S->zrows = nullptr; return false; }
-    S->hbm_bytes += (nh + nr) * sizeof(double);
+    if (eu_dalloc(S, &S->zhalo, nh, EU_MEM_HANDLE, EU_DEV_QUIET)) return false;
+    if (eu_dalloc(S, &S->zrows, nr, EU_MEM_HANDLE, EU_DEV_QUIET)) { (void)eu_dev_free(S, S->zhalo); S->zhalo = nullptr; return false; }
     HIPCHK(hipMemsetAsync(S->zhalo, 0, nh * sizeof(double), S->stream));
     HIPCHK(hipMemsetAsync(S->zrows, 0, nr * sizeof(double), S->stream));
   }
@@ -502,16 +501,14 @@ static int ring_begin(euler_sim* S) {
   for (int k = 2; k < n; ++k) {
     if (!S->s_ring_alloc[k]) {
       const size_t elems = S->Sw + EU_SKEW_SLACK;
-      if (hipMalloc(&S->s_ring_alloc[k], elems * sizeof(double)) != hipSuccess) {
+      if (eu_dev_alloc(S, &S->s_ring_alloc[k], elems * sizeof(double), EU_MEM_RING, EU_DEV_QUIET)) {
         // no room for the ring (13 GB at 16384^2 on one GPU): the solve goes on with the handle's own two arrays - the same bits (tests/test_gpu_tile_precond.py: the
         // forms test), p is updated every second iteration instead of every eighth - rather than fail a substep whose marker stage has already run
-        (void)hipGetLastError();
-        S->s_ring_alloc[k] = nullptr;
-        for (int j = 2; j < k; ++j) if (S->s_ring_alloc[j]) { (void)hipFree(S->s_ring_alloc[j]); S->s_ring_alloc[j] = nullptr; S->hbm_bytes -= elems * sizeof(double); }
+        eu_dev_free_group(S, EU_MEM_RING);
+        for (void*& d : S->s_ring_alloc) d = nullptr;
         S->opt[EULER_OPT_P_STEPS] = 2;
         return ring_begin(S);
       }
-      S->hbm_bytes += elems * sizeof(double);      // (euler_hbm_bytes: what the handle holds)
       HIPCHK(hipMemsetAsync(S->s_ring_alloc[k], 0, elems * sizeof(double), S->stream));
     }
     S->s_ring[k] = static_cast<double*>(S->s_ring_alloc[k]) + EU_SKEW_SLACK - S->skew_off;

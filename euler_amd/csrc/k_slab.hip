@@ -82,35 +82,26 @@ int eu_slab_alloc(euler_sim* S) {
   s->mig_cap = (size_t)16 * S->X + 4096;
   const size_t mig_bytes = 8 + s->mig_cap * sizeof(SlMigrant), row_bytes = (size_t)S->X * 4 * 2 * 2 + 64;   // ghost rows: <= 2 fields x 2 rows of floats
   s->buf_doubles = ((mig_bytes > row_bytes ? mig_bytes : row_bytes) + 7) / 8;
-  HIPCHK(hipMalloc((void**)&s->xg, s->blk * s->R));
-  HIPCHK(hipMemset(s->xg, 0, s->blk * s->R));
-  HIPCHK(hipMalloc((void**)&s->sortbuf, (size_t)s->sort_cap * 8));
-  HIPCHK(hipMalloc((void**)&s->ev_th, (size_t)s->sort_cap * 4));
-  HIPCHK(hipMalloc((void**)&s->ev_de, (size_t)s->sort_cap * 4));
-  HIPCHK(hipMalloc((void**)&s->d_sorted, (size_t)s->sort_cap * 4));
-  for (double** b : {&s->send_lo, &s->send_hi, &s->recv_lo, &s->recv_hi}) {
-    HIPCHK(hipMalloc((void**)b, s->buf_doubles * 8));
-    HIPCHK(hipMemset(*b, 0, s->buf_doubles * 8));
-  }
-  HIPCHK(hipMalloc((void**)&s->vec, (SL_MAXR + 8) * 8));
-  HIPCHK(hipMalloc((void**)&s->vec2, 2 * SL_MAXR * 8));
-  HIPCHK(hipMalloc((void**)&s->mask2, ((S->max_markers + 63) / 64) * 8));
+  int rc;
+  if ((rc = eu_dalloc(S, &s->xg, s->blk * s->R, EU_MEM_SLAB, EU_MEM_ZERO))) return rc;
+  if ((rc = eu_dalloc(S, &s->sortbuf, s->sort_cap, EU_MEM_SLAB))) return rc;      // (the sort's and the merge's scratch: written before it is read)
+  if ((rc = eu_dalloc(S, &s->ev_th, s->sort_cap, EU_MEM_SLAB))) return rc;
+  if ((rc = eu_dalloc(S, &s->ev_de, s->sort_cap, EU_MEM_SLAB))) return rc;
+  if ((rc = eu_dalloc(S, &s->d_sorted, s->sort_cap, EU_MEM_SLAB))) return rc;
+  for (double** b : {&s->send_lo, &s->send_hi, &s->recv_lo, &s->recv_hi})
+    if ((rc = eu_dalloc(S, b, s->buf_doubles, EU_MEM_SLAB, EU_MEM_ZERO))) return rc;
+  if ((rc = eu_dalloc(S, &s->vec, SL_MAXR + 8, EU_MEM_SLAB))) return rc;
+  if ((rc = eu_dalloc(S, &s->vec2, 2 * SL_MAXR, EU_MEM_SLAB))) return rc;
+  if ((rc = eu_dalloc(S, &s->mask2, (S->max_markers + 63) / 64, EU_MEM_SLAB))) return rc;
   s->ag_off.resize(s->R); s->ag_cnt.resize(s->R);
   for (int r = 0; r < s->R; ++r) { s->ag_off[r] = (int64_t)r * (int64_t)s->blk; s->ag_cnt[r] = (int64_t)s->blk; }
   return EULER_OK;
 }
 
-size_t eu_slab_bytes(const euler_sim* S) {
-  const SlabScratch* s = S->slab;
-  if (!s) return 0;
-  return s->blk * s->R + (size_t)s->sort_cap * 20 + 4 * s->buf_doubles * 8 + ((S->max_markers + 63) / 64) * 8 + (3 * SL_MAXR + 8) * 8;
-}
-
 void eu_slab_release(euler_sim* S) {
   SlabScratch* s = S->slab;
   if (!s) return;
-  void* dev[] = {s->xg, s->sortbuf, s->ev_th, s->ev_de, s->d_sorted, s->send_lo, s->send_hi, s->recv_lo, s->recv_hi, s->vec, s->vec2, s->mask2};
-  for (void* p : dev) if (p) (void)hipFree(p);
+  eu_dev_free_group(S, EU_MEM_SLAB);
   delete s;
   S->slab = nullptr;
 }

@@ -78,23 +78,7 @@ static int tr_reserve(euler_sim* S, size_t need) {
   size_t ncap = cap ? 2 * cap : TR_MIN_RECORDS;
   while (ncap < need) ncap *= 2;
   if (ncap > EULER_TRACERS_MAX) ncap = EULER_TRACERS_MAX;
-  const size_t bytes = ncap * sizeof(euler_tracer);
-  void* nb = nullptr;
-  if (hipMalloc(&nb, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    eu_set_error("euler_tracers_add: %zu bytes of device memory for the tracers", bytes);
-    return EULER_ENOMEM;
-  }
-  if (S->n_tracers && hipMemcpyAsync(nb, S->tracer_buf.p, S->n_tracers * sizeof(euler_tracer), hipMemcpyDeviceToDevice, S->stream) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(nb);
-    eu_set_error("euler_tracers_add: the records could not be moved");
-    return EULER_EHIP;
-  }
-  if (S->tracer_buf.p && hipStreamSynchronize(S->stream) != hipSuccess) { (void)hipFree(nb); return eu_hip_fail(hipGetLastError(), "hipStreamSynchronize", __FILE__, __LINE__); }
-  eu_devbuf_release(S, &S->tracer_buf);
-  S->tracer_buf.p = nb; S->tracer_buf.bytes = bytes;
-  S->hbm_bytes += bytes;
-  return EULER_OK;
+  return eu_devbuf_reserve(S, "euler_tracers_add", "the tracers", &S->tracer_buf, ncap * sizeof(euler_tracer), S->n_tracers * sizeof(euler_tracer));
 }
 
 extern "C" int euler_tracers_add(euler_sim* S, const float* xy, size_t n) {

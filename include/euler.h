@@ -913,7 +913,10 @@ int euler_profile_reset(euler_sim* sim);
 int euler_measure_copy_bandwidth(euler_sim* sim, size_t bytes, int32_t reps, double* gbps);
 int euler_measure_exchange(euler_sim* sim, int32_t reps, int32_t row_doubles, int32_t nsmall, double* us_per_exchange);   /* collective: one exchange point of a distributed PCG iteration over the installed communicator, HIP-event time per call */
 int euler_device_name(euler_sim* sim, char* out, int32_t cap);
-uint64_t euler_hbm_bytes(const euler_sim* sim);   /* device memory the handle allocated (a row-slab handle: its slab only) */
+/* Device memory the handle holds NOW (a row-slab handle: its slab only): the counted bytes of the handle's memory ledger (docs/handle_memory.md) - everything it
+ * allocated at creation and since (the solver's ring and halo buffers with the first solve that needs them, a coarse mode's arrays when it is selected, every
+ * feature's buffers), except the source cells' draws and the transfer scratch of euler_get_field / euler_set_field. */
+uint64_t euler_hbm_bytes(const euler_sim* sim);
 /* Diagnostics: the band pipeline of the most recent IC(0) sweep launch.  For each of this rank's bands in
  * sweep order, 8 words: wave entry, first block's boundary ready, wave exit (100 MHz constant clock
  * ticks), (blocks run << 32 | blocks that had to wait for the previous band), and four hand-off time
