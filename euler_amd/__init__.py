@@ -76,6 +76,16 @@ TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER
 TRACER_RASTER_ALL = 1
 TRACER_DTYPE = np.dtype({"names": ["x", "y", "path", "age", "wet_time", "substeps", "flags", "reserved"],
                          "formats": [np.float32] * 5 + [np.uint32] * 3, "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
+# the SETT chunk of a session file (csrc/euler_host.h eu_session_settings, docs/session.md); EULER_SESSION_* flags of euler_load_session
+SESSION_IGNORE_SETTINGS = 1
+SESSION_OPTS = 32
+SESSION_SETTINGS_DTYPE = np.dtype({"names": ["max_iterations", "dot_mode", "precond", "tile_records", "sweep_mode", "max_substeps", "rainbow", "pcg_precision", "resident",
+                                             "pcg_poll_interval", "viscosity_bits", "frame_time_bits", "tol", "nopts", "reserved", "opt"],
+                                   "formats": [np.int32] * 10 + [np.uint32] * 2 + [np.float64] + [np.int32] * 2 + [(np.int64, SESSION_OPTS)],
+                                   "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 56, 60, 64], "itemsize": 320})
+SESSION_STAT_KEYS = ("last_substeps", "last_pcg_iterations", "last_residual", "last_dt", "pad", "marker_dt_events", "marker_multi_events")      # the STAT chunk, 40 bytes
+SESSION_STAT_FORMAT = "<iidfIQQ"
+SESSION_TAGS = (b"TIME", b"FORC", b"HEAT", b"TRAC", b"BODY", b"RSED", b"SETT", b"STAT", b"END\0")      # the chunks of a session file, in file order
 GAUGE_VALUES = ("a", "b", "mean_a", "depth")      # euler_gauge_values, four doubles
 DIAG_VALUES = ("mean_abs_div", "kinetic_energy", "com_x", "com_y", "markers_per_cell", "crowded_fraction")      # euler_diag_values, six doubles
 (F_U, F_V, F_UTMP, F_VTMP, F_SOLID, F_SOURCE, F_SINK, F_COUNT, F_PREV_COUNT, F_MARKERS, F_PRECON,
@@ -132,7 +142,7 @@ EXPORTS = [
     "euler_get_field", "euler_set_field", "euler_set_markers", "euler_set_rng", "euler_get_stats",
     "euler_field_bytes", "euler_render", "euler_render_grids", "euler_render_grids_rgb", "euler_colorize", "euler_profile_enable",
     "euler_profile_class_count", "euler_profile_class_name", "euler_profile_get", "euler_profile_reset",
-    "euler_measure_copy_bandwidth", "euler_measure_exchange", "euler_device_name", "euler_hbm_bytes", "euler_sweep_timeline", "euler_save_state", "euler_load_state", "euler_set_comm", "euler_set_stream", "euler_slab_info",
+    "euler_measure_copy_bandwidth", "euler_measure_exchange", "euler_device_name", "euler_hbm_bytes", "euler_sweep_timeline", "euler_save_state", "euler_load_state", "euler_save_session", "euler_load_session", "euler_set_comm", "euler_set_stream", "euler_slab_info",
     "euler_rccl_unique_id", "euler_rccl_version", "euler_set_comm_rccl", "euler_comm_calls",
     "euler_p2p_export", "euler_p2p_connect", "euler_p2p_disconnect", "euler_p2p_calls", "euler_resident_info",
     "euler_set_option", "euler_get_option",
@@ -204,6 +214,8 @@ def load_library():
         "euler_sweep_timeline": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
         "euler_save_state": (C.c_int, [vp, C.c_char_p]),
         "euler_load_state": (C.c_int, [vp, C.c_char_p]),
+        "euler_save_session": (C.c_int, [vp, C.c_char_p]),
+        "euler_load_session": (C.c_int, [vp, C.c_char_p, C.c_uint32]),
         "euler_set_comm": (C.c_int, [vp, vp, i32]),                 # euler_amd/slab.py passes a CommOps struct
         "euler_set_stream": (C.c_int, [vp, vp]),
         "euler_slab_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -567,6 +579,122 @@ def write_snapshot(path, st):
     if dye:
         body += b"".join(np.ascontiguousarray(st[k], np.float32).tobytes() for k in SNAPSHOT_DYE)
     body += mk.tobytes()
+    with open(path, "wb") as f:
+        f.write(body + struct.pack("<Q", _fnv1a64(body)))
+
+
+def _session_core(raw, path):
+    """header, arrays and markers of a version-4 file: the dict of read_snapshot and the offset where the chunks begin"""
+    import struct
+    magic, version, X, Y, flags, n, rng, exhausted, _, frames, substeps, iters = struct.unpack_from("<8sIiiIQQiiQQQ", raw, 0)
+    if magic != b"EULERSNP" or version != 4:
+        raise ValueError("%s is not an euler session file (version 4)" % path)
+    out = {"X": X, "Y": Y, "n_markers": n, "rng_state": rng, "source_exhausted": exhausted, "frames": frames,
+           "total_substeps": substeps, "total_pcg_iterations": iters}
+    off, Cn = 72, X * Y
+    for name in SNAPSHOT_F32:
+        out[name] = np.frombuffer(raw, np.float32, Cn, off).reshape(Y, X).copy(); off += 4 * Cn
+    for name in SNAPSHOT_U8:
+        out[name] = np.frombuffer(raw, np.uint8, Cn, off).reshape(Y, X).copy(); off += Cn
+    out["precon"] = np.frombuffer(raw, np.float64, Cn, off).reshape(Y, X).copy(); off += 8 * Cn
+    if flags & 1:
+        for name in SNAPSHOT_DYE:
+            out[name] = np.frombuffer(raw, np.float32, Cn, off).reshape(Y, X).copy(); off += 4 * Cn
+    out["markers"] = np.frombuffer(raw, np.float32, 2 * n, off).reshape(n, 2).copy(); off += 8 * n
+    return out, off
+
+
+def read_session(path, verify=True):
+    """Parse a session file written by euler_save_session (layout: include/euler.h "session files") into the dict of read_snapshot plus
+      time      float
+      forcing   {"record": FORCING_DTYPE scalar array [1], "boxes": FORCE_BOX_DTYPE [nboxes]}
+      heat      {"on": bool, "record": HEAT_DTYPE [1], "boxes": HEAT_BOX_DTYPE [nboxes], "field": float32 [Y][X] or None}
+      tracers   TRACER_DTYPE [n]
+      bodies    {"bodies": BODY_DTYPE [n], "origins": int32 [n][2]}
+      reseed    {"record": RESEED_DTYPE [1], "stats": RESEED_STATS_DTYPE [1]}
+      settings  SESSION_SETTINGS_DTYPE [1]
+      stats     {SESSION_STAT_KEYS: value}
+    A file with other chunks than these in their order is refused, as the library refuses it."""
+    import struct
+    raw = open(path, "rb").read()
+    out, off = _session_core(raw, path)
+    X, Y = out["X"], out["Y"]
+    if verify and _fnv1a64(raw[:-8]) != struct.unpack_from("<Q", raw, len(raw) - 8)[0]:
+        raise ValueError("%s: checksum mismatch" % path)
+    for tag in SESSION_TAGS:
+        got, version, nbytes = struct.unpack_from("<4sIQ", raw, off)
+        if got != tag or version != 1:
+            raise ValueError("%s: chunk %r version %d where %r belongs" % (path, got, version, tag))
+        p, off = off + 16, off + 16 + ((nbytes + 7) & ~7)
+        arr = lambda dt, n, at: np.frombuffer(raw, dt, n, at).copy()
+        if tag == b"TIME":
+            out["time"] = struct.unpack_from("<d", raw, p)[0]
+        elif tag == b"FORC":
+            rec = arr(FORCING_DTYPE, 1, p)
+            out["forcing"] = {"record": rec, "boxes": arr(FORCE_BOX_DTYPE, int(rec["nboxes"][0]), p + 48)}
+        elif tag == b"HEAT":
+            on = struct.unpack_from("<i", raw, p)[0]
+            rec = arr(HEAT_DTYPE, 1, p + 8)
+            nb = int(rec["nboxes"][0])
+            out["heat"] = {"on": bool(on), "record": rec, "boxes": arr(HEAT_BOX_DTYPE, nb, p + 40),
+                           "field": arr(np.float32, X * Y, p + 40 + 24 * nb).reshape(Y, X) if on else None}
+        elif tag == b"TRAC":
+            out["tracers"] = arr(TRACER_DTYPE, struct.unpack_from("<Q", raw, p)[0], p + 8)
+        elif tag == b"BODY":
+            n = struct.unpack_from("<i", raw, p)[0]
+            out["bodies"] = {"bodies": arr(BODY_DTYPE, n, p + 8), "origins": arr(np.int32, 2 * n, p + 8 + 64 * n).reshape(n, 2)}
+        elif tag == b"RSED":
+            out["reseed"] = {"record": arr(RESEED_DTYPE, 1, p), "stats": arr(RESEED_STATS_DTYPE, 1, p + 32)}
+        elif tag == b"SETT":
+            out["settings"] = arr(SESSION_SETTINGS_DTYPE, 1, p)
+        elif tag == b"STAT":
+            out["stats"] = dict(zip(SESSION_STAT_KEYS, struct.unpack_from(SESSION_STAT_FORMAT, raw, p)))
+    if len(raw) != off + 8:
+        raise ValueError("%s: %d bytes between the END chunk and the checksum" % (path, len(raw) - off - 8))
+    return out
+
+
+def session_bytes(st, chunks=None):
+    """The bytes of a session file without its checksum: the core of write_snapshot's layout (version 4), then the chunks.  chunks: None for the chunks of `st`,
+    or a list of (tag, chunk_version, payload bytes) to forge another sequence (tests: an unknown tag, a chunk out of order)."""
+    import struct
+    Y, X = st["u"].shape
+    mk = np.ascontiguousarray(st["markers"], np.float32).reshape(-1, 2)
+    dye = "dye_r" in st
+    body = struct.pack("<8sIiiIQQiiQQQ", b"EULERSNP", 4, int(st.get("X", X)), int(st.get("Y", Y)), 1 if dye else 0, len(mk), int(st["rng_state"]),
+                       int(st.get("source_exhausted", 0)), 0, int(st.get("frames", 0)), int(st.get("total_substeps", 0)), int(st.get("total_pcg_iterations", 0)))
+    body += b"".join(np.ascontiguousarray(st[k], np.float32).tobytes() for k in SNAPSHOT_F32)
+    body += b"".join(np.ascontiguousarray(st[k], np.uint8).tobytes() for k in SNAPSHOT_U8)
+    body += np.ascontiguousarray(st["precon"], np.float64).tobytes()
+    if dye:
+        body += b"".join(np.ascontiguousarray(st[k], np.float32).tobytes() for k in SNAPSHOT_DYE)
+    body += mk.tobytes()
+    if chunks is None:
+        chunks = [(tag, 1, payload) for tag, payload in zip(SESSION_TAGS, session_payloads(st))]
+    for tag, version, payload in chunks:
+        body += struct.pack("<4sIQ", tag, version, len(payload)) + payload + b"\0" * (-len(payload) % 8)
+    return body
+
+
+def session_payloads(st):
+    """the payloads of the chunks of `st` (read_session's entries), in file order"""
+    import struct
+    tb = lambda a, dt: np.ascontiguousarray(a, dt).tobytes()
+    fo, he, bo, rs = st["forcing"], st["heat"], st["bodies"], st["reseed"]
+    heat = struct.pack("<ii", 1 if he["on"] else 0, 0) + tb(he["record"], HEAT_DTYPE) + tb(he["boxes"], HEAT_BOX_DTYPE)
+    if he["on"]:
+        heat += tb(he["field"], np.float32)
+    tr = np.ascontiguousarray(st["tracers"], TRACER_DTYPE)
+    return [struct.pack("<d", float(st["time"])), tb(fo["record"], FORCING_DTYPE) + tb(fo["boxes"], FORCE_BOX_DTYPE), heat, struct.pack("<Q", len(tr)) + tr.tobytes(),
+            struct.pack("<ii", len(bo["bodies"]), 0) + tb(bo["bodies"], BODY_DTYPE) + tb(bo["origins"], np.int32),
+            tb(rs["record"], RESEED_DTYPE) + tb(rs["stats"], RESEED_STATS_DTYPE), tb(st["settings"], SESSION_SETTINGS_DTYPE),
+            struct.pack(SESSION_STAT_FORMAT, *(st["stats"][k] for k in SESSION_STAT_KEYS)), b""]
+
+
+def write_session(path, st, chunks=None):
+    """Inverse of read_session.  st["X"] / st["Y"], where present, go into the header as they are (tests forge a wrong size with them); chunks as for session_bytes."""
+    import struct
+    body = session_bytes(st, chunks)
     with open(path, "wb") as f:
         f.write(body + struct.pack("<Q", _fnv1a64(body)))
 
@@ -1008,6 +1136,15 @@ class Simulation:
 
     def load_state(self, path):
         _check(self.L.euler_load_state(self.h, os.fsencode(path)))
+        return self
+
+    def save_session(self, path):
+        """A session file (include/euler.h "session files", docs/session.md): the snapshot plus clock, forcing, heat, tracers, bodies, reseed record and totals."""
+        _check(self.L.euler_save_session(self.h, os.fsencode(path)))
+
+    def load_session(self, path, ignore_settings=False):
+        """Puts the handle into the saving handle's state; a refused load leaves it as it was.  ignore_settings: do not compare the file's SETT chunk with this handle's settings."""
+        _check(self.L.euler_load_session(self.h, os.fsencode(path), SESSION_IGNORE_SETTINGS if ignore_settings else 0))
         return self
 
     def sweep_timeline(self, raw=False):

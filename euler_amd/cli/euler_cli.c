@@ -15,7 +15,8 @@
  *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
  *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]...
  *         [--reseed THIN[:fill]]
- *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>
+ *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show]
+ *         [--session-out FILE [--session-every N]] [--session-in FILE] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
  * (the scenario argument may then be omitted); --checkpoint writes one after the last frame.
  * --fit draws the WHOLE interior fitted into the window (euler_render_fit: boxes of cells reduced on the device, docs/overview.md) instead of
@@ -70,6 +71,14 @@
  * frame of --fit / --view (both regimes) and the images of --ppm (euler_tracer_raster + euler_tracer_paint, behind any --paint; the other water pixels blue unless
  * --rainbow or --paint colour them; the images are then written in the dye mode); with --view, and only with it, the key t toggles it.  A malformed spec, a 1025th
  * tracer, a 65th box or emitter, a position or box outside the interior and --tracers-show without --fit, --view or --ppm are usage errors.
+ * --session-out FILE writes a session file (euler_save_session, docs/session.md: the snapshot plus clock, forcing, heat, tracers, bodies, reseed record and totals)
+ * after the last frame; with --session-every N also behind every N-th frame, to the same name (written as FILE.tmp and renamed: a reader never sees half a file).
+ * --session-in FILE starts from a session instead of a scenario: the frame counter begins at the file's `frames` F0, so --edit F:..., --emit's schedule, the frame
+ * columns of --stats / --gauges / --tracers, the numbers of --ppm and --frames N (absolute) continue, and from `--- frame F0` on the output is the uninterrupted
+ * run's.  Frame F0 is drawn and logged as the saving run drew it; the edits and emitters of frames <= F0 are the saving run's and are not applied again.  What the
+ * file carries cannot be given again: a scenario, --resume, --upscale, --gravity, --shake, --force, --heat*, --body, --reseed, --tracer and --tracer-box beside
+ * --session-in are usage errors.  The settings (--size, --rainbow, --solver, --max-iterations, --advection, --maccormack) are given again and checked against the
+ * file: a mismatch exits with status 1 and names the field.  --checkpoint and --resume are unchanged.
  */
 #include <errno.h>
 #include <signal.h>
@@ -88,12 +97,13 @@
 #include "cli_reseed.h"
 #include "cli_heat.h"
 #include "cli_tracers.h"
+#include "cli_session.h"
 #include "euler_host.h"      /* eu_tracer_lattice */
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--reseed THIN[:fill]] [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--reseed THIN[:fill]] [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] [--session-out FILE [--session-every N]] [--session-in FILE] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -439,6 +449,9 @@ int main(int argc, char** argv) {
   cli_emitter emitters[MAX_EMITTERS];
   int n_seeds = 0, n_points = 0, n_tboxes = 0, n_emitters = 0, tracers_every = 1, tracers_show = 0;
   const char* tracers = NULL;
+  const char* session_out = NULL;
+  const char* session_in = NULL;
+  int session_every = 0;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--size") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &cfg.X, &cfg.Y) != 2) { usage(argv[0]); return 1; } }
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) { if (sscanf(argv[++i], "%dx%d", &wx, &wy) != 2) { usage(argv[0]); return 1; } window_given = 1; }
@@ -527,10 +540,20 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     /* marker density control (docs/reseed.md) */
     else if (!strcmp(argv[i], "--reseed") && i + 1 < argc) { if (parse_reseed(argv[++i], &reseed) != 0) { usage(argv[0]); return 1; } reseed_given = 1; }
+    /* session files (docs/session.md) */
+    else if (!strcmp(argv[i], "--session-out") && i + 1 < argc) session_out = argv[++i];
+    else if (!strcmp(argv[i], "--session-every") && i + 1 < argc) { session_every = atoi(argv[++i]); if (session_every < 1) { usage(argv[0]); return 1; } }
+    else if (!strcmp(argv[i], "--session-in") && i + 1 < argc) session_in = argv[++i];
     else if (argv[i][0] == '-') { fprintf(stderr, "Unrecognized input: %s\n", argv[i]); return 1; }   /* main.c:995 */
     else scenario = argv[i];
   }
-  if (!scenario && !resume) { usage(argv[0]); return 1; }                                                       /* main.c:986-989 */
+  if (!scenario && !resume && !session_in) { usage(argv[0]); return 1; }                                        /* main.c:986-989 */
+  if (session_every && !session_out) { usage(argv[0]); return 1; }
+  if (session_in) {      /* what the file carries cannot be given again */
+    const cli_session_clash clash = {scenario != NULL, resume != NULL, upscale, forcing_given, heat_given || heat_extra, n_bodies, reseed_given, n_seeds};
+    const char* what = cli_session_conflict(&clash);
+    if (what) { fprintf(stderr, "--session-in: %s comes from the session file\n", what); usage(argv[0]); return 1; }
+  }
 
   if (view && (fit || vbox[0] < 1 || vbox[1] < 1 || vbox[2] > cfg.X - 2 || vbox[3] > cfg.Y - 2 || vbox[0] > vbox[2] || vbox[1] > vbox[3])) { usage(argv[0]); return 1; }
   for (int k = 0; k < n_edits; ++k) {
@@ -548,7 +571,7 @@ int main(int argc, char** argv) {
     if (fb->x0 < 1 || fb->y0 < 1 || fb->x1 > cfg.X - 2 || fb->y1 > cfg.Y - 2 || fb->x0 > fb->x1 || fb->y0 > fb->y1) { usage(argv[0]); return 1; }
   }
   forcing.nboxes = n_force_boxes;
-  if (!heat_given && (heat_extra || paint == CLI_PAINT_HEAT)) { usage(argv[0]); return 1; }      /* --heat-source, --heat-box, --heat-init, --paint heat: only with --heat */
+  if (!heat_given && (heat_extra || (paint == CLI_PAINT_HEAT && !session_in))) { usage(argv[0]); return 1; }      /* --heat-source, --heat-box, --heat-init, --paint heat: only with --heat */
   for (int k = 0; k < n_heat_boxes; ++k) {
     const euler_heat_box* hb = &heat_boxes[k];
     if (hb->x0 < 1 || hb->y0 < 1 || hb->x1 > cfg.X - 2 || hb->y1 > cfg.Y - 2 || hb->x0 > hb->x1 || hb->y0 > hb->y1) { usage(argv[0]); return 1; }
@@ -599,7 +622,7 @@ int main(int argc, char** argv) {
   app.show = tracers_show;
   if (euler_create(&cfg, &app.sim) != EULER_OK || euler_set_option(app.sim, EULER_OPT_ADVECT_RK2, advect_rk2) != EULER_OK ||
       euler_set_option(app.sim, EULER_OPT_ADVECT_MACCORMACK, maccormack) != EULER_OK ||
-      (resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
+      (session_in ? euler_load_session(app.sim, session_in, 0) : resume ? euler_load_state(app.sim, resume) : euler_load_scenario_file(app.sim, scenario, upscale)) != EULER_OK ||
       (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK) ||
       (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK) ||      /* (behind the load and the forcing) */
       (n_bodies && euler_set_bodies(app.sim, bodies, n_bodies) != EULER_OK) ||
@@ -613,6 +636,9 @@ int main(int argc, char** argv) {
       return 1;
     }
   if (add_seeds(app.sim, seeds, n_seeds) != 0) return 1;
+  const long long first = session_in ? cli_session_first_frame(app.sim) : 0;      /* a session continues its frame numbers */
+  if (first < 0) { fprintf(stderr, "%s\n", euler_last_error()); return 1; }
+  const int f0 = (int)first;
   if (interactive) {
     if (enable_raw_mode() == -1) { perror("failed to enable raw mode"); return 1; }
     write_all("\x1b[2J\x1b[H", 7);      /* clear_screen_now */
@@ -638,8 +664,8 @@ int main(int argc, char** argv) {
   struct timespec next;
   clock_gettime(CLOCK_MONOTONIC, &next);
   size_t key_pos = 0;
-  for (int f = 0; !rc_exit && (frames < 0 || f <= frames); ++f) {
-    if (f > 0) {
+  for (int f = f0; !rc_exit && (frames < 0 || f <= frames); ++f) {
+    if (f > f0) {
       /* one key per frame: a scripted one (--keys) or whatever the terminal has (non-blocking read) */
       char c = '\0';
       if (keys) { if (keys[key_pos]) c = keys[key_pos++]; }
@@ -659,9 +685,9 @@ int main(int argc, char** argv) {
         else clock_nanosleep(CLOCK_MONOTONIC, TIMER_ABSTIME, &next, NULL);
       }
     }
-    else for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == 0 && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;      /* before frame 0 is drawn */
+    else if (!session_in) for (int k = 0; k < n_edits && !rc_exit; ++k) if (edits[k].frame == 0 && apply_edit(app.sim, edits[k].op, edits[k].box) != 0) rc_exit = 1;      /* before frame 0 is drawn */
     if (rc_exit) break;
-    if (f == 0 && n_emitters && emit_tracers(app.sim, emitters, n_emitters, 0) != 0) { rc_exit = 1; break; }
+    if (f == 0 && !session_in && n_emitters && emit_tracers(app.sim, emitters, n_emitters, 0) != 0) { rc_exit = 1; break; }
     if (g_resized) {                        /* handle_window_size_changed (main.c:1010-1014) */
       g_resized = 0;
       if (window_size(&wx, &wy) == 0) write_all("\x1b[2J\x1b[H", 7);
@@ -708,12 +734,14 @@ int main(int argc, char** argv) {
     if (stats_file && f % stats_every == 0 && write_stats_line(app.sim, stats_file, stats, f, cfg.X, cfg.Y) != 0) { rc_exit = 1; break; }
     if (gauges_file && f % gauges_every == 0 && write_gauge_lines(app.sim, gauges_file, gauges, f, gauge_list, n_gauges) != 0) { rc_exit = 1; break; }
     if (tracers_file && f % tracers_every == 0 && write_tracer_lines(app.sim, tracers_file, tracers, f) != 0) { rc_exit = 1; break; }
+    if (session_every && f > f0 && f % session_every == 0 && cli_session_save(app.sim, session_out) != 0) { rc_exit = 1; break; }
   }
   if (interactive) { write_all("\x1b[2J\x1b[H", 7); restore_terminal(); }
   if (stats_file && fclose(stats_file) != 0 && !rc_exit) { fprintf(stderr, "--stats: cannot write %s: %s\n", stats, strerror(errno)); rc_exit = 1; }
   if (tracers_file && fclose(tracers_file) != 0 && !rc_exit) { fprintf(stderr, "--tracers: cannot write %s: %s\n", tracers, strerror(errno)); rc_exit = 1; }
   if (gauges_file && fclose(gauges_file) != 0 && !rc_exit) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }
+  if (!rc_exit && session_out && cli_session_save(app.sim, session_out) != 0) rc_exit = 1;
   euler_stats st;
   if (euler_get_stats(app.sim, &st) == EULER_OK)
     fprintf(stderr, "frames %llu substeps %llu pcg_iterations %llu markers %llu\n", (unsigned long long)st.frames,

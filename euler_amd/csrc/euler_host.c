@@ -989,3 +989,244 @@ int euler_tracer_paint(const uint32_t* counts, euler_overview_px* px, int32_t W,
   }
   return EULER_OK;
 }
+
+/* ---- session files: a version-4 snapshot composed, parsed and checked in memory (include/euler.h "session files", docs/session.md) ---- */
+
+uint64_t eu_fnv1a64(uint64_t h, const void* p, size_t n) {
+  const unsigned char* b = (const unsigned char*)p;
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  return h;
+}
+
+#define SE_HEADER 72u
+#define SE_CHUNK_HEADER 16u
+#define SE_NCHUNKS 9
+static const char SE_TAGS[SE_NCHUNKS][4] = {{'T', 'I', 'M', 'E'}, {'F', 'O', 'R', 'C'}, {'H', 'E', 'A', 'T'}, {'T', 'R', 'A', 'C'},
+                                   {'B', 'O', 'D', 'Y'}, {'R', 'S', 'E', 'D'}, {'S', 'E', 'T', 'T'}, {'S', 'T', 'A', 'T'}, {'E', 'N', 'D', 0}};
+static size_t se_pad8(size_t n) { return (n + 7u) & ~(size_t)7u; }
+
+size_t eu_session_core_bytes(int32_t X, int32_t Y, int32_t dye, uint64_t n_markers) {
+  const size_t C = (size_t)X * (size_t)Y;
+  return SE_HEADER + C * 29u + (dye ? C * 24u : 0u) + (size_t)n_markers * 8u;
+}
+
+/* the payload sizes of the chunks, in file order */
+static void se_payloads(const eu_session* s, size_t out[SE_NCHUNKS]) {
+  const size_t C = (size_t)s->X * (size_t)s->Y;
+  out[0] = 8;
+  out[1] = sizeof(euler_forcing) + (size_t)s->forcing.nboxes * sizeof(euler_force_box);
+  out[2] = 8 + sizeof(euler_heat) + (size_t)s->heat.nboxes * sizeof(euler_heat_box) + (s->heat_on ? C * 4u : 0u);
+  out[3] = 8 + (size_t)s->n_tracers * sizeof(euler_tracer);
+  out[4] = 8 + (size_t)s->n_bodies * (sizeof(euler_body) + 8u);
+  out[5] = sizeof(euler_reseed) + sizeof(euler_reseed_stats);
+  out[6] = sizeof(eu_session_settings);
+  out[7] = 40;
+  out[8] = 0;
+}
+
+size_t eu_session_chunk_bytes(const eu_session* s) {
+  size_t pay[SE_NCHUNKS], n = 0;
+  se_payloads(s, pay);
+  for (int k = 0; k < SE_NCHUNKS; ++k) n += SE_CHUNK_HEADER + se_pad8(pay[k]);
+  return n;
+}
+
+size_t eu_session_put_chunks(const eu_session* s, unsigned char* out) {
+  size_t pay[SE_NCHUNKS];
+  se_payloads(s, pay);
+  const size_t C = (size_t)s->X * (size_t)s->Y;
+  unsigned char* w = out;
+#define PUT(p, n) do { if ((n) > 0) memcpy(w, (p), (n)); w += (n); } while (0)
+  for (int k = 0; k < SE_NCHUNKS; ++k) {
+    const uint32_t version = 1;
+    const uint64_t bytes = (uint64_t)pay[k];
+    unsigned char* const start = w + SE_CHUNK_HEADER;
+    PUT(SE_TAGS[k], 4); PUT(&version, 4); PUT(&bytes, 8);
+    const int32_t zero = 0;
+    switch (k) {
+      case 0: PUT(&s->time, 8); break;
+      case 1: PUT(&s->forcing, sizeof s->forcing); PUT(s->force_boxes, (size_t)s->forcing.nboxes * sizeof(euler_force_box)); break;
+      case 2: { const int32_t on = s->heat_on ? 1 : 0;
+        PUT(&on, 4); PUT(&zero, 4); PUT(&s->heat, sizeof s->heat); PUT(s->heat_boxes, (size_t)s->heat.nboxes * sizeof(euler_heat_box));
+        if (on) PUT(s->heat_field, C * 4u);
+        break; }
+      case 3: PUT(&s->n_tracers, 8); PUT(s->tracers, (size_t)s->n_tracers * sizeof(euler_tracer)); break;
+      case 4: PUT(&s->n_bodies, 4); PUT(&zero, 4); PUT(s->bodies, (size_t)s->n_bodies * sizeof(euler_body));
+        for (int32_t b = 0; b < s->n_bodies; ++b) { PUT(&s->body_ox[b], 4); PUT(&s->body_oy[b], 4); }
+        break;
+      case 5: PUT(&s->reseed, sizeof s->reseed); PUT(&s->reseed_stats, sizeof s->reseed_stats); break;
+      case 6: PUT(&s->settings, sizeof s->settings); break;
+      case 7: PUT(&s->last_substeps, 4); PUT(&s->last_pcg_iterations, 4); PUT(&s->last_residual, 8); PUT(&s->last_dt, 4); PUT(&zero, 4);
+        PUT(&s->marker_dt_events, 8); PUT(&s->marker_multi_events, 8);
+        break;
+      default: break;
+    }
+    while ((size_t)(w - start) < se_pad8(pay[k])) *w++ = 0;
+  }
+#undef PUT
+  return (size_t)(w - out);
+}
+
+int eu_session_parse(const void* buf, size_t n, int32_t X, int32_t Y, int32_t dye, uint64_t max_markers, eu_session* out, char* why, size_t cap) {
+#define REFUSE(code, ...) do { if (why && cap) snprintf(why, cap, __VA_ARGS__); return (code); } while (0)
+  if (!buf || !out || X < 3 || Y < 3) REFUSE(EULER_EINVAL, "null argument or a grid below 3 x 3");
+  const unsigned char* b = (const unsigned char*)buf;
+  eu_session s;
+  memset(&s, 0, sizeof s);
+  uint32_t version, reserved;
+  int32_t reserved2;
+  if (n < SE_HEADER + 8u) REFUSE(EULER_EIO, "truncated: %zu bytes are less than a header and a checksum", n);
+  if (memcmp(b, "EULERSNP", 8) != 0) REFUSE(EULER_EINVAL, "not an euler state snapshot");
+  memcpy(&version, b + 8, 4); memcpy(&s.X, b + 12, 4); memcpy(&s.Y, b + 16, 4); memcpy(&reserved, b + 20, 4);
+  memcpy(&s.n_markers, b + 24, 8); memcpy(&s.rng_state, b + 32, 8); memcpy(&s.source_exhausted, b + 40, 4); memcpy(&reserved2, b + 44, 4);
+  memcpy(&s.frames, b + 48, 8); memcpy(&s.total_substeps, b + 56, 8); memcpy(&s.total_pcg_iterations, b + 64, 8);
+  if (version != 4) REFUSE(EULER_EINVAL, "snapshot version %u is not a session file (version 4)", version);
+  if (s.X != X || s.Y != Y) REFUSE(EULER_EINVAL, "session grid %dx%d does not fit this %dx%d handle", s.X, s.Y, X, Y);
+  if ((reserved & ~1u) != 0 || reserved2 != 0) REFUSE(EULER_EINVAL, "reserved header words %u, %d", reserved, reserved2);
+  s.dye = (int32_t)(reserved & 1u);
+  if (s.dye != (dye != 0)) REFUSE(EULER_EINVAL, "the session %s the dye fields but this handle was created %s euler_config.rainbow", s.dye ? "carries" : "lacks", dye ? "with" : "without");
+  if (s.n_markers > max_markers) REFUSE(EULER_EINVAL, "the session holds %llu markers, more than this handle's capacity %llu", (unsigned long long)s.n_markers, (unsigned long long)max_markers);
+  const size_t C = (size_t)X * (size_t)Y, core = eu_session_core_bytes(X, Y, s.dye, s.n_markers), end = n - 8u;
+  if (core > end) REFUSE(EULER_EIO, "truncated: the arrays and markers need %zu bytes, the file has %zu", core + 8u, n);
+  uint64_t stored;
+  memcpy(&stored, b + end, 8);
+  if (stored != eu_fnv1a64(EU_FNV_BASIS, b, end)) REFUSE(EULER_EIO, "truncated or corrupt (checksum)");
+  s.solid = b + SE_HEADER + C * 16u;
+  /* the chunks: each in its place, its size the one its own counts give */
+  size_t at = core;
+  for (int k = 0; k < SE_NCHUNKS; ++k) {
+    char tag[5] = {0, 0, 0, 0, 0};
+    uint32_t cv;
+    uint64_t bytes;
+    if (end - at < SE_CHUNK_HEADER) REFUSE(EULER_EINVAL, "the chunks end in front of %.4s (every session ends with an END chunk)", SE_TAGS[k]);
+    memcpy(tag, b + at, 4); memcpy(&cv, b + at + 4, 4); memcpy(&bytes, b + at + 8, 8);
+    for (int c = 0; c < 4; ++c) if (tag[c] != 0 && (tag[c] < 32 || tag[c] > 126)) tag[c] = '?';
+    if (memcmp(b + at, SE_TAGS[k], 4) != 0) {
+      int known = 0;
+      for (int j = 0; j < SE_NCHUNKS; ++j) known |= memcmp(b + at, SE_TAGS[j], 4) == 0;
+      if (known) REFUSE(EULER_EINVAL, "chunk %s stands where %.4s belongs (the chunks come once each, in a fixed order)", tag, SE_TAGS[k]);
+      REFUSE(EULER_EINVAL, "unknown chunk tag '%s' where %.4s belongs", tag, SE_TAGS[k]);
+    }
+    if (cv != 1) REFUSE(EULER_EINVAL, "chunk %s: unknown chunk version %u", tag, cv);
+    at += SE_CHUNK_HEADER;
+    if (bytes > end - at || se_pad8((size_t)bytes) > end - at) REFUSE(EULER_EINVAL, "chunk %s: %llu bytes of payload, %zu left in the file", tag, (unsigned long long)bytes, end - at);
+    const unsigned char* p = b + at;
+    const size_t len = (size_t)bytes;
+    size_t want = 0;
+    char rec[320];
+#define SIZE_IS(w) do { want = (w); if (len != want) REFUSE(EULER_EINVAL, "chunk %s: %zu bytes of payload, its counts give %zu", tag, len, want); } while (0)
+#define AT_LEAST(w) do { if (len < (size_t)(w)) REFUSE(EULER_EINVAL, "chunk %s: %zu bytes of payload are less than its fixed part, %zu", tag, len, (size_t)(w)); } while (0)
+    switch (k) {
+      case 0:
+        SIZE_IS(8);
+        memcpy(&s.time, p, 8);
+        if (!isfinite(s.time)) REFUSE(EULER_EINVAL, "chunk TIME: the clock is not finite");
+        break;
+      case 1:
+        AT_LEAST(sizeof s.forcing);
+        memcpy(&s.forcing, p, sizeof s.forcing);
+        if (s.forcing.nboxes < 0 || s.forcing.nboxes > EULER_FORCE_BOXES_MAX) REFUSE(EULER_EINVAL, "chunk FORC: %d boxes (0 ... %d)", s.forcing.nboxes, EULER_FORCE_BOXES_MAX);
+        SIZE_IS(sizeof s.forcing + (size_t)s.forcing.nboxes * sizeof(euler_force_box));
+        memcpy(s.force_boxes, p + sizeof s.forcing, (size_t)s.forcing.nboxes * sizeof(euler_force_box));
+        if (eu_forcing_check(&s.forcing, s.force_boxes, X, Y, rec, sizeof rec)) REFUSE(EULER_EINVAL, "chunk FORC: %s", rec);
+        break;
+      case 2: {
+        int32_t pad;
+        AT_LEAST(8 + sizeof s.heat);
+        memcpy(&s.heat_on, p, 4); memcpy(&pad, p + 4, 4); memcpy(&s.heat, p + 8, sizeof s.heat);
+        if ((s.heat_on != 0 && s.heat_on != 1) || pad != 0) REFUSE(EULER_EINVAL, "chunk HEAT: on = %d, pad = %d", s.heat_on, pad);
+        if (s.heat.nboxes < 0 || s.heat.nboxes > EULER_HEAT_BOXES_MAX) REFUSE(EULER_EINVAL, "chunk HEAT: %d boxes (0 ... %d)", s.heat.nboxes, EULER_HEAT_BOXES_MAX);
+        const size_t fixed = 8 + sizeof s.heat + (size_t)s.heat.nboxes * sizeof(euler_heat_box);
+        SIZE_IS(fixed + (s.heat_on ? C * 4u : 0u));
+        memcpy(s.heat_boxes, p + 8 + sizeof s.heat, (size_t)s.heat.nboxes * sizeof(euler_heat_box));
+        if (eu_heat_check(&s.heat, s.heat_boxes, X, Y, NULL, rec, sizeof rec)) REFUSE(EULER_EINVAL, "chunk HEAT: %s", rec);
+        if (s.heat_on) {
+          s.heat_field = p + fixed;
+          for (size_t i = 0; i < C; ++i) {
+            float t;
+            memcpy(&t, s.heat_field + 4u * i, 4);
+            if (!eu_heat_value_ok(t)) REFUSE(EULER_EINVAL, "chunk HEAT: cell %zu holds %g (finite and at most 1e4 in size)", i, (double)t);
+          }
+        }
+        break; }
+      case 3:
+        AT_LEAST(8);
+        memcpy(&s.n_tracers, p, 8);
+        if (s.n_tracers > EULER_TRACERS_MAX) REFUSE(EULER_EINVAL, "chunk TRAC: %llu tracers (at most %u)", (unsigned long long)s.n_tracers, (unsigned)EULER_TRACERS_MAX);
+        SIZE_IS(8 + (size_t)s.n_tracers * sizeof(euler_tracer));
+        s.tracers = p + 8;
+        for (uint64_t i = 0; i < s.n_tracers; ++i) {
+          euler_tracer t;
+          memcpy(&t, s.tracers + (size_t)i * sizeof t, sizeof t);
+          if (t.reserved != 0) REFUSE(EULER_EINVAL, "chunk TRAC: tracer %llu: reserved must be 0", (unsigned long long)i);
+          if (!(isfinite(t.x) && isfinite(t.y)) && (t.flags & (EULER_TRACER_RETIRED | EULER_TRACER_LOST)) != (EULER_TRACER_RETIRED | EULER_TRACER_LOST))
+            REFUSE(EULER_EINVAL, "chunk TRAC: tracer %llu: a position that is not finite on a record that is not flagged lost", (unsigned long long)i);
+        }
+        break;
+      case 4: {
+        int32_t pad;
+        AT_LEAST(8);
+        memcpy(&s.n_bodies, p, 4); memcpy(&pad, p + 4, 4);
+        if (s.n_bodies < 0 || s.n_bodies > EULER_BODIES_MAX || pad != 0) REFUSE(EULER_EINVAL, "chunk BODY: %d bodies (0 ... %d), pad = %d", s.n_bodies, EULER_BODIES_MAX, pad);
+        SIZE_IS(8 + (size_t)s.n_bodies * (sizeof(euler_body) + 8u));
+        memcpy(s.bodies, p + 8, (size_t)s.n_bodies * sizeof(euler_body));
+        if (eu_body_check(s.bodies, s.n_bodies, X, Y, rec, sizeof rec)) REFUSE(EULER_EINVAL, "chunk BODY: %s", rec);
+        for (int32_t q = 0; q < s.n_bodies; ++q) {
+          const unsigned char* o = p + 8 + (size_t)s.n_bodies * sizeof(euler_body) + 8u * (size_t)q;
+          memcpy(&s.body_ox[q], o, 4); memcpy(&s.body_oy[q], o + 4, 4);
+          const int32_t ox = s.body_ox[q], oy = s.body_oy[q], w = s.bodies[q].w, h = s.bodies[q].h;
+          if (ox < 2 || oy < 2 || ox > X - 2 - w || oy > Y - 2 - h) REFUSE(EULER_EINVAL, "chunk BODY: body %d: the origin (%d, %d) leaves [2, %d] x [2, %d]", q, ox, oy, X - 2 - w, Y - 2 - h);
+          for (int32_t y = oy; y < oy + h; ++y)
+            for (int32_t x = ox; x < ox + w; ++x)
+              if (!s.solid[(size_t)y * (size_t)X + (size_t)x]) REFUSE(EULER_EINVAL, "chunk BODY: body %d stands at (%d, %d) but cell (%d, %d) of the session's solid grid is open", q, ox, oy, x, y);
+        }
+        break; }
+      case 5:
+        SIZE_IS(sizeof s.reseed + sizeof s.reseed_stats);
+        memcpy(&s.reseed, p, sizeof s.reseed); memcpy(&s.reseed_stats, p + sizeof s.reseed, sizeof s.reseed_stats);
+        if (eu_reseed_check(&s.reseed, rec, sizeof rec)) REFUSE(EULER_EINVAL, "chunk RSED: %s", rec);
+        break;
+      case 6:
+        SIZE_IS(sizeof s.settings);
+        memcpy(&s.settings, p, sizeof s.settings);
+        if (s.settings.reserved != 0 || s.settings.nopts < 1 || s.settings.nopts > EU_SESSION_OPTS) REFUSE(EULER_EINVAL, "chunk SETT: nopts = %d, reserved = %d", s.settings.nopts, s.settings.reserved);
+        break;
+      case 7: {
+        int32_t pad;
+        SIZE_IS(40);
+        memcpy(&s.last_substeps, p, 4); memcpy(&s.last_pcg_iterations, p + 4, 4); memcpy(&s.last_residual, p + 8, 8); memcpy(&s.last_dt, p + 16, 4); memcpy(&pad, p + 20, 4);
+        memcpy(&s.marker_dt_events, p + 24, 8); memcpy(&s.marker_multi_events, p + 32, 8);
+        if (pad != 0) REFUSE(EULER_EINVAL, "chunk STAT: pad = %d", pad);
+        break; }
+      default:
+        SIZE_IS(0);
+        break;
+    }
+#undef SIZE_IS
+#undef AT_LEAST
+    at += se_pad8(len);
+  }
+  if (at != end) REFUSE(EULER_EINVAL, "%zu bytes between the END chunk and the checksum", end - at);
+#undef REFUSE
+  *out = s;
+  return EULER_OK;
+}
+
+int eu_session_settings_diff(const eu_session_settings* f, const eu_session_settings* h, char* why, size_t cap) {
+#define DIFF_I(field) do { if (f->field != h->field) { if (why && cap) snprintf(why, cap, "%s: the session has %lld, the handle %lld", #field, (long long)f->field, (long long)h->field); return 1; } } while (0)
+  DIFF_I(max_iterations); DIFF_I(dot_mode); DIFF_I(precond); DIFF_I(tile_records); DIFF_I(sweep_mode); DIFF_I(max_substeps); DIFF_I(rainbow); DIFF_I(pcg_precision);
+  DIFF_I(resident); DIFF_I(pcg_poll_interval);
+#undef DIFF_I
+  float a, b;
+  memcpy(&a, &f->viscosity_bits, 4); memcpy(&b, &h->viscosity_bits, 4);
+  if (f->viscosity_bits != h->viscosity_bits) { if (why && cap) snprintf(why, cap, "viscosity: the session has %.9g, the handle %.9g", (double)a, (double)b); return 1; }
+  memcpy(&a, &f->frame_time_bits, 4); memcpy(&b, &h->frame_time_bits, 4);
+  if (f->frame_time_bits != h->frame_time_bits) { if (why && cap) snprintf(why, cap, "frame_time: the session has %.9g, the handle %.9g", (double)a, (double)b); return 1; }
+  if (memcmp(&f->tol, &h->tol, 8) != 0) { if (why && cap) snprintf(why, cap, "tol: the session has %.17g, the handle %.17g", f->tol, h->tol); return 1; }
+  const int32_t nopts = f->nopts > h->nopts ? f->nopts : h->nopts;
+  for (int32_t k = 1; k < nopts && k < EU_SESSION_OPTS; ++k) {
+    if (k == EULER_OPT_RESIDENT_FORCE_TIMEOUT || k == EULER_OPT_MG_SPLIT_ACTIVE || k == EULER_OPT_PROFILE_STRIDE) continue;      /* a test hook that counts down, a read-only result, a measurement's stride */
+    if (f->opt[k] != h->opt[k]) { if (why && cap) snprintf(why, cap, "option %d: the session has %lld, the handle %lld", k, (long long)f->opt[k], (long long)h->opt[k]); return 1; }
+  }
+  return 0;
+}

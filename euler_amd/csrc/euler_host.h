@@ -154,6 +154,55 @@ typedef struct eu_mg_split_plan {
  * 1 ... levels - 1, nranks outside 2 ... MG_SPLIT_MAXR, such a partition, or counts beyond int32.  seg_cap: table entries to use (<= 4 MG_MAXLEV, which callers pass) */
 int      eu_mg_split_plan_fill(eu_mg_split_plan* P, int32_t levels, const int32_t* nx, const int32_t* ny, int32_t Lg, int32_t nranks, int32_t rank,
                                const int32_t* part_lo, const int32_t* part_hi, int32_t seg_cap);
+/* session files (snapshot.hip, include/euler.h "session files", docs/session.md): a version-4 snapshot in memory - composed, and parsed and checked whole, without a
+ * device.  The SETT chunk's payload: every setting that can change a bit of a run and that the file does not otherwise fix; opt[k] is the value of EULER_OPT_* key k
+ * (opt[0] and the keys beyond nopts - 1 are 0) */
+#define EU_SESSION_OPTS 32
+typedef struct eu_session_settings {      /* 320 bytes, no padding */
+  int32_t  max_iterations, dot_mode, precond, tile_records, sweep_mode, max_substeps, rainbow, pcg_precision, resident, pcg_poll_interval;
+  uint32_t viscosity_bits, frame_time_bits;      /* the floats' bit patterns */
+  double   tol;
+  int32_t  nopts, reserved;                      /* EULER_OPT__COUNT of the writer; 0 */
+  int64_t  opt[EU_SESSION_OPTS];
+} eu_session_settings;
+/* What a session holds beside the arrays of the core.  The byte pointers may be unaligned (a chunk begins wherever the markers end): read them with memcpy.  For the
+ * composer they point to the caller's arrays, for the parser into the buffer it was given. */
+typedef struct eu_session {
+  int32_t  X, Y, dye;                        /* dye: the six dye arrays are present (bit 0 of the header's reserved word) */
+  uint64_t n_markers, rng_state;
+  int32_t  source_exhausted;
+  uint64_t frames, total_substeps, total_pcg_iterations;
+  const unsigned char* solid;                /* the file's own solid grid, X * Y bytes (set by the parser; the composer does not read it) */
+  double   time;
+  euler_forcing forcing;  euler_force_box force_boxes[EULER_FORCE_BOXES_MAX];
+  int32_t  heat_on;
+  euler_heat heat;        euler_heat_box heat_boxes[EULER_HEAT_BOXES_MAX];
+  const unsigned char* heat_field;           /* X * Y floats where heat_on, else NULL */
+  uint64_t n_tracers;
+  const unsigned char* tracers;              /* n_tracers records of 32 bytes */
+  int32_t  n_bodies;
+  euler_body bodies[EULER_BODIES_MAX];
+  int32_t  body_ox[EULER_BODIES_MAX], body_oy[EULER_BODIES_MAX];
+  euler_reseed reseed;
+  euler_reseed_stats reseed_stats;
+  eu_session_settings settings;
+  /* the STAT chunk: what euler_stats reports beside the header's three counters and the marker state */
+  int32_t  last_substeps, last_pcg_iterations;
+  double   last_residual;
+  float    last_dt;
+  uint64_t marker_dt_events, marker_multi_events;
+} eu_session;
+uint64_t eu_fnv1a64(uint64_t h, const void* p, size_t n);   /* h = EU_FNV_BASIS to begin */
+#define EU_FNV_BASIS 14695981039346656037ull
+size_t   eu_session_core_bytes(int32_t X, int32_t Y, int32_t dye, uint64_t n_markers);   /* header, arrays and markers: where the chunks begin */
+size_t   eu_session_chunk_bytes(const eu_session* s);          /* all chunks, END included, without the trailer */
+size_t   eu_session_put_chunks(const eu_session* s, unsigned char* out);   /* writes them; returns eu_session_chunk_bytes */
+/* The whole file in buf: header, sizes, checksum, every chunk in its order and every record through its host check; reads no byte beyond n, writes only *out and why.
+ * X, Y, dye, max_markers: the loading handle's.  EULER_EIO: truncated or the checksum fails; EULER_EINVAL: everything else. */
+int      eu_session_parse(const void* buf, size_t n, int32_t X, int32_t Y, int32_t dye, uint64_t max_markers, eu_session* out, char* why, size_t cap);
+/* 0: the settings agree; 1: why names the first field that differs, with both values.  Not compared: the options that cannot change a bit of a whole-grid run and
+ * are not settings of it (docs/session.md) */
+int      eu_session_settings_diff(const eu_session_settings* file, const eu_session_settings* handle, char* why, size_t cap);
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,9 @@
 // Little-endian; layouts documented in include/euler.h.
 //   * a whole-grid handle writes ONE file (version 1, version 2 with the dye);
 //   * a job of row slabs writes one PART file per rank (version 3: the rank's own rows, its markers WITH their keys = their
-//     positions in the reference's array) and, rank 0, a small manifest under the given name listing the ranks' band ranges.
+//     positions in the reference's array) and, rank 0, a small manifest under the given name listing the ranks' band ranges;
+//   * euler_save_session (at the end of this file) writes version 4: the layout of version 1 / 2 followed by tagged chunks for the state this build added to the
+//     reference's.  The loader below takes the core of such a file and passes its chunks through the checksum unread.
 // Loading is independent of how the state was written: any handle - whole grid, or a slab of ANY partition - takes its rows
 // (ghost rows included: the files of a job hold every row) and the markers inside its rows from whichever files hold them.  So a
 // 3-rank job can be resumed on 2 ranks, or on one GPU, or with another (fluid-balanced) partition: the re-partitioning of a run
@@ -52,7 +54,8 @@ static std::string part_name(const char* path, int rank, int nranks) {
 // agree (one all-reduce of the status) that every part file was written and closed before any of them is renamed, and again that every rename
 // succeeded before rank 0 puts the manifest in place - a manifest never names a part that is missing or belongs to an older state, and a rank
 // that fails makes the call fail on every rank.
-static int write_part_file(euler_sim* S, const euler_stats& st, const std::string& tmp, bool slab, int nranks, int rank) {
+// chunks (a session file, version 4: whole-grid handles only): the bytes that follow the markers, under the same checksum
+static int write_part_file(euler_sim* S, const euler_stats& st, const std::string& tmp, bool slab, int nranks, int rank, const std::vector<unsigned char>* chunks = nullptr) {
   FILE* f = fopen(tmp.c_str(), "wb");
   if (!f) { eu_set_error("cannot open %s for writing", tmp.c_str()); return EULER_EIO; }
   int rc = EULER_OK;
@@ -60,6 +63,7 @@ static int write_part_file(euler_sim* S, const euler_stats& st, const std::strin
   memset(&h, 0, sizeof h);
   memcpy(h.magic, "EULERSNP", 8);
   h.version = slab ? 3 : (S->dye[0] ? 2 : 1); h.reserved = (slab && S->dye[0]) ? 1 : 0;      // (version 3 with the dye: reserved = 1)
+  if (chunks) { h.version = 4; h.reserved = S->dye[0] ? 1 : 0; }
   h.X = S->X; h.Y = S->Y; h.n_markers = st.n_markers; h.rng_state = st.rng_state;
   h.source_exhausted = st.source_exhausted; h.frames = st.frames; h.total_substeps = st.total_substeps;
   h.total_pcg_iterations = st.total_pcg_iterations;
@@ -89,6 +93,10 @@ static int write_part_file(euler_sim* S, const euler_stats& st, const std::strin
   if (S->dye[0]) for (int fd : SNAP_DYE) put(fd, Cr * 4);
   put(EULER_F_MARKERS, (size_t)n_loc * 8);
   if (slab) put(EULER_F_MARKER_KEYS, (size_t)n_loc * 4);
+  if (chunks && ok && !chunks->empty()) {
+    sum = snap_fnv(sum, chunks->data(), chunks->size());
+    ok = fwrite(chunks->data(), 1, chunks->size(), f) == chunks->size();
+  }
   ok = ok && fwrite(&sum, 8, 1, f) == 1;
   ok = (fclose(f) == 0) && ok;
   if (rc) return rc;
@@ -140,6 +148,8 @@ extern "C" int euler_save_state(euler_sim* S, const char* path) {
 namespace {
 struct Part {
   std::string file;
+  const void* mem = nullptr;        // a session already in memory (euler_load_session): read from there, not from `file`
+  size_t mem_n = 0;
   SnapHeader h;
   int row_lo, row_hi;               // rows the FILE holds
   int keep_lo, keep_hi;             // rows of it kept in memory: those the handle's window needs
@@ -149,7 +159,7 @@ struct Part {
   std::vector<unsigned char> sec[16];
   std::vector<float> mk;
   std::vector<unsigned int> keys;
-  bool has_dye() const { return h.version == 2 || (h.version == 3 && h.reserved == 1); }
+  bool has_dye() const { return h.version == 2 || ((h.version == 3 || h.version == 4) && (h.reserved & 1u) == 1); }
   const unsigned char* rows(int k, int y) const { return sec[k].data() + (size_t)(y - keep_lo) * h.X * elem(k); }      // row y (kept) of section k
   static size_t elem(int k) { return k <= 3 ? 4 : (k <= 8 ? 1 : (k == 9 ? 8 : 4)); }      // 0..3 f32 fields, 4..8 u8 grids, 9 precon, 10..15 dye
 };
@@ -158,14 +168,14 @@ struct Part {
 // inside [mark_lo, mark_hi) - so a whole-grid snapshot of 16384^2 (7.8 GB + 2.7 GB of markers) loaded into eight row slabs costs each rank its own eighth,
 // not the whole file.
 int read_part(Part& p, int need_lo, int need_hi, int mark_lo, int mark_hi) {
-  FILE* f = fopen(p.file.c_str(), "rb");
+  FILE* f = p.mem ? fmemopen(const_cast<void*>(p.mem), p.mem_n, "rb") : fopen(p.file.c_str(), "rb");
   if (!f) { eu_set_error("cannot open %s", p.file.c_str()); return EULER_EIO; }
   struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
   fseek(f, 0, SEEK_END);
   const long n = ftell(f);
   fseek(f, 0, SEEK_SET);
-  if (n < (long)(sizeof(SnapHeader) + 8) || fread(&p.h, sizeof p.h, 1, f) != 1 || memcmp(p.h.magic, "EULERSNP", 8) != 0 || p.h.version < 1 || p.h.version > 3) {
-    eu_set_error("%s is not an euler state snapshot (version 1, 2 or 3)", p.file.c_str()); return EULER_EINVAL;
+  if (n < (long)(sizeof(SnapHeader) + 8) || fread(&p.h, sizeof p.h, 1, f) != 1 || memcmp(p.h.magic, "EULERSNP", 8) != 0 || p.h.version < 1 || p.h.version > 4) {
+    eu_set_error("%s is not an euler state snapshot (version 1, 2, 3 or 4)", p.file.c_str()); return EULER_EINVAL;
   }
   uint64_t sum = snap_fnv(14695981039346656037ull, &p.h, sizeof p.h);
   size_t body = sizeof(SnapHeader);
@@ -180,7 +190,9 @@ int read_part(Part& p, int need_lo, int need_hi, int mark_lo, int mark_hi) {
   if (p.h.X <= 0 || p.row_hi < p.row_lo) { eu_set_error("%s: bad header", p.file.c_str()); return EULER_EINVAL; }
   const size_t X = (size_t)p.h.X, C = (size_t)(p.row_hi - p.row_lo) * X;
   const size_t want = body + C * 29 + (p.has_dye() ? C * 24 : 0) + (size_t)p.n_loc * (p.keyed ? 12 : 8) + 8;
-  if ((size_t)n != want) { eu_set_error("%s is truncated or corrupt (size)", p.file.c_str()); return EULER_EIO; }
+  // (version 4, a session file: the chunks stand between the markers and the checksum; this loader passes them through the checksum and reads none)
+  if (p.h.version == 4 ? (size_t)n < want : (size_t)n != want) { eu_set_error("%s is truncated or corrupt (size)", p.file.c_str()); return EULER_EIO; }
+  const size_t chunk_bytes = (size_t)n - want;
   p.keep_lo = need_lo > p.row_lo ? need_lo : p.row_lo; p.keep_hi = need_hi < p.row_hi ? need_hi : p.row_hi;
   if (p.keep_hi < p.keep_lo) p.keep_hi = p.keep_lo;
   std::vector<unsigned char> chunk;
@@ -245,6 +257,7 @@ int read_part(Part& p, int need_lo, int need_hi, int mark_lo, int mark_hi) {
     try { p.keys.resize(kept.size()); } catch (...) { return EULER_ENOMEM; }
     for (size_t i = 0; i < kept.size(); ++i) p.keys[i] = (unsigned int)kept[i];
   }
+  if (chunk_bytes && !stream(chunk_bytes, [](size_t, const unsigned char*, size_t) {})) { eu_set_error("%s: short read", p.file.c_str()); return EULER_EIO; }
   uint64_t stored = 0;
   if (fread(&stored, 8, 1, f) != 1 || stored != sum) { eu_set_error("%s is truncated or corrupt (checksum)", p.file.c_str()); return EULER_EIO; }
   return EULER_OK;
@@ -252,10 +265,14 @@ int read_part(Part& p, int need_lo, int need_hi, int mark_lo, int mark_hi) {
 }  // namespace
 
 // everything of a load that is this rank's own business (files, host buffers, uploads): NO collective in here, so a failure leaves no other rank waiting
-static int load_state_local(euler_sim* S, const char* path, SnapHeader* h_out) {
+static int load_state_local(euler_sim* S, const char* path, SnapHeader* h_out, const void* mem = nullptr, size_t mem_n = 0) {
   // what is there: one whole-grid file, or a manifest naming the part files of a job
   std::vector<Part> parts;
-  {
+  if (mem) {
+    Part p;
+    p.file = path; p.mem = mem; p.mem_n = mem_n; p.row_lo = 0; p.row_hi = S->Y;
+    parts.push_back(p);
+  } else {
     FILE* f = fopen(path, "rb");
     if (!f) { eu_set_error("cannot open %s", path); return EULER_EIO; }
     char magic[8] = {0};
@@ -384,6 +401,8 @@ static int load_state_local(euler_sim* S, const char* path, SnapHeader* h_out) {
   return EULER_OK;
 }
 
+static int load_state_finish(euler_sim* S, const SnapHeader& h0);
+
 // Collective on a row-slab handle: every rank loads its rows and markers on its own, then the ranks AGREE on the outcome (one all-reduce of the
 // status) before the first collective of the restore - a missing or corrupt part file, a row no file holds, more markers than a slab's capacity or
 // an allocation failure on ONE rank fails the call on EVERY rank (the handle is then unloaded everywhere) instead of leaving the others waiting.
@@ -411,6 +430,12 @@ extern "C" int euler_load_state(euler_sim* S, const char* path) {
     if ((rc = eu_slab_after_restore(S))) return rc;      // collective: the source cells of all ranks
     if ((rc = eu_sync_marker_state(S))) return rc;
   } else if (rc) return rc;
+  return load_state_finish(S, h0);
+}
+
+// behind the arrays and markers of a load: the validity flags, the counters, and the extras by the rules of a snapshot
+static int load_state_finish(euler_sim* S, const SnapHeader& h0) {
+  int rc;
   eu_vd_solver_arrays_foreign(&S->vd);      // the solver arrays may hold another state's pressure and masks: the next assembly writes them whole
   eu_vd_replaced(&S->vd);      // (the solid / sink grids were replaced)
   memset(&S->stats, 0, sizeof S->stats);
@@ -421,6 +446,153 @@ extern "C" int euler_load_state(euler_sim* S, const char* path) {
   if ((rc = eu_heat_reset(S))) return rc;      // (nor is the temperature: the record stays as set, the field starts from ambient, docs/heat.md)
   S->loaded = 1;
   return EULER_OK;
+}
+
+// ------------------------------------------------------------------------------------------ session files (version 4; include/euler.h, docs/session.md)
+// The core of a snapshot followed by tagged chunks for everything else a whole-grid handle holds.  The chunks are composed, parsed and checked in plain C
+// (euler_host.c: eu_session_put_chunks, eu_session_parse); this file gathers the handle's state for the composer and puts a parsed session into the handle.
+// No kernel of its own: the core goes through the loader above, the heat field through euler_heat_set_field (its mask pass writes `ambient` over the dry
+// cells: k_heat_mask serves where k_heat_dry would), everything else is host state or a plain copy.
+static void session_settings(const euler_sim* S, eu_session_settings* t) {
+  memset(t, 0, sizeof *t);
+  t->max_iterations = S->cfg.max_iterations; t->dot_mode = S->cfg.dot_mode; t->precond = S->cfg.precond; t->tile_records = S->tile_w;
+  t->sweep_mode = S->cfg.sweep_mode; t->max_substeps = S->cfg.max_substeps; t->rainbow = S->dye[0] ? 1 : 0; t->pcg_precision = S->cfg.pcg_precision;
+  t->resident = S->cfg.resident; t->pcg_poll_interval = S->cfg.pcg_poll_interval;
+  memcpy(&t->viscosity_bits, &S->cfg.viscosity, 4); memcpy(&t->frame_time_bits, &S->cfg.frame_time, 4);
+  t->tol = S->cfg.tol;
+  t->nopts = EULER_OPT__COUNT;
+  for (int k = 1; k < EULER_OPT__COUNT; ++k) t->opt[k] = (int64_t)S->opt[k];
+}
+static_assert(EULER_OPT__COUNT <= EU_SESSION_OPTS, "the SETT chunk has room for every option key");
+static_assert(sizeof(eu_session_settings) == 320 && offsetof(eu_session_settings, viscosity_bits) == 40 && offsetof(eu_session_settings, tol) == 48 &&
+              offsetof(eu_session_settings, nopts) == 56 && offsetof(eu_session_settings, opt) == 64, "eu_session_settings is 320 bytes without padding");
+
+static int session_enter(euler_sim* S, const char* path, const char* who) {
+  if (!S || !path) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
+  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (a slab holds none of what a session adds to a snapshot; euler_save_state / euler_load_state serve it)", who); return EULER_ESTATE; }
+  return EULER_OK;
+}
+
+extern "C" int euler_save_session(euler_sim* S, const char* path) {
+  const char* who = "euler_save_session";
+  int rc = session_enter(S, path, who);
+  if (rc) return rc;
+  if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
+  euler_stats st;
+  if ((rc = euler_get_stats(S, &st))) return rc;      // (syncs the marker state: the reseed totals below are current)
+  eu_session* s = (eu_session*)calloc(1, sizeof(eu_session));
+  if (!s) return EULER_ENOMEM;
+  struct Free { eu_session* s; ~Free() { free(s); } } guard{s};
+  s->X = S->X; s->Y = S->Y; s->dye = S->dye[0] ? 1 : 0;
+  s->time = S->time;
+  s->forcing = S->forcing;
+  if (S->forcing.nboxes > 0) memcpy(s->force_boxes, S->force_boxes, (size_t)S->forcing.nboxes * sizeof(euler_force_box));
+  std::vector<float> field;
+  std::vector<euler_tracer> tracers;
+  try { if (S->heat_on) field.resize(S->C); tracers.resize(S->n_tracers); } catch (...) { return EULER_ENOMEM; }
+  s->heat_on = S->heat_on ? 1 : 0;
+  if (S->heat_on) {
+    s->heat = S->heat;
+    if (S->heat.nboxes > 0) memcpy(s->heat_boxes, S->heat_boxes, (size_t)S->heat.nboxes * sizeof(euler_heat_box));
+    if ((rc = euler_heat_get_field(S, field.data(), S->C * sizeof(float)))) return rc;
+    s->heat_field = (const unsigned char*)field.data();
+  }
+  s->n_tracers = S->n_tracers;
+  if (S->n_tracers && (rc = euler_tracers_get(S, 0, S->n_tracers, tracers.data(), S->n_tracers * sizeof(euler_tracer)))) return rc;
+  s->tracers = (const unsigned char*)tracers.data();
+  s->n_bodies = S->n_bodies;
+  for (int k = 0; k < S->n_bodies; ++k) { s->bodies[k] = S->bodies[k]; s->body_ox[k] = S->body_ox[k]; s->body_oy[k] = S->body_oy[k]; }
+  if ((rc = euler_get_reseed(S, &s->reseed, &s->reseed_stats))) return rc;
+  session_settings(S, &s->settings);
+  s->last_substeps = st.last_substeps; s->last_pcg_iterations = st.last_pcg_iterations; s->last_residual = st.last_residual; s->last_dt = st.last_dt;
+  s->marker_dt_events = st.marker_dt_events; s->marker_multi_events = st.marker_multi_events;
+  std::vector<unsigned char> chunks;
+  try { chunks.resize(eu_session_chunk_bytes(s)); } catch (...) { return EULER_ENOMEM; }
+  (void)eu_session_put_chunks(s, chunks.data());
+  const std::string tmp = std::string(path) + ".tmp";
+  if ((rc = write_part_file(S, st, tmp, false, 1, 0, &chunks))) { remove(tmp.c_str()); return rc; }
+  if (rename(tmp.c_str(), path) != 0) { eu_set_error("cannot rename %s to %s", tmp.c_str(), path); return EULER_EIO; }
+  return EULER_OK;
+}
+
+extern "C" int euler_load_session(euler_sim* S, const char* path, uint32_t flags) {
+  const char* who = "euler_load_session";
+  int rc = session_enter(S, path, who);
+  if (rc) return rc;
+  if (flags & ~(uint32_t)EULER_SESSION_IGNORE_SETTINGS) { eu_set_error("%s: unknown flag bits %#x", who, flags); return EULER_EINVAL; }
+  // ---- the whole file, read and checked before the handle changes
+  std::vector<unsigned char> buf;
+  {
+    FILE* f = fopen(path, "rb");
+    if (!f) { eu_set_error("cannot open %s", path); return EULER_EIO; }
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+    fseek(f, 0, SEEK_END);
+    const long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (n < 0) { eu_set_error("cannot read %s", path); return EULER_EIO; }
+    try { buf.resize((size_t)n); } catch (...) { return EULER_ENOMEM; }
+    if (n > 0 && fread(buf.data(), 1, (size_t)n, f) != (size_t)n) { eu_set_error("%s: short read", path); return EULER_EIO; }
+  }
+  eu_session* s = (eu_session*)calloc(1, sizeof(eu_session));
+  if (!s) return EULER_ENOMEM;
+  struct Free { eu_session* s; ~Free() { free(s); } } guard{s};
+  char why[400];
+  if ((rc = eu_session_parse(buf.data(), buf.size(), S->X, S->Y, S->dye[0] ? 1 : 0, S->max_markers, s, why, sizeof why))) { eu_set_error("%s(%s): %s", who, path, why); return rc; }
+  if (!(flags & EULER_SESSION_IGNORE_SETTINGS)) {
+    eu_session_settings mine;
+    session_settings(S, &mine);
+    if (eu_session_settings_diff(&s->settings, &mine, why, sizeof why)) {
+      eu_set_error("%s(%s): the settings differ - %s (create the handle with the session's settings, or pass EULER_SESSION_IGNORE_SETTINGS)", who, path, why);
+      return EULER_ESTATE;
+    }
+  }
+  // ---- the device memory the extras need, while a failure still leaves the handle as it was (grow-only buffers: their contents stay)
+  const bool reseed_on = s->reseed.thin_above != 0 || s->reseed.fill_holes != 0;
+  if (s->heat_on && (rc = eu_devbuf_reserve(S, who, "the temperature and its scratch copy", &S->heat_buf, 2 * S->C * sizeof(float)))) return rc;
+  if (s->n_tracers > S->tracer_buf.bytes / sizeof(euler_tracer)) {      // (the store's own policy: doubling from 256 records; nothing of the old records is kept)
+    size_t cap = 256;
+    while (cap < s->n_tracers) cap *= 2;
+    if ((rc = eu_devbuf_reserve(S, who, "the tracers", &S->tracer_buf, cap * sizeof(euler_tracer)))) return rc;
+  }
+  if (reseed_on) {      // (what euler_set_reseed below would reserve)
+    const size_t max_cells = (size_t)eu_reseed_limit(s->reseed.max_cells), max_fill = (size_t)eu_reseed_limit(s->reseed.max_fill);
+    if ((rc = eu_devbuf_reserve(S, who, "the hole mask", &S->rs_mask_buf, ((S->C + 63) / 64 + 1) * sizeof(unsigned long long)))) return rc;
+    if ((rc = eu_devbuf_reserve(S, who, "the cell list", &S->rs_cell_buf, max_cells * sizeof(unsigned int)))) return rc;
+    if ((rc = eu_devbuf_reserve(S, who, "the sub-cell slots", &S->rs_slot_buf, 16 * max_cells * sizeof(unsigned int)))) return rc;
+    if ((rc = eu_devbuf_reserve(S, who, "the draws", &S->rs_draw_buf, 2 * max_fill * sizeof(float)))) return rc;
+  }
+  // ---- the core, as euler_load_state restores it (from the bytes just checked, not from the file again)
+  SnapHeader h0;
+  memset(&h0, 0, sizeof h0);
+  if ((rc = load_state_local(S, path, &h0, buf.data(), buf.size()))) return rc;
+  S->heat_on = 0;      // (off unless the session says otherwise; load_state_finish then has no field to reset)
+  if ((rc = load_state_finish(S, h0))) return rc;
+  // ---- the extras, without the side effects of switching them on
+  S->time = s->time;
+  if ((rc = euler_set_forcing(S, &s->forcing, s->force_boxes))) return rc;      // (the record, the box table and what follows from the values: no grid is touched)
+  if (s->heat_on) {
+    // from off: any ambient passes, the arrays are there, the field is set to the session's ambient and then replaced; euler_heat_set_field writes ambient over
+    // the cells without markers - for an honest file a no-op by the field's invariant
+    if ((rc = euler_set_heat(S, &s->heat, s->heat_boxes))) return rc;
+    std::vector<float> field;
+    try { field.resize(S->C); } catch (...) { return EULER_ENOMEM; }
+    memcpy(field.data(), s->heat_field, S->C * sizeof(float));
+    if ((rc = euler_heat_set_field(S, field.data(), S->C * sizeof(float)))) return rc;
+  }
+  if (s->n_tracers) {      // the records byte for byte
+    HIPCHK(hipMemcpyAsync(S->tracer_buf.p, s->tracers, (size_t)s->n_tracers * sizeof(euler_tracer), hipMemcpyHostToDevice, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+  }
+  S->n_tracers = (size_t)s->n_tracers;
+  for (int k = 0; k < s->n_bodies; ++k) { S->bodies[k] = s->bodies[k]; S->body_ox[k] = s->body_ox[k]; S->body_oy[k] = s->body_oy[k]; }
+  S->n_bodies = s->n_bodies;      // (the masks already hold the rectangles: no SOLID edit, no marker deleted)
+  if ((rc = euler_set_reseed(S, &s->reseed))) return rc;      // (zeroes the totals ...)
+  const unsigned long long totals[4] = {s->reseed_stats.removed, s->reseed_stats.added, s->reseed_stats.cells_thinned, s->reseed_stats.deferred};
+  HIPCHK(hipMemcpyAsync(&S->ms->rs_removed, totals, sizeof totals, hipMemcpyHostToDevice, S->stream));      // (... which are the session's)
+  const unsigned long long events[2] = {s->marker_dt_events, s->marker_multi_events};
+  HIPCHK(hipMemcpyAsync(&S->ms->total_dt_events, events, sizeof events, hipMemcpyHostToDevice, S->stream));
+  S->stats.last_substeps = s->last_substeps; S->stats.last_pcg_iterations = s->last_pcg_iterations; S->stats.last_residual = s->last_residual; S->stats.last_dt = s->last_dt;
+  return eu_sync_marker_state(S);
 }
 
 // ------------------------------------------------------------------------------------------ render on a row-slab handle

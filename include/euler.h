@@ -286,6 +286,40 @@ int euler_get_stats(euler_sim* sim, euler_stats* out);
  * collective (communicator installed first, like euler_load_scenario_*). */
 int euler_save_state(euler_sim* sim, const char* path);
 int euler_load_state(euler_sim* sim, const char* path);
+/* ---- session files: checkpoints that carry the clock, the forcing, heat, tracers, bodies and the density control (docs/session.md) ----
+ * A snapshot above is the reference's state.  A SESSION is everything a whole-grid handle holds that the next substep depends on: loading one puts the handle into
+ * the saving handle's state, whatever it held before, and the continued run equals the uninterrupted one bit for bit - fields, markers in order, RNG, clock,
+ * temperature, tracer records, body origins, reseed totals, frame counters.  File layout, little-endian: the 72-byte header above with version = 4, bit 0 of the
+ * word behind Y set where the six dye arrays are present; the arrays of version 1 (with the bit: of version 2) in their order; the markers; then CHUNKS, each
+ *   char tag[4]; u32 chunk_version = 1; u64 payload_bytes; the payload, padded with zeros to a multiple of 8 bytes
+ * - all of them, always, in this order, with an "off" record where a feature is off:
+ *   "TIME"  f64 the clock (euler_get_time)
+ *   "FORC"  euler_forcing; nboxes x euler_force_box.  A handle that never called euler_set_forcing holds the default record (euler_forcing_default): what a substep
+ *           launches is a function of the record's VALUES alone (the forced kernels run iff the uniform part differs from (0, -10) or shakes, the box pass iff
+ *           nboxes > 0), so "never set" and "set to the default" are one state and a restored handle launches what the saver launched
+ *   "HEAT"  i32 on, i32 0; euler_heat; nboxes x euler_heat_box; with on: f32[Y][X] the field as euler_heat_get_field returns it (off: the default record, no boxes)
+ *   "TRAC"  u64 n; n x euler_tracer, verbatim, retired ones included
+ *   "BODY"  i32 n, i32 0; n x euler_body; n x {i32 ox, oy}, the remembered origins
+ *   "RSED"  euler_reseed; euler_reseed_stats
+ *   "SETT"  the settings that can change a bit of the run (the table in docs/session.md; 320 bytes)
+ *   "STAT"  i32 last_substeps, last_pcg_iterations; f64 last_residual; f32 last_dt; u32 0; u64 marker_dt_events, marker_multi_events: what euler_get_stats reports
+ *           beside the header's counters and the marker state, so that the first line a resumed run logs is the one the saving run logged
+ *   "END\0" empty
+ * and the u64 FNV-1a-64 of all preceding bytes.  Written under "<path>.tmp" and renamed, like the other files.
+ * euler_load_session reads and checks the WHOLE file before the handle changes - the checksum, X, Y, the dye bit, the marker capacity, the chunks' order and their
+ * sizes against the counts inside them (an unknown tag or chunk version is named), every record through the check of its euler_set_* call, the heat field's values,
+ * the tracers (a finite position, or flagged LOST; reserved 0), every cell of every body's rectangle at its remembered origin solid in the file's own solid grid,
+ * and SETT against the handle's own settings: the settings are CHECKED, not applied.  A refused load leaves the handle exactly as it was.  Then the core is restored
+ * as euler_load_state restores it, and the rest without the side effects of switching it on: no SOLID edit and no marker is deleted for a body, the reseed totals
+ * are the file's, the file's ambient replaces the handle's, cells without markers hold it (as behind euler_heat_set_field), and a feature that is off in the file is
+ * off afterwards.  Not carried: the pressure (each solve starts from 0; no snapshot ever held it).
+ * Refusals: a null sim or path, a flag bit other than EULER_SESSION_IGNORE_SETTINGS (EULER_EINVAL); a row-slab handle (EULER_ESTATE, "slab"); euler_save_session
+ * with nothing loaded (EULER_ESTATE); a file that cannot be opened, is truncated or fails its checksum (EULER_EIO); a settings mismatch (EULER_ESTATE, naming the first
+ * field that differs with both values; EULER_SESSION_IGNORE_SETTINGS skips this comparison and nothing else); everything else about the file EULER_EINVAL.
+ * euler_load_state accepts a version-4 file too: it verifies the checksum, takes the core and ignores the chunks - on a row-slab handle of any partition as well. */
+enum { EULER_SESSION_IGNORE_SETTINGS = 1 };
+int euler_save_session(euler_sim* sim, const char* path);
+int euler_load_session(euler_sim* sim, const char* path, uint32_t flags);
 size_t euler_field_bytes(const euler_sim* sim, int32_t field);   /* current size in bytes */
 
 /* ---- render = draw_rows (main.c:914-951) ------------------------------------------------- */
@@ -554,7 +588,7 @@ int euler_edit_box(euler_sim* sim, int32_t op, int32_t x0, int32_t y0, int32_t x
 /* ---- forcing: gravity vector, shaken tank, force boxes (docs/forcing.md) --------------------------- */
 /* Tilt or shake the tank, drive a current with a pump, run in reduced or zero gravity.  The handle keeps a double clock `time` (0 after a load, advanced
  * by time += (double)dt behind every substep of euler_step / euler_substep, in substep order; euler_stage does not advance it; it is not part of a
- * snapshot: euler_load_state leaves it at 0 and the forcing as set, the caller restores both).  The uniform acceleration of a substep is
+ * snapshot: euler_load_state leaves it at 0 and the forcing as set, the caller restores both; a session file, euler_save_session, carries both).  The uniform acceleration of a substep is
  * euler_forcing_at(f, time at the start of that substep): in double, a[0] = (float)(gx + shake_x sin(2 pi shake_hz t + shake_phase)), a[1] likewise from
  * gy, shake_y.  Per live face (live as for the FLUX gauge above), float32 without contraction, last in the velocity advection (with MacCormack: behind the
  * clamp): a live v face gets out += a[1] * dt, always; a live u face gets out += a[0] * dt ONLY when a[0] != 0.f (x + 0.f is not x for x = -0.f).  Then,
@@ -606,7 +640,7 @@ int euler_set_time(euler_sim* sim, double t);   /* EULER_EINVAL: a non-finite t 
  * either WHERE THE TRANSPORT REPRODUCES THE CONSTANT: fl(fl(fl(1 - f) a) + fl(f a)) is a again for a = 0 and for a power of two, not for every float - with
  * ambient = 20, say, a transported cell can come out one ulp off and the buoyancy acts on that ulp (docs/heat.md).  Choose such an ambient where this matters.  A handle that never calls
  * euler_set_heat launches what it always launched.  Heat is no part of a snapshot: a scenario load and euler_load_state keep the record and reset the field
- * to `ambient`. */
+ * to `ambient`.  A session file (euler_save_session) carries the record, the boxes and the field. */
 #define EULER_HEAT_BOXES_MAX 64
 enum { EULER_HEAT_FIX = 0, EULER_HEAT_RATE = 1 };
 typedef struct euler_heat_box { int32_t x0, y0, x1, y1; float value; int32_t kind; } euler_heat_box;   /* 24 bytes; inclusive, inside [1, X-2] x [1, Y-2] */
@@ -671,7 +705,7 @@ int euler_heat_paint(const euler_heat_px* heat, euler_overview_px* px, int32_t W
  *   6. WET becomes wet; WAS_DRY is set for good if !wet; x, y = x', y'.
  * A tracer in air does not move (the masked velocity there is 0).  Scenario loads, the half-tank loaders and euler_load_state clear the tracers;
  * euler_set_field, euler_set_markers, euler_edit_box, euler_set_forcing and euler_set_time leave them alone (a wall raised over a tracer retires it on
- * its next substep).  Tracers are not part of a snapshot.  Whole-grid handles only. */
+ * its next substep).  Tracers are not part of a snapshot; a session file (euler_save_session) carries their records.  Whole-grid handles only. */
 #define EULER_TRACERS_MAX (1u << 22)
 enum { EULER_TRACER_WET = 1, EULER_TRACER_RETIRED = 2, EULER_TRACER_IN_SOLID = 4, EULER_TRACER_IN_SINK = 8,
        EULER_TRACER_LOST = 16, EULER_TRACER_WAS_DRY = 32 };
@@ -730,7 +764,8 @@ int euler_tracer_paint(const uint32_t* counts, euler_overview_px* px, int32_t W,
  * count != 0 && !solid and wx != 0.f; the v faces of the lower and upper edge take vtmp = wy likewise.  The same faces are set back to 0.f behind the stage.  The
  * right-hand side picks the velocity up (every fluid cell reads its four faces, solid ones too); the velocity update leaves u = v = 0 on the body's faces.  A body
  * with wx == wy == 0 is bit for bit a wall made by euler_edit_box.
- * Bodies are not part of a snapshot: a scenario load and euler_load_state drop them (n = 0; their cells are whatever the loaded masks say).  Whole-grid handles only. */
+ * Bodies are not part of a snapshot: a scenario load and euler_load_state drop them (n = 0; their cells are whatever the loaded masks say); a session file (euler_save_session) carries the list and the
+ * remembered origins.  Whole-grid handles only. */
 #define EULER_BODIES_MAX 16
 typedef struct euler_body {          /* 64 bytes, no padding */
   double  x, y;                      /* lower-left corner at t = 0, in cells, continuous */
@@ -772,7 +807,8 @@ int euler_get_bodies(euler_sim* sim, euler_body* bodies, int32_t cap, euler_body
  *        update_fluid_sources, main.c:288), and its count becomes 1; appending stops when the array holds max_markers - 1 markers (the holes left over add to
  *        `deferred`; the source stage's latch is not written);
  *     4. u, v, the dye and the temperature are untouched: the cell was water one refresh ago, its samples stand, and no extrapolation fires (prev_count != 0).
- * Tracers and dye are not pushed.  The settings survive a scenario load and euler_load_state like the options; they are not part of a snapshot. */
+ * Tracers and dye are not pushed.  The settings survive a scenario load and euler_load_state like the options; they are not part of a snapshot.
+ * A session file (euler_save_session) carries the record and the totals. */
 typedef struct euler_reseed {      /* 32 bytes, no padding */
   int32_t thin_above;   /* 0: no thinning; else 4 ... 254: a cell whose count byte exceeds it is thinned */
   int32_t fill_holes;   /* 0 / 1 */
