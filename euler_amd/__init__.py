@@ -70,6 +70,11 @@ BODY_STATE_DTYPE = np.dtype({"names": ["px", "py", "ox", "oy"], "formats": [np.f
 RESEED_DTYPE = np.dtype({"names": ["thin_above", "fill_holes", "max_cells", "max_fill", "reserved"], "formats": [np.int32] * 4 + [(np.int32, 4)],
                          "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
 RESEED_STATS_DTYPE = np.dtype({"names": ["removed", "added", "cells_thinned", "deferred"], "formats": [np.uint64] * 4, "offsets": [0, 8, 16, 24], "itemsize": 32})
+# the run-long envelopes (include/euler.h EULER_ENV_*, euler_envelope_px; docs/envelope.md): the channel bits and one pixel of euler_envelope_raster
+ENV_ARRIVAL, ENV_WET, ENV_SPEED, ENV_PRESSURE, ENV_ALL = 1, 2, 4, 8, 15
+ENV_NAMES = {ENV_ARRIVAL: "arrival", ENV_WET: "wet", ENV_SPEED: "speed", ENV_PRESSURE: "pressure"}
+ENVELOPE_PX_DTYPE = np.dtype({"names": ["cells", "touched", "arrival_min", "arrival_max", "wet_max", "speed2_max", "p_max", "reserved"],
+                              "formats": [np.uint32] * 8, "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
 # euler_tracer (include/euler.h): one passive tracer; EULER_TRACER_* flag bits; EULER_TRACER_RASTER_ALL of euler_tracer_raster
 TRACERS_MAX = 1 << 22
 TRACER_WET, TRACER_RETIRED, TRACER_IN_SOLID, TRACER_IN_SINK, TRACER_LOST, TRACER_WAS_DRY = 1, 2, 4, 8, 16, 32
@@ -156,6 +161,7 @@ EXPORTS = [
     "euler_heat_default", "euler_set_heat", "euler_get_heat", "euler_heat_get_field", "euler_heat_set_field", "euler_heat_fill", "euler_heat_raster", "euler_heat_paint",
     "euler_body_at", "euler_set_bodies", "euler_get_bodies",
     "euler_set_reseed", "euler_get_reseed",
+    "euler_set_envelope", "euler_get_envelope", "euler_envelope_reset", "euler_envelope_get_field", "euler_envelope_set_field", "euler_envelope_raster", "euler_envelope_rgb",
     "euler_tracers_add", "euler_tracers_count", "euler_tracers_get", "euler_tracers_clear", "euler_tracer_raster", "euler_tracer_paint",
 ]
 
@@ -263,6 +269,13 @@ def load_library():
         "euler_get_bodies": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
         "euler_set_reseed": (C.c_int, [vp, vp]),
         "euler_get_reseed": (C.c_int, [vp, vp, vp]),
+        "euler_set_envelope": (C.c_int, [vp, C.c_uint32]),
+        "euler_get_envelope": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(u64)]),
+        "euler_envelope_reset": (C.c_int, [vp]),
+        "euler_envelope_get_field": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "euler_envelope_set_field": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "euler_envelope_raster": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t]),
+        "euler_envelope_rgb": (C.c_int, [vp, i32, i32, i32, f64, vp, C.c_size_t]),
         "euler_tracers_add": (C.c_int, [vp, vp, C.c_size_t]),
         "euler_tracers_count": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
         "euler_tracers_get": (C.c_int, [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
@@ -495,6 +508,18 @@ def heat_paint(heat, px, ambient, scale):
     h, w = px.shape
     _check_host(load_library().euler_heat_paint(heat.ctypes.data, px.ctypes.data, w, h, float(ambient), float(scale)), "euler_heat_paint")
     return px
+
+
+def envelope_rgb(px, channel, scale):
+    """Envelope records (ENVELOPE_PX_DTYPE, shape (h, w)) -> uint8 (h, w, 3), row 0 = top (euler_envelope_rgb, host only): white to red with the channel's value
+    over `scale` - the arrival time, the wet time, the peak speed or the peak pressure of the pixel -, black where the water never was."""
+    px = np.ascontiguousarray(px, ENVELOPE_PX_DTYPE)
+    if px.ndim != 2:
+        raise ValueError("envelope_rgb: records of shape %r" % (px.shape,))
+    h, w = px.shape
+    rgb = np.empty((h, w, 3), np.uint8)
+    _check_host(load_library().euler_envelope_rgb(px.ctypes.data, w, h, int(channel), float(scale), rgb.ctypes.data, rgb.nbytes), "euler_envelope_rgb")
+    return rgb
 
 
 def tracer_lattice(box, k):
@@ -975,6 +1000,45 @@ class Simulation:
         px = np.zeros((max(int(h), 0), max(int(w), 0)), HEAT_PX_DTYPE)
         dst = px.ctypes.data if px.size else np.zeros(1, HEAT_PX_DTYPE).ctypes.data
         _check(self.L.euler_heat_raster(self.h, x0, y0, x1, y1, w, h, dst, px.nbytes))
+        return px
+
+    # --- run-long envelopes (docs/envelope.md)
+    def set_envelope(self, channels):
+        """Switch envelope channels on or off (euler_set_envelope): a set of ENV_* bits; a newly enabled channel starts from its initial words, one that stays
+        keeps its plane, 0 frees them all.  From then on every substep ends with the planes' update."""
+        _check(self.L.euler_set_envelope(self.h, int(channels)))
+        return self
+
+    def envelope(self):
+        """(channels, substeps) (euler_get_envelope): the ENV_* bits that are on and the substeps accumulated since they were switched on or last reset."""
+        ch, n = C.c_uint32(0), C.c_uint64(0)
+        _check(self.L.euler_get_envelope(self.h, C.byref(ch), C.byref(n)))
+        return int(ch.value), int(n.value)
+
+    def envelope_reset(self):
+        _check(self.L.euler_envelope_reset(self.h))
+        return self
+
+    def envelope_field(self, channel):
+        """One plane (euler_envelope_get_field): float32 of shape (Y, X); view it as uint32 for the arrival's "never" word 0xffffffff."""
+        out = np.empty((self.Y, self.X), np.float32)
+        _check(self.L.euler_envelope_get_field(self.h, int(channel), out.ctypes.data, out.nbytes))
+        return out
+
+    def set_envelope_field(self, channel, array):
+        """Restore a plane the caller kept (euler_envelope_set_field): float32 (or its uint32 view) of shape (Y, X)."""
+        a = np.asarray(array)
+        a = np.ascontiguousarray(a.view(np.float32) if a.dtype == np.uint32 else a, np.float32)
+        _check(self.L.euler_envelope_set_field(self.h, int(channel), a.ctypes.data, a.nbytes))
+        return self
+
+    def envelope_raster(self, box, w, h):
+        """The planes per pixel of overview(w, h, box) (euler_envelope_raster): an array of ENVELOPE_PX_DTYPE, shape (h, w), row 0 = top.  box = None: the
+        whole interior."""
+        x0, y0, x1, y1 = (1, 1, self.X - 2, self.Y - 2) if box is None else (int(t) for t in box)
+        px = np.zeros((max(int(h), 0), max(int(w), 0)), ENVELOPE_PX_DTYPE)
+        dst = px.ctypes.data if px.size else np.zeros(1, ENVELOPE_PX_DTYPE).ctypes.data
+        _check(self.L.euler_envelope_raster(self.h, x0, y0, x1, y1, int(w), int(h), dst, px.nbytes))
         return px
 
     # --- passive tracers (docs/tracers.md)

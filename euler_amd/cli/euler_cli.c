@@ -14,7 +14,7 @@
  *         [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]]
  *         [--paint vorticity:S|pressure:S|speed:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]]
  *         [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]...
- *         [--reseed THIN[:fill]]
+ *         [--reseed THIN[:fill]] [--envelope CH[,CH...] [--envelope-out PREFIX] [--envelope-ppm PREFIX:S_ARRIVAL,S_WET,S_SPEED,S_PRESSURE]]
  *         [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show]
  *         [--session-out FILE [--session-every N]] [--session-in FILE] <scenario>
  * --resume continues from a state snapshot (include/euler.h) instead of the scenario's initial state
@@ -63,6 +63,13 @@
  * (4 ... 254) is thinned to one marker per quarter-cell square, with :fill a single-cell hole in the water gets a marker back; THIN = 0 with :fill fills only.  The
  * totals - markers removed and added, cells thinned, cells deferred - go on one line to stderr at exit.  A malformed spec is a usage error, a value
  * euler_set_reseed refuses exits with status 1.  Without it every byte is as before.
+ * --envelope CH[,CH...] (CH one of arrival wet speed pressure all) switches the run-long envelopes on (euler_set_envelope, docs/envelope.md), set once behind the
+ * load and all the other set-up: per cell the time the water first arrived, the time it stayed, the peak speed squared and the peak pressure, gathered at the end of
+ * every substep.  --envelope-out PREFIX writes PREFIX.<channel>.f32 at exit, one file per enabled channel: the plane raw, little-endian, row-major, X * Y words;
+ * --envelope-ppm PREFIX:S_ARRIVAL,S_WET,S_SPEED,S_PRESSURE writes PREFIX.<channel>.ppm at exit: the whole interior at min(X - 2, 1024) x min(Y - 2, 1024) pixels,
+ * white to red over the channel's scale (seconds, seconds, cells per second, pressure), black where the water never was (euler_envelope_raster +
+ * euler_envelope_rgb).  Both are written under .tmp and renamed.  A malformed spec and --envelope-out or --envelope-ppm without --envelope are usage errors.
+ * Beside --session-in, --envelope is allowed: a session file does not carry the planes, so they start fresh.  Without the three every byte is as before.
  * --tracer (up to 1024 times) and --tracer-box (up to 64 times; the K x K lattice of every cell of the box, K = 1, 2 or 4) place passive tracers
  * (euler_tracers_add, docs/tracers.md), added once behind the load in command-line order.  --emit (up to 64 times) is a point that releases a tracer right before
  * the step that produces frame F whenever F % EVERY == 0 (default 1; F = 0 counts: before frame 0 is drawn) - a streakline; the emitters of a frame go in
@@ -98,12 +105,13 @@
 #include "cli_heat.h"
 #include "cli_tracers.h"
 #include "cli_session.h"
+#include "cli_envelope.h"
 #include "euler_host.h"      /* eu_tracer_lattice */
 
 static void usage(const char* argv0) {
   fprintf(stderr, "usage: %s [--rainbow] [--size XxY] [--upscale] [--frames N] [--window WxH] [--dump] [--no-pace] [--keys STRING] "
                   "[--resume FILE] [--checkpoint FILE] [--solver reference|tile|tile-fp32|two-level|multilevel] [--max-iterations N] [--advection rk1|rk2] [--maccormack] "
-                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--reseed THIN[:fill]] [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] [--session-out FILE [--session-every N]] [--session-in FILE] <scenario>\n", argv0);
+                  "[--fit] [--view X0,Y0,X1,Y1] [--edit F:solid|clear|sink|source|fill|drain:X0,Y0,X1,Y1]... [--ppm PREFIX [--ppm-size WxH] [--ppm-every N] [--ppm-mode coverage|dye|speed:SCALE]] [--stats FILE [--stats-every N]] [--paint vorticity:S|pressure:S|speed:S|heat:S] [--gauge level|pressure|force|flux:X0,Y0,X1,Y1]... [--gauges FILE [--gauges-every N]] [--gravity GX,GY] [--shake SX,SY:HZ[:PHASE_DEG]] [--force FX,FY:X0,Y0,X1,Y1]... [--body W,H:X,Y:VX,VY[:AX,AY:HZ[:DEG]]]... [--reseed THIN[:fill]] [--envelope arrival|wet|speed|pressure|all[,...] [--envelope-out PREFIX] [--envelope-ppm PREFIX:S_ARRIVAL,S_WET,S_SPEED,S_PRESSURE]] [--heat AMBIENT:BETA[:KAPPA] [--heat-source T] [--heat-box fix|rate:VALUE:X0,Y0,X1,Y1]... [--heat-init VALUE:X0,Y0,X1,Y1]...] [--tracer X,Y]... [--tracer-box X0,Y0,X1,Y1:K]... [--emit X,Y[:EVERY]]... [--tracers FILE [--tracers-every N]] [--tracers-show] [--session-out FILE [--session-every N]] [--session-in FILE] <scenario>\n", argv0);
 }
 
 /* ---- terminal (misc/terminal.c) ------------------------------------------------------------ */
@@ -209,6 +217,38 @@ static int write_ppm_frame(euler_sim* sim, const char* prefix, int frame, const 
     if (!ok) fprintf(stderr, "--ppm: cannot write %s: %s\n", path, strerror(errno));
   }
   free(px); free(rgb); free(path);
+  return ok ? 0 : -1;
+}
+
+/* ---- --envelope-out, --envelope-ppm: the planes and their images at exit (docs/envelope.md) ---------------- */
+static int write_envelopes(euler_sim* sim, uint32_t channels, int X, int Y, const char* out_prefix, const char* ppm_prefix, const double* scale) {
+  const int W = X - 2 < 1024 ? X - 2 : 1024, H = Y - 2 < 1024 ? Y - 2 : 1024;
+  const size_t cells = (size_t)X * (size_t)Y, n = (size_t)W * (size_t)H, plen = strlen(out_prefix ? out_prefix : "") + strlen(ppm_prefix ? ppm_prefix : "") + 32;
+  float* plane = out_prefix ? (float*)malloc(cells * sizeof *plane) : NULL;
+  euler_envelope_px* px = ppm_prefix ? (euler_envelope_px*)malloc(n * sizeof *px) : NULL;
+  uint8_t* rgb = ppm_prefix ? (uint8_t*)malloc(n * 3) : NULL;
+  char* path = (char*)malloc(plen);
+  char head[64];
+  int ok = path && (!out_prefix || plane) && (!ppm_prefix || (px && rgb));
+  if (!ok) fprintf(stderr, "--envelope: out of memory\n");
+  if (ok && ppm_prefix && euler_envelope_raster(sim, 1, 1, X - 2, Y - 2, W, H, px, n * sizeof *px) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); ok = 0; }
+  for (int k = 0; ok && k < CLI_ENVELOPE_CHANNELS; ++k) {
+    if (!(channels & (1u << k))) continue;
+    if (out_prefix) {
+      if (euler_envelope_get_field(sim, 1 << k, plane, cells * sizeof *plane) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); ok = 0; break; }
+      if (cli_envelope_path(path, plen, out_prefix, k, "f32") != 0 || cli_envelope_write(path, NULL, plane, cells * sizeof *plane) != 0) {
+        fprintf(stderr, "--envelope-out: cannot write %s: %s\n", path, strerror(errno)); ok = 0; break;
+      }
+    }
+    if (ppm_prefix) {
+      if (euler_envelope_rgb(px, W, H, 1 << k, scale[k], rgb, n * 3) != EULER_OK) { fprintf(stderr, "--envelope-ppm: the painter refused\n"); ok = 0; break; }
+      snprintf(head, sizeof head, "P6\n%d %d\n255\n", W, H);
+      if (cli_envelope_path(path, plen, ppm_prefix, k, "ppm") != 0 || cli_envelope_write(path, head, rgb, n * 3) != 0) {
+        fprintf(stderr, "--envelope-ppm: cannot write %s: %s\n", path, strerror(errno)); ok = 0; break;
+      }
+    }
+  }
+  free(plane); free(px); free(rgb); free(path);
   return ok ? 0 : -1;
 }
 
@@ -445,6 +485,12 @@ int main(int argc, char** argv) {
   int n_bodies = 0;
   euler_reseed reseed;
   int reseed_given = 0;
+  uint32_t envelope = 0;
+  int envelope_given = 0;
+  const char* envelope_out = NULL;
+  static char envelope_ppm[4096];
+  double envelope_scale[CLI_ENVELOPE_CHANNELS];
+  int envelope_ppm_given = 0;
   static cli_seed seeds[MAX_CLI_TRACERS + MAX_TRACER_BOXES];
   cli_emitter emitters[MAX_EMITTERS];
   int n_seeds = 0, n_points = 0, n_tboxes = 0, n_emitters = 0, tracers_every = 1, tracers_show = 0;
@@ -540,6 +586,10 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--max-iterations") && i + 1 < argc) { cfg.max_iterations = atoi(argv[++i]); if (cfg.max_iterations < 1) { usage(argv[0]); return 1; } }
     /* marker density control (docs/reseed.md) */
     else if (!strcmp(argv[i], "--reseed") && i + 1 < argc) { if (parse_reseed(argv[++i], &reseed) != 0) { usage(argv[0]); return 1; } reseed_given = 1; }
+    /* run-long envelopes (docs/envelope.md) */
+    else if (!strcmp(argv[i], "--envelope") && i + 1 < argc) { if (parse_envelope(argv[++i], &envelope) != 0) { usage(argv[0]); return 1; } envelope_given = 1; }
+    else if (!strcmp(argv[i], "--envelope-out") && i + 1 < argc) envelope_out = argv[++i];
+    else if (!strcmp(argv[i], "--envelope-ppm") && i + 1 < argc) { if (parse_envelope_ppm(argv[++i], envelope_ppm, sizeof envelope_ppm, envelope_scale) != 0) { usage(argv[0]); return 1; } envelope_ppm_given = 1; }
     /* session files (docs/session.md) */
     else if (!strcmp(argv[i], "--session-out") && i + 1 < argc) session_out = argv[++i];
     else if (!strcmp(argv[i], "--session-every") && i + 1 < argc) { session_every = atoi(argv[++i]); if (session_every < 1) { usage(argv[0]); return 1; } }
@@ -549,6 +599,7 @@ int main(int argc, char** argv) {
   }
   if (!scenario && !resume && !session_in) { usage(argv[0]); return 1; }                                        /* main.c:986-989 */
   if (session_every && !session_out) { usage(argv[0]); return 1; }
+  if ((envelope_out || envelope_ppm_given) && !envelope_given) { usage(argv[0]); return 1; }
   if (session_in) {      /* what the file carries cannot be given again */
     const cli_session_clash clash = {scenario != NULL, resume != NULL, upscale, forcing_given, heat_given || heat_extra, n_bodies, reseed_given, n_seeds};
     const char* what = cli_session_conflict(&clash);
@@ -626,7 +677,8 @@ int main(int argc, char** argv) {
       (forcing_given && euler_set_forcing(app.sim, &forcing, n_force_boxes ? force_boxes : NULL) != EULER_OK) ||
       (heat_given && euler_set_heat(app.sim, &heat, n_heat_boxes ? heat_boxes : NULL) != EULER_OK) ||      /* (behind the load and the forcing) */
       (n_bodies && euler_set_bodies(app.sim, bodies, n_bodies) != EULER_OK) ||
-      (reseed_given && euler_set_reseed(app.sim, &reseed) != EULER_OK)) {
+      (reseed_given && euler_set_reseed(app.sim, &reseed) != EULER_OK) ||
+      (envelope_given && euler_set_envelope(app.sim, envelope) != EULER_OK)) {      /* (beside --session-in too: the file does not carry the planes, they start fresh) */
     fprintf(stderr, "%s\n", euler_last_error());
     return 1;
   }
@@ -742,6 +794,7 @@ int main(int argc, char** argv) {
   if (gauges_file && fclose(gauges_file) != 0 && !rc_exit) { fprintf(stderr, "--gauges: cannot write %s: %s\n", gauges, strerror(errno)); rc_exit = 1; }
   if (!rc_exit && checkpoint && euler_save_state(app.sim, checkpoint) != EULER_OK) { fprintf(stderr, "%s\n", euler_last_error()); rc_exit = 1; }
   if (!rc_exit && session_out && cli_session_save(app.sim, session_out) != 0) rc_exit = 1;
+  if (!rc_exit && (envelope_out || envelope_ppm_given) && write_envelopes(app.sim, envelope, cfg.X, cfg.Y, envelope_out, envelope_ppm_given ? envelope_ppm : NULL, envelope_scale) != 0) rc_exit = 1;
   euler_stats st;
   if (euler_get_stats(app.sim, &st) == EULER_OK)
     fprintf(stderr, "frames %llu substeps %llu pcg_iterations %llu markers %llu\n", (unsigned long long)st.frames,

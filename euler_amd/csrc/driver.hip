@@ -568,6 +568,7 @@ static int upload_scenario(euler_sim* S, const uint8_t* solid, const uint8_t* so
   S->time = 0.0;      // (the forcing stays as set: docs/forcing.md)
   S->n_tracers = 0;   // (the tracers belonged to the run that was replaced: docs/tracers.md)
   S->n_bodies = 0;    // (so did the bodies: their cells are whatever the loaded masks say, docs/bodies.md)
+  if ((rc = eu_envelope_off(S))) return rc;    // (and the envelopes: their planes were that run's history, docs/envelope.md)
   if ((rc = eu_heat_reset(S))) return rc;      // (the heat record stays as set, the field starts from ambient: docs/heat.md)
   S->loaded = 1;
   return EULER_OK;
@@ -752,10 +753,10 @@ static int run_stage(euler_sim* S, int stage, float dt) {
       return rc;
     }
     case EULER_STAGE_PROJECT: {
-      if (!S->n_bodies) return eu_launch_project(S, dt);
-      int rc = eu_launch_body_faces(S, dt, 1);      // the wall velocity stands on the bodies' wet faces for the length of the solve, and nowhere else in a substep
+      int rc = S->n_bodies ? eu_launch_body_faces(S, dt, 1) : EULER_OK;      // the wall velocity stands on the bodies' wet faces for the length of the solve, and nowhere else in a substep
       if (!rc) rc = eu_launch_project(S, dt);
-      return rc ? rc : eu_launch_body_faces(S, dt, 0);
+      if (!rc && S->n_bodies) rc = eu_launch_body_faces(S, dt, 0);
+      return rc || !S->env_channels ? rc : eu_launch_envelope(S, dt);      // the run-long envelopes, where they are on, on what the stage leaves (docs/envelope.md)
     }
     default: eu_set_error("unknown stage %d", stage); return EULER_EINVAL;
   }

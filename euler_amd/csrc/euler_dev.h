@@ -196,6 +196,12 @@ struct euler_sim {
   euler_reseed reseed;
   int reseed_on;
   eu_devbuf rs_mask_buf, rs_cell_buf, rs_slot_buf, rs_draw_buf;
+  // euler_set_envelope (k_envelope.hip, docs/envelope.md): the channels that are on (the host flag run_stage tests), the substeps accumulated, one plane per
+  // enabled channel - arrival, wet, speed row-major [C], the pressure's in the band-skewed order of S->p [geom.S] - and the records of euler_envelope_raster
+  uint32_t env_channels;
+  uint64_t env_substeps;
+  uint32_t* env_plane[4];
+  eu_devbuf env_ras_buf;
   float *mc_u, *mc_v;     // EULER_OPT_ADVECT_MACCORMACK (whole-grid handles; allocated by the first switch to 1): the forward results of u, v without gravity; before them
                           // in the same stage, the dye's corrected channels on their way into g_r, g_g, g_b (docs/advection_maccormack.md)
   // markers, ping-pong (main.c:95)
@@ -438,6 +444,9 @@ int eu_launch_bodies_shift(euler_sim* S, float dt);
 int eu_launch_body_faces(euler_sim* S, float dt, int impose);
 // k_reseed.hip (euler_set_reseed; callers test S->reseed_on): one pass of the marker density control, behind eu_launch_refresh_counts in EULER_STAGE_REFRESH_COUNTS
 int eu_launch_reseed(euler_sim* S);
+// k_envelope.hip (euler_set_envelope; callers test S->env_channels): the planes' update at the end of EULER_STAGE_PROJECT; the switch-off behind a load
+int eu_launch_envelope(euler_sim* S, float dt);
+int eu_envelope_off(euler_sim* S);
 // k_edit.hip: the cell pass of an edit alone (SOLID, CLEAR) and the source cells of a box, for the bodies' strips
 int eu_edit_cells_box(euler_sim* S, int cls, int op, int x0, int y0, int x1, int y1);
 int eu_edit_source_census(euler_sim* S, int cls, int x0, int y0, int x1, int y1, size_t* nsrc);

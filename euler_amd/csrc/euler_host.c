@@ -397,6 +397,52 @@ int euler_overview_rgb(const euler_overview_px* px, int32_t W, int32_t H, int32_
   return EULER_OK;
 }
 
+/* ---- the envelopes' host side (include/euler.h, docs/envelope.md): the channel index, the words a restored plane may hold, the image ---- */
+
+int eu_envelope_index(int32_t channel) {
+  switch (channel) {
+    case EULER_ENV_ARRIVAL: return 0;
+    case EULER_ENV_WET: return 1;
+    case EULER_ENV_SPEED: return 2;
+    case EULER_ENV_PRESSURE: return 3;
+    default: return -1;
+  }
+}
+
+size_t eu_envelope_check_words(int32_t channel, const uint32_t* w, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    if (channel == EULER_ENV_ARRIVAL && w[i] == 0xffffffffu) continue;
+    if (w[i] >= 0x7f800000u) return i;      /* an infinity, a NaN or a set sign bit (-0.f too) */
+  }
+  return (size_t)-1;
+}
+
+static float envelope_word(uint32_t w) {
+  float f;
+  memcpy(&f, &w, sizeof f);
+  return f;
+}
+
+int euler_envelope_rgb(const euler_envelope_px* px, int32_t W, int32_t H, int32_t channel, double scale, uint8_t* rgb, size_t rgb_bytes) {
+  if (!px || !rgb || W < 1 || H < 1 || eu_envelope_index(channel) < 0) return EULER_EINVAL;
+  if (!isfinite(scale) || !(scale > 0.0)) return EULER_EINVAL;
+  if (rgb_bytes != (size_t)W * (size_t)H * 3) return EULER_EINVAL;
+  const size_t n = (size_t)W * (size_t)H;
+  for (size_t i = 0; i < n; ++i) {
+    const euler_envelope_px* r = px + i;
+    const uint32_t word = channel == EULER_ENV_ARRIVAL ? r->arrival_min : (channel == EULER_ENV_WET ? r->wet_max : (channel == EULER_ENV_SPEED ? r->speed2_max : r->p_max));
+    const int dark = channel == EULER_ENV_ARRIVAL ? r->touched == 0 : (r->touched == 0 && word == 0);
+    if (dark) { rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = 0; continue; }
+    double value = (double)envelope_word(word);
+    if (channel == EULER_ENV_SPEED) value = sqrt(value);
+    double t = value / scale;
+    t = t > 0.0 ? (t < 1.0 ? t : 1.0) : 0.0;      /* (a NaN: 0) */
+    const uint8_t c = (uint8_t)(255.0 * (1.0 - t));
+    rgb[3 * i] = 255; rgb[3 * i + 1] = c; rgb[3 * i + 2] = c;
+  }
+  return EULER_OK;
+}
+
 /* ---- flow diagnostics: what a user reads off an euler_diag record (include/euler.h, docs/diagnostics.md) ---- */
 
 int euler_diag_derive(const euler_diag* rec, euler_diag_values* out) {

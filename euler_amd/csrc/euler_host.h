@@ -65,6 +65,10 @@ size_t   eu_tracer_lattice(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32
 /* moving bodies (k_bodies.hip, docs/bodies.md): the refusals of euler_set_bodies that need no device, in its order; the unit shifts that take a body from its
  * remembered origin to its target - all x shifts first, then y -; and the faces of a rectangle's perimeter */
 int      eu_body_check(const euler_body* b, int32_t n, int32_t X, int32_t Y, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */
+/* the envelopes (k_envelope.hip, docs/envelope.md): channel is exactly one EULER_ENV_* bit -> its index 0 ... 3, else -1; and the words euler_envelope_set_field
+ * accepts for it - arrival: 0xffffffff or a finite float >= 0, the others: a finite float >= +0 (no NaN, no -0.f) -: the index of the first bad word, (size_t)-1: none */
+int      eu_envelope_index(int32_t channel);
+size_t   eu_envelope_check_words(int32_t channel, const uint32_t* w, size_t n);
 typedef struct eu_body_shift { int32_t axis, dir; } eu_body_shift;   /* axis 0: x, 1: y; dir +1 or -1 */
 /* the number of unit shifts from (ox, oy) to (tx, ty), |tx - ox| + |ty - oy|; out (may be NULL) takes the first min(count, cap) of them */
 int64_t  eu_body_plan(int32_t ox, int32_t oy, int32_t tx, int32_t ty, eu_body_shift* out, int64_t cap);

@@ -443,6 +443,7 @@ static int load_state_finish(euler_sim* S, const SnapHeader& h0) {
   S->time = 0.0;      // (the clock is no part of a snapshot and the forcing stays as set: the caller restores both, docs/forcing.md)
   S->n_tracers = 0;   // (tracers are no part of a snapshot either: docs/tracers.md)
   S->n_bodies = 0;    // (nor are the moving bodies: docs/bodies.md)
+  if ((rc = eu_envelope_off(S))) return rc;      // (nor are the envelopes' planes, in a snapshot or in a session file: docs/envelope.md)
   if ((rc = eu_heat_reset(S))) return rc;      // (nor is the temperature: the record stays as set, the field starts from ambient, docs/heat.md)
   S->loaded = 1;
   return EULER_OK;

@@ -824,6 +824,56 @@ int euler_set_reseed(euler_sim* sim, const euler_reseed* r);
 /* The record as set (all zero: off; the limits as given, 0 where the default stands) and the totals; either pointer may be NULL. */
 int euler_get_reseed(euler_sim* sim, euler_reseed* r, euler_reseed_stats* stats);
 
+/* ---- run-long envelopes: arrival time, wet time, peak speed and peak pressure per cell (docs/envelope.md) ---- */
+/* Opt-in, whole-grid handles only; a handle that never switches it on launches what it launched.  While channels are on, the handle holds one plane per channel of
+ * one 32-bit word per cell of the X x Y grid, and every EULER_STAGE_PROJECT ends - behind the bodies' face withdrawal, in a substep and in euler_stage - with one
+ * update of the interior cells that are FLUID at that moment (count != 0 && !solid, as the gauges define it), in float32 without contraction:
+ *   channel               initial word            update
+ *   EULER_ENV_ARRIVAL     0xffffffff ("never")    a word that is still 0xffffffff becomes the bits of t_end = (float)(euler_get_time() + (double)dt), the clock taken
+ *                                                 before the substep
+ *   EULER_ENV_WET         +0.f                    w = w + dt
+ *   EULER_ENV_SPEED       +0.f                    the maximum, as bit patterns, of the word and s2 = dx*dx + dy*dy, dx = (u[i] + u[i-1]) / 2, dy = (v[i] + v[i-X]) / 2
+ *   EULER_ENV_PRESSURE    +0.f                    the maximum of the word and pf > 0.f ? pf : 0.f, pf = (float) of the double euler_get_field(EULER_F_PRESSURE) shows
+ * A NaN in s2 or pf is skipped.  A cell that is not fluid is not touched in any channel: a cell that is solid now keeps what it gathered while it was wet.  The clock
+ * does not advance inside euler_stage, so a repeated euler_stage(EULER_STAGE_PROJECT) accumulates again with the same t_end.  With the pressure channel on the pending
+ * pressure is finished first (as euler_get_field does); nothing else of the state is touched: fields, markers, generator and counters are those of a handle without it.
+ * The planes are not part of a snapshot or of a session file: a scenario load, euler_load_state and euler_load_session switch the envelope off. */
+enum { EULER_ENV_ARRIVAL = 1, EULER_ENV_WET = 2, EULER_ENV_SPEED = 4, EULER_ENV_PRESSURE = 8, EULER_ENV_ALL = 15 };
+/* Refusals of the calls below, in this order, changing and allocating nothing: a null handle or pointer (EULER_EINVAL); a row-slab handle (EULER_ESTATE, "slab" in
+ * the text); nothing loaded (EULER_ESTATE); then EULER_EINVAL for the call's own arguments.
+ * euler_set_envelope: channels is a set of EULER_ENV_* bits (a bit outside EULER_ENV_ALL: refused).  A newly enabled channel's plane is allocated (EULER_ENOMEM: the
+ * handle as it was) and takes its initial words, a disabled one is freed, one that stays enabled keeps its words; 0 switches the feature off.  The substep count
+ * starts from 0 whenever the envelope goes from off to on.  The planes are counted in euler_hbm_bytes: 4 X Y bytes each, the pressure's - kept in the solver's
+ * band-skewed order - 4 S bytes for the S elements of a skewed array. */
+int euler_set_envelope(euler_sim* sim, uint32_t channels);
+/* the channels that are on and the substeps accumulated since the envelope was switched on or last reset; either pointer may be NULL */
+int euler_get_envelope(euler_sim* sim, uint32_t* channels, uint64_t* substeps);
+/* the enabled planes back to their initial words, the substep count to 0 */
+int euler_envelope_reset(euler_sim* sim);
+/* One plane, row-major, X * Y words (row 0 first); channel is exactly one enabled bit and bytes == 4 * X * Y: else EULER_EINVAL.  euler_envelope_set_field restores
+ * a plane the caller kept: an arrival word must be 0xffffffff or a finite float >= 0, any other channel's word a finite float >= +0 (no NaN, no -0.f); otherwise
+ * EULER_EINVAL with the first bad index named and the plane unchanged. */
+int euler_envelope_get_field(euler_sim* sim, int32_t channel, float* dst, size_t bytes);
+int euler_envelope_set_field(euler_sim* sim, int32_t channel, const float* src, size_t bytes);
+typedef struct euler_envelope_px {   /* one pixel = one box of interior cells; 32 bytes.  Integer sums and extremes of bit patterns: exact in any order */
+  uint32_t cells;        /* cells of the box */
+  uint32_t touched;      /* ... whose arrival word is set (0 with that channel off) */
+  uint32_t arrival_min;  /* the unsigned minimum of the arrival words (bits of a float; 0xffffffff: no cell was reached, or the channel is off) */
+  uint32_t arrival_max;  /* the maximum over the words that are set; 0: none */
+  uint32_t wet_max;      /* maxima of the words as bit patterns; 0 with the channel off */
+  uint32_t speed2_max;
+  uint32_t p_max;
+  uint32_t reserved;     /* 0 */
+} euler_envelope_px;
+/* The planes per pixel: the box, W, H, the pixel geometry and the row order of euler_overview_box; out_bytes exactly W * H * sizeof(euler_envelope_px).  Reads the
+ * planes only (they are a history: the tile map of the present state does not apply). */
+int euler_envelope_raster(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H, euler_envelope_px* out, size_t out_bytes);
+/* host only, no GPU: W * H * 3 bytes, row 0 = top.  A pixel with touched == 0 is (0, 0, 0) - for a channel other than the arrival, only if that
+ * channel's extreme is 0 as well: with the arrival channel off nothing counts as touched, and the extreme alone says whether water was there.  Otherwise t = clamp(value / scale, 0, 1) in double, value = arrival_min, wet_max,
+ * sqrt(speed2_max) or p_max read as floats, and the colour is (255, 255 (1 - t), 255 (1 - t)), truncated.  EULER_EINVAL with rgb untouched: a null pointer, W or H < 1,
+ * a channel that is not one EULER_ENV_* bit, a scale that is not finite and positive, rgb_bytes != W * H * 3. */
+int euler_envelope_rgb(const euler_envelope_px* px, int32_t W, int32_t H, int32_t channel, double scale, uint8_t* rgb, size_t rgb_bytes);
+
 /* ---- multi-GPU: 1-D row slabs (DESIGN.md "Multi-GPU") ------------------------------ */
 /* One process per GPU.  Two layouts share the communicator interface below:
  *   row slabs for EVERY stage (euler_config.slab_nranks >= 1; the default of bench.py --gpus N): a handle holds only the rows of
