@@ -977,8 +977,10 @@ class Simulation:
 
     @property
     def temperature(self):
-        """The temperature field, float32 of shape (Y, X) (euler_heat_get_field): cells without markers hold ambient."""
-        t = np.zeros((self.Y, self.X), np.float32)
+        """The temperature field, float32 of shape (Y, X) (euler_heat_get_field): cells without markers hold ambient.  A row-slab handle returns and accepts
+        its own rows, shape (rows, X); setting it is collective there (the neighbours' ghost rows follow)."""
+        lo, hi = self.slab_rows()
+        t = np.zeros((hi - lo, self.X), np.float32)
         _check(self.L.euler_heat_get_field(self.h, t.ctypes.data, t.nbytes))
         return t
 

@@ -184,6 +184,7 @@ struct euler_sim {
   euler_heat heat;
   euler_heat_box heat_boxes[EULER_HEAT_BOXES_MAX];
   int heat_on, heat_cur;
+  int heat_ghost_stale;   // row slabs: a pass has written T's own rows since its ghost rows last travelled (eu_slab_exchange_heat clears it)
   unsigned int heat_ntiles;
   eu_devbuf heat_buf, heat_box_buf, heat_fill_buf, heat_ras_buf;      // (heat_ras_buf: the records of euler_heat_raster)
   // euler_set_bodies (k_bodies.hip, docs/bodies.md): the list as set and, per body, the REMEMBERED origin - the cells that are solid now; host state only
@@ -410,11 +411,15 @@ int  eu_slab_after_load(euler_sim* S);
 int  eu_slab_check_partition(euler_sim* S);   // collective: the ranks' band ranges tile the grid
 int  eu_slab_exchange_uv(euler_sim* S);     // ghost rows of u, v (euler_set_field on a slab handle)
 int  eu_slab_exchange_dye(euler_sim* S);    // ghost rows of g_r, g_g, g_b (--rainbow)
+int  eu_slab_exchange_heat(euler_sim* S);   // ghost rows of T (euler_set_heat; a no-op with heat off): one below, one above - the invariant of docs/heat.md "On row slabs"
+float* eu_heat_field(const euler_sim* S);   // k_heat.hip: the half of heat_buf that holds T, as a global-indexed pointer
 int  eu_slab_render(euler_sim* S, int wx, int wy, char* out, int cap, int* len);   // snapshot.hip: euler_render on a row-slab handle (collective)
 int  eu_slab_after_restore(euler_sim* S);   // collective: the job-wide facts a scenario load sets up (source cells of all ranks)
 int  eu_slab_error_sync(euler_sim* S);      // collective: the ranks' sticky error words -> their maximum on every rank
 int  eu_slab_same_everywhere(euler_sim* S, const double* vals, int n, int* same);   // collective: do these host-side values agree on every rank?
 int  eu_slab_status_sync(euler_sim* S, int local_rc, int* worst);   // collective: a host-side status code -> non-zero on every rank if any rank failed
+int  eu_slab_all_ok(euler_sim* S, const char* who, int local_rc);   // collective: an allocation behind the agreement failed on no rank (else an error on every rank)
+int  eu_slab_agree(euler_sim* S, const char* who, int local_rc, unsigned long long digest);   // collective: every rank passed its own check, with the same record and list
 // the tile map describes both count grids and this handle's passes may use it (EULER_OPT_NO_TILE_MAP: rounds 1-5's forms)
 static inline bool eu_tile_map_on(const euler_sim* S) { return eu_vd_tile_map(&S->vd, !S->tmap || S->slab_on || S->opt[EULER_OPT_NO_TILE_MAP] != 0) != 0; }
 // launch groups implemented in the kernel files
@@ -465,7 +470,7 @@ int eu_devbuf_reserve(euler_sim* S, const char* who, const char* what, eu_devbuf
 int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t bytes);   // copy to the caller and wait for it
 // the passes on a row-slab handle (k_observe_slab.hip, docs/observer_passes.md "On row slabs"): every rank reduces the rows of the box it owns into its share of the staging
 // area, the shares are all-gathered as bytes and folded on the device into the pass's own buffer - integer sums and extremes: the whole-grid record bit for bit
-enum { EU_OBS_REC_OVERVIEW = 0, EU_OBS_REC_FLOW, EU_OBS_REC_DIAG, EU_OBS_REC_GAUGE, EU_OBS_REC__COUNT };   // the record types the fold knows
+enum { EU_OBS_REC_OVERVIEW = 0, EU_OBS_REC_FLOW, EU_OBS_REC_DIAG, EU_OBS_REC_GAUGE, EU_OBS_REC_HEAT, EU_OBS_REC__COUNT };   // the record types the fold knows
 enum { EU_OBS_ROWS_NONE = 0, EU_OBS_ROWS_CELLS, EU_OBS_ROWS_FLOW, EU_OBS_ROWS_GAUGES };   // the ghost rows a pass reads (k_slab.hip eu_slab_exchange_observed)
 int eu_slab_exchange_observed(euler_sim* S, int rows);   // k_slab.hip: one grouped exchange of those rows
 size_t eu_observe_rec_bytes(int type);

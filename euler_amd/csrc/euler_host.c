@@ -779,8 +779,15 @@ int eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, int32
 /* (eu_gauge_chunks cuts every box for itself, a tile that n boxes touch n times; here a tile comes once and carries its boxes, so the tiles' bit sets are formed
  * over the tile grid and the touched ones listed row by row) */
 size_t eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, eu_force_tile* out) {
+  return eu_force_tiles_bands(boxes, stride, n, X, Y, 0, (Y + 63) >> 6, out);
+}
+
+/* (a tile row is a band: the entries with band_lo <= ty < band_hi, in the order the whole table lists them) */
+size_t eu_force_tiles_bands(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, int32_t band_lo, int32_t band_hi, eu_force_tile* out) {
   if (n < 1) return 0;
   const int32_t tnx = (X + 63) >> 6, tny = (Y + 63) >> 6;
+  if (band_lo < 0) band_lo = 0;
+  if (band_hi > tny) band_hi = tny;
   uint64_t* set = (uint64_t*)calloc((size_t)tnx * (size_t)tny, sizeof(uint64_t));
   if (!set) return (size_t)-1;
   for (int32_t k = 0; k < n; ++k) {
@@ -789,7 +796,7 @@ size_t eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, in
       for (int32_t tx = r[0] >> 6; tx <= r[2] >> 6; ++tx) set[(size_t)ty * tnx + tx] |= 1ull << k;
   }
   size_t m = 0;
-  for (int32_t ty = 0; ty < tny; ++ty)
+  for (int32_t ty = band_lo; ty < band_hi; ++ty)
     for (int32_t tx = 0; tx < tnx; ++tx) {
       const uint64_t s = set[(size_t)ty * tnx + tx];
       if (!s) continue;
@@ -798,6 +805,23 @@ size_t eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, in
     }
   free(set);
   return m;
+}
+
+/* the record and the first nboxes boxes as bytes (neither struct has padding): what the ranks of a row-slab job compare.  A count outside the list's range - a record
+ * its check refuses - is hashed as it stands, without boxes */
+static uint64_t record_digest(const void* rec, size_t rec_bytes, const void* boxes, size_t box_bytes, int32_t nboxes, int32_t max_boxes) {
+  uint64_t h = eu_fnv1a64(EU_FNV_BASIS, rec, rec_bytes);
+  if (boxes && nboxes > 0 && nboxes <= max_boxes) h = eu_fnv1a64(h, boxes, (size_t)nboxes * box_bytes);
+  return h;
+}
+
+uint64_t eu_forcing_digest(const euler_forcing* f, const euler_force_box* boxes) {
+  return record_digest(f, sizeof *f, boxes, sizeof *boxes, f->nboxes, EULER_FORCE_BOXES_MAX);
+}
+
+uint64_t eu_heat_digest(const euler_heat* h, const euler_heat_box* boxes) {
+  if (!h) return eu_fnv1a64(EU_FNV_BASIS, "off", 3);      /* switching off (euler_set_heat with a null record) against a rank that switches on */
+  return record_digest(h, sizeof *h, boxes, sizeof *boxes, h->nboxes, EULER_HEAT_BOXES_MAX);
 }
 
 /* ---- moving bodies: the law of motion, the list checked, the unit shifts and their strips (include/euler.h, docs/bodies.md) ---- */

@@ -50,6 +50,13 @@ int      eu_forcing_check(const euler_forcing* f, const euler_force_box* boxes, 
 /* boxes: n records `stride` bytes apart that begin with x0, y0, x1, y1 as four int32_t (euler_force_box, euler_heat_box); out == NULL: the count only; the list must
  * have passed its check; (size_t)-1: no memory */
 size_t   eu_force_tiles(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, eu_force_tile* out);
+/* ... and only the entries of the tile rows [band_lo, band_hi) (clipped to the grid's), in the order eu_force_tiles lists them.  A tile lies in one 64-row band and a
+ * row slab is cut at band boundaries, so over the ranks of a row-slab job these tables are a partition of the whole-grid one; a rank no box touches gets 0 entries */
+size_t   eu_force_tiles_bands(const void* boxes, size_t stride, int32_t n, int32_t X, int32_t Y, int32_t band_lo, int32_t band_hi, eu_force_tile* out);
+/* what the ranks of a row-slab job compare before euler_set_forcing / euler_set_heat change anything: FNV-1a over the record's bytes and the first nboxes boxes'
+ * (slots beyond nboxes are not read); h == NULL - switching heat off - has a digest of its own */
+uint64_t eu_forcing_digest(const euler_forcing* f, const euler_force_box* boxes);
+uint64_t eu_heat_digest(const euler_heat* h, const euler_heat_box* boxes);
 /* euler_set_heat (k_heat.hip, docs/heat.md): refusals 4 - 9 of include/euler.h in their order - the ones that need no device; live: the ambient of a handle whose
  * heat is on (NULL: off, any ambient passes).  The tile table of the heat boxes is the force boxes': eu_force_tiles with the stride of euler_heat_box */
 int      eu_heat_check(const euler_heat* h, const euler_heat_box* boxes, int32_t X, int32_t Y, const float* live, char* why, size_t cap);   /* EULER_OK, or EULER_EINVAL with the reason in why */

@@ -13,6 +13,10 @@
 // second cells i + 1 and i + X lie in the grid.  Faces that are not live are neither read nor written: utmp / vtmp stay zero outside the typed fluid property, and
 // nothing else is written - no validity flag changes (docs/stage_validity.md).  With the tile map a tile leaves at once when it, the tile right of it and the tile
 // above it are dry: then no cell of it has a live face.
+//
+// Row slabs (docs/forcing.md "On row slabs"): a tile lies in one 64-row band, so each rank keeps the table entries of its own bands (eu_box_table_upload) and the
+// kernel runs as it stands - global (x, y) through the window-shifted pointers, count[i + X] / solid[i + X] of the top row in the ghost rows, no tile map there.
+// euler_set_forcing is collective on a slab handle: the ranks agree on the record and the list before anything changes (eu_slab_agree).
 #include "k_observe.h"
 #include "k_boxes.h"
 #include "euler_host.h"
@@ -68,17 +72,22 @@ int eu_launch_force_boxes(euler_sim* S, float dt) {
 extern "C" int euler_set_forcing(euler_sim* S, const euler_forcing* f, const euler_force_box* boxes) {
   const char* who = "euler_set_forcing";
   if (!S || !f) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (a slab keeps the reference's gravity, as it keeps the reference's transport)", who); return EULER_ESTATE; }
+  if (S->slab_on && !S->has_comm) { eu_set_error("%s: row-slab handle without a communicator", who); return EULER_ESTATE; }      // (collective there: the ranks agree on the record)
   if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
   char why[256];
-  if (eu_forcing_check(f, boxes, S->X, S->Y, why, sizeof why)) { eu_set_error("%s: %s", who, why); return EULER_EINVAL; }
-  if (f->nboxes > 0) {
-    unsigned int ntiles = 0;
-    const int rc = eu_box_table_upload(S, who, &S->force_buf, boxes, f->nboxes, sizeof(euler_force_box), EULER_FORCE_BOXES_MAX, &ntiles);
-    if (rc) return rc;
-    S->force_ntiles = ntiles;
-    memcpy(S->force_boxes, boxes, (size_t)f->nboxes * sizeof(euler_force_box));
-  } else S->force_ntiles = 0;
+  int rc = EULER_OK;
+  if (eu_forcing_check(f, boxes, S->X, S->Y, why, sizeof why)) { eu_set_error("%s: %s", who, why); rc = EULER_EINVAL; }
+  // a slab handle: every rank takes part in the comparison, whatever its own check said; nothing has changed yet (docs/forcing.md "On row slabs")
+  if (S->slab_on) rc = eu_slab_agree(S, who, rc, rc ? 0ull : eu_forcing_digest(f, boxes));
+  if (rc) return rc;
+  unsigned int ntiles = 0;      // (a slab handle keeps the table entries of its own bands; force_ntiles == 0: this rank launches nothing)
+  if (f->nboxes > 0) rc = eu_box_table_upload(S, who, &S->force_buf, boxes, f->nboxes, sizeof(euler_force_box), EULER_FORCE_BOXES_MAX, &ntiles);
+  // a slab handle: a rank that alone could not hold its table must not go on with the old list beside neighbours that took the new one - the failure is every
+  // rank's, and every rank is left WITHOUT boxes (the buffers of those that succeeded already hold the new table; the record stays the old one otherwise)
+  if (S->slab_on && (rc = eu_slab_all_ok(S, who, rc))) { S->forcing.nboxes = 0; S->force_ntiles = 0; }
+  if (rc) return rc;
+  S->force_ntiles = ntiles;
+  if (f->nboxes > 0) memcpy(S->force_boxes, boxes, (size_t)f->nboxes * sizeof(euler_force_box));
   S->forcing = *f;
   S->force_uniform = !(f->gx == 0.f && f->gy == EU_G && f->shake_x == 0.f && f->shake_y == 0.f);      // the reference's (0, k_gravity): the kernels a handle always ran
   return EULER_OK;

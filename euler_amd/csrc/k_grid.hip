@@ -422,8 +422,8 @@ int eu_launch_advect_velocity(euler_sim* S, float dt) {
   if (lean) while (rep < 16 && ((size_t)S->X * S->Y >> 22) >= (size_t)(2 * rep)) rep *= 2;      // (2048^2: 1, 4096^2: 4, 8192^2 and beyond: 16 - at least 16 K workgroups)
   grid.y = (unsigned)((S->row_hi - S->row_lo + 4 * rep - 1) / (4 * rep));
   const uint8_t* tm = lean ? (const uint8_t*)S->tmap : (const uint8_t*)nullptr;
-  // euler_set_forcing (docs/forcing.md; never on a row slab): the uniform acceleration of this substep, formed once on the host at the handle's clock.  A handle that
-  // holds the default record launches what it always launched
+  // euler_set_forcing (docs/forcing.md): the uniform acceleration of this substep, formed once on the host at the handle's clock - on a row slab at this rank's clock,
+  // which the all-reduced dt advances alike on every rank.  A handle that holds the default record launches what it always launched
   float acc[2] = {0.f, EU_G};
   if (S->force_uniform) (void)euler_forcing_at(&S->forcing, S->time, acc);
   const bool mc = S->opt[EULER_OPT_ADVECT_MACCORMACK] != 0, forced = S->force_uniform != 0;

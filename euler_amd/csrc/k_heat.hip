@@ -45,10 +45,10 @@ __global__ __launch_bounds__(256) void k_heat_mask(const float* __restrict__ src
 // extrapolate(q, P) for T (k_extrapolate_dye's sum: y-major then x, divided by the number of terms), ambient where no neighbour was fluid; then the source cells.
 // Out of place: a source cell that was fluid is read by its new neighbours with the value it had
 __global__ __launch_bounds__(256) void k_heat_extend(const float* __restrict__ tin, float* __restrict__ tout, const uint8_t* __restrict__ prev, const uint8_t* __restrict__ cur,
-                                                     const uint8_t* __restrict__ source, int X, int Y, float ambient, float source_t) {
+                                                     const uint8_t* __restrict__ source, int X, int Y, float ambient, float source_t, int ya, int yb) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= X || y >= Y) return;
+  const int y = ya + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= X || y >= yb) return;
   const size_t i = (size_t)y * X + x;
   float r;
   if (source[i]) r = source_t;
@@ -72,11 +72,11 @@ __global__ __launch_bounds__(256) void k_heat_extend(const float* __restrict__ t
 // count masks; else every cell is written, the dry ones with ambient
 template <bool RK2, bool FWD>
 __global__ __launch_bounds__(256) void k_heat_advect(const float* __restrict__ tin, float* __restrict__ tout, const float* __restrict__ u, const float* __restrict__ v,
-                                                     GridRef gr, float dt, float ambient) {
+                                                     GridRef gr, float dt, float ambient, int ya, int yb) {
   const int X = gr.X;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= X || y >= gr.Y) return;
+  const int y = ya + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= X || y >= yb) return;
   const size_t i = (size_t)y * X + x;
   if (!gr.count[i]) {                            // never fluid on the border ring (all sink): i - X, i - 1 exist below
     if (!FWD) tout[i] = ambient;
@@ -125,11 +125,11 @@ __global__ __launch_bounds__(256) void k_heat_boxes(float* __restrict__ t, const
 }
 
 // one explicit diffusion step over the fluid cells, k_diffuse_velocity's arithmetic: Jacobi from tin; solids and air are insulated; dry cells take ambient
-__global__ __launch_bounds__(256) void k_heat_diffuse(const float* __restrict__ tin, float* __restrict__ tout, const uint8_t* __restrict__ count, int X, int Y, float c,
-                                                      float ambient) {
+__global__ __launch_bounds__(256) void k_heat_diffuse(const float* __restrict__ tin, float* __restrict__ tout, const uint8_t* __restrict__ count, int X, float c,
+                                                      float ambient, int ya, int yb) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= X || y >= Y) return;
+  const int y = ya + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= X || y >= yb) return;
   const size_t i = (size_t)y * X + x;
   if (!count[i]) { tout[i] = ambient; return; }      // (never fluid on the border ring: the four neighbours exist)
   const float q = tin[i];
@@ -143,10 +143,10 @@ __global__ __launch_bounds__(256) void k_heat_diffuse(const float* __restrict__ 
 
 // Boussinesq: a live face (k_force_boxes' test) whose temperature differs from ambient gets -beta (Tf - ambient) a dt; ax == 0 leaves the u faces alone
 __global__ __launch_bounds__(256) void k_heat_buoyancy(const float* __restrict__ t, float* __restrict__ utmp, float* __restrict__ vtmp, const uint8_t* __restrict__ count,
-                                                       const uint8_t* __restrict__ solid, int X, int Y, float ambient, float beta, float ax, float ay, float dt) {
+                                                       const uint8_t* __restrict__ solid, int X, int Y, float ambient, float beta, float ax, float ay, float dt, int ya, int yb) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= X || y >= Y) return;
+  const int y = ya + blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= X || y >= yb) return;
   const size_t i = (size_t)y * X + x;
   const bool cn = count[i] != 0, so = solid[i] != 0;
   if (y < Y - 1) {
@@ -173,13 +173,16 @@ __global__ __launch_bounds__(256) void k_heat_dry(float* __restrict__ t, const u
   if (i < n && !count[i]) t[i] = ambient;
 }
 
-// euler_heat_raster, first launch: every record of the W x H raster with its cell count (euler_overview_box's pixel edges) and zeros
-__global__ __launch_bounds__(256) void k_heat_ras_init(euler_heat_px* __restrict__ out, int W, int H, int Bw, int Bh) {
+// euler_heat_raster, first launch: every record of the W x H raster with its cell count (euler_overview_box's pixel edges) and zeros.  A row slab: the Hl pixel
+// rows from py0 on that this rank's rows [cy0, cy1] of the box touch, each with the cells of those rows only - the shares' counts add up to the whole-grid one
+__global__ __launch_bounds__(256) void k_heat_ras_init(euler_heat_px* __restrict__ out, int W, int H, int Bw, int Bh, int Hl, int py0, int by1, int cy0, int cy1) {
   const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= (size_t)W * (size_t)H) return;
-  const unsigned long long px = k % (unsigned int)W, py = k / (unsigned int)W;
+  if (k >= (size_t)W * (size_t)Hl) return;
+  const unsigned long long px = k % (unsigned int)W, py = (unsigned long long)py0 + k / (unsigned int)W;
   const unsigned int wpx = (unsigned int)((px + 1) * (unsigned int)Bw / (unsigned int)W) - (unsigned int)(px * (unsigned int)Bw / (unsigned int)W);
-  const unsigned int hpx = (unsigned int)((py + 1) * (unsigned int)Bh / (unsigned int)H) - (unsigned int)(py * (unsigned int)Bh / (unsigned int)H);
+  const int ytop = by1 - (int)(py * (unsigned int)Bh / (unsigned int)H), ybot = by1 + 1 - (int)((py + 1) * (unsigned int)Bh / (unsigned int)H);      // the pixel row's cell rows
+  const int yhi = ytop < cy1 ? ytop : cy1, ylo = ybot > cy0 ? ybot : cy0;
+  const unsigned int hpx = yhi >= ylo ? (unsigned int)(yhi - ylo + 1) : 0u;
   euler_heat_px r;
   r.cells = wpx * hpx; r.water = 0u; r.t_pos = 0ull; r.t_neg = 0ull; r.max_above = 0.f; r.max_below = 0.f;
   out[k] = r;
@@ -187,15 +190,16 @@ __global__ __launch_bounds__(256) void k_heat_ras_init(euler_heat_px* __restrict
 // ... second launch: a thread per cell of the box, a wave along 64 columns; a water cell goes to the record of its pixel with integer adds and bit-pattern maxima
 // (exact in any order).  qv is the flow raster's: min(a, 4096) 2^20, truncated; a NaN goes to no sum and no maximum
 __global__ __launch_bounds__(256) void k_heat_raster(const float* __restrict__ t, const uint8_t* __restrict__ solid, const uint8_t* __restrict__ sink, const uint8_t* __restrict__ count,
-                                                     euler_heat_px* __restrict__ out, int X, int bx0, int by0, int by1, int Bw, int Bh, int W, int H, float ambient) {
+                                                     euler_heat_px* __restrict__ out, int X, int bx0, int ry0, int nrows, int by1, int Bw, int Bh, int W, int H, int py0,
+                                                     float ambient) {      // rows ry0 ... ry0 + nrows - 1 of the box (a row slab: the own ones), records from pixel row py0 on
   const int cx = blockIdx.x * 64 + (int)(threadIdx.x & 63), cy = blockIdx.y * 4 + (int)(threadIdx.x >> 6);
-  if (cx >= Bw || cy >= Bh) return;
-  const int x = bx0 + cx, y = by0 + cy;
+  if (cx >= Bw || cy >= nrows) return;
+  const int x = bx0 + cx, y = ry0 + cy;
   const size_t i = (size_t)y * (size_t)X + (size_t)x;
   if (solid[i] || sink[i] || !count[i]) return;
   const int px = (int)(((unsigned long long)(cx + 1) * (unsigned int)W - 1ull) / (unsigned int)Bw);      // the pixel column whose range holds x ...
   const int py = (int)(((unsigned long long)(by1 - y + 1) * (unsigned int)H - 1ull) / (unsigned int)Bh);  // ... and the pixel row, counted from the top
-  euler_heat_px* o = out + (size_t)py * W + px;
+  euler_heat_px* o = out + (size_t)(py - py0) * W + px;
   atomicAdd(&o->water, 1u);
   const float d = t[i] - ambient;
   if (d != d) return;
@@ -208,28 +212,38 @@ static_assert(sizeof(euler_heat_px) == 32 && offsetof(euler_heat_px, water) == 4
               offsetof(euler_heat_px, max_above) == 24 && offsetof(euler_heat_px, max_below) == 28, "euler_heat_px is 32 bytes without padding");
 
 // ------------------------------------------------------------------------------------------ the launchers
-static inline dim3 heat_grid(const euler_sim* S) { return dim3((S->X + 63) / 64, (S->Y + 3) / 4); }
-static inline float* heat_half(const euler_sim* S, int k) { return (float*)S->heat_buf.p + (size_t)k * S->C; }
+// The passes run over the handle's own rows [row_lo, row_hi) - the whole grid without slabs.  A half of heat_buf holds the window (own rows + ghost rows, Cw floats;
+// the grid without slabs) and is addressed with GLOBAL (x, y) through a base shifted by win_off, like u (euler_dev.h).  On a row slab one ghost row of T below and
+// one above the own rows hold the neighbours' current values behind every stage and every call that writes T (docs/heat.md "On row slabs"): eu_slab_exchange_heat
+static inline dim3 heat_grid(const euler_sim* S) { return dim3((S->X + 63) / 64, (S->row_hi - S->row_lo + 3) / 4); }
+static inline float* heat_half(const euler_sim* S, int k) { return (float*)S->heat_buf.p + (size_t)k * S->Cw - S->win_off; }
 static inline float* heat_t(const euler_sim* S) { return heat_half(S, S->heat_cur); }
 static inline float* heat_other(const euler_sim* S) { return heat_half(S, S->heat_cur ^ 1); }
+static inline size_t heat_own0(const euler_sim* S) { return (size_t)S->row_lo * S->X; }                       // the first own cell ...
+static inline size_t heat_own_n(const euler_sim* S) { return (size_t)(S->row_hi - S->row_lo) * S->X; }       // ... and how many there are
+float* eu_heat_field(const euler_sim* S) { return heat_t(S); }      // (k_slab.hip: the field whose ghost rows travel)
 
-int eu_heat_reset(euler_sim* S) {
+int eu_heat_reset(euler_sim* S) {      // the whole window: the ghost rows hold ambient as the neighbours' rows do
   if (!S->heat_on) return EULER_OK;
   S->heat_cur = 0;
-  LAUNCH(S, KC_MISC, k_heat_set, dim3(eu_blocks(S->C, 256)), dim3(256), heat_t(S), S->C, S->heat.ambient);
+  S->heat_ghost_stale = 0;
+  LAUNCH(S, KC_MISC, k_heat_set, dim3(eu_blocks(S->Cw, 256)), dim3(256), heat_t(S) + S->win_off, S->Cw, S->heat.ambient);
   HIPCHK(hipGetLastError());
   return EULER_OK;
 }
 
 int eu_heat_dry(euler_sim* S) {
-  LAUNCH(S, KC_MISC, k_heat_dry, dim3(eu_blocks(S->C, 256)), dim3(256), heat_t(S), S->count, S->C, S->heat.ambient);
+  LAUNCH(S, KC_MISC, k_heat_dry, dim3(eu_blocks(heat_own_n(S), 256)), dim3(256), heat_t(S) + heat_own0(S), S->count + heat_own0(S), heat_own_n(S), S->heat.ambient);
   HIPCHK(hipGetLastError());
   return EULER_OK;
 }
 
+// (on a row slab: behind the exchange of the count grids that follows the sources - the 3 x 3 reads prev_count across the row edges -, and in front of T's)
 int eu_launch_heat_sources(euler_sim* S) {
-  LAUNCH(S, KC_EXTRAPOLATE, k_heat_extend, heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->prev_count, S->count, S->source, S->X, S->Y, S->heat.ambient, S->heat.source_t);
+  LAUNCH(S, KC_EXTRAPOLATE, k_heat_extend, heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->prev_count, S->count, S->source, S->X, S->Y, S->heat.ambient, S->heat.source_t,
+         S->row_lo, S->row_hi);
   S->heat_cur ^= 1;
+  S->heat_ghost_stale = 1;
   return EULER_OK;
 }
 
@@ -248,19 +262,28 @@ int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]) {
   eu_flag(S->opt[EULER_OPT_ADVECT_RK2] != 0, [&](auto R) {
     eu_flag(S->opt[EULER_OPT_ADVECT_MACCORMACK] != 0, [&](auto M) {
       constexpr bool RK2 = decltype(R)::value, MC = decltype(M)::value;
-      LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<RK2, MC>), heat_grid(S), dim3(256), heat_t(S), MC ? S->mc_u : heat_other(S), S->u, S->v, g, dt, amb);
-      if (MC) LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_correct<RK2>, heat_grid(S), dim3(256), heat_t(S), S->mc_u, heat_other(S), S->u, S->v, g, dt, amb);
+      LAUNCH(S, KC_ADVECT_VELOCITY, (k_heat_advect<RK2, MC>), heat_grid(S), dim3(256), heat_t(S), MC ? S->mc_u : heat_other(S), S->u, S->v, g, dt, amb, S->row_lo, S->row_hi);
+      if (MC) LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_correct<RK2>, heat_grid(S), dim3(256), heat_t(S), S->mc_u, heat_other(S), S->u, S->v, g, dt, amb);      // (never on a row slab)
     });
   });
   S->heat_cur ^= 1;
+  S->heat_ghost_stale = 1;
+  // (a row slab: this rank's entries of the table - none when no box touches its bands)
   if (S->heat.nboxes > 0 && S->heat_ntiles) { int rc = heat_launch_boxes(S, KC_ADVECT_VELOCITY, &S->heat_box_buf, S->heat_ntiles, dt); if (rc) return rc; }
+  // Row slabs: the diffusion reads T one row below and above the own rows, the buoyancy one row above - each behind an exchange of what the passes before it wrote,
+  // and only then: with kappa == 0 and beta == 0 T's ghost rows travel with vtmp's, behind this stage (k_slab.hip)
   if (S->heat.kappa > 0.f) {
+    if (S->slab_on) { int rc = eu_slab_exchange_heat(S); if (rc) return rc; }
     const float c = S->heat.kappa * dt;
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_diffuse, heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->count, S->X, S->Y, c, amb);
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_diffuse, heat_grid(S), dim3(256), heat_t(S), heat_other(S), S->count, S->X, c, amb, S->row_lo, S->row_hi);
     S->heat_cur ^= 1;
+    S->heat_ghost_stale = 1;
   }
-  if (S->heat.beta != 0.f)
-    LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_buoyancy, heat_grid(S), dim3(256), heat_t(S), S->utmp, S->vtmp, S->count, S->solid, S->X, S->Y, amb, S->heat.beta, acc[0], acc[1], dt);
+  if (S->heat.beta != 0.f) {
+    if (S->slab_on) { int rc = eu_slab_exchange_heat(S); if (rc) return rc; }
+    LAUNCH(S, KC_ADVECT_VELOCITY, k_heat_buoyancy, heat_grid(S), dim3(256), heat_t(S), S->utmp, S->vtmp, S->count, S->solid, S->X, S->Y, amb, S->heat.beta, acc[0], acc[1], dt,
+           S->row_lo, S->row_hi);
+  }
   HIPCHK(hipGetLastError());
   return EULER_OK;
 }
@@ -269,15 +292,23 @@ int eu_launch_heat_advect(euler_sim* S, float dt, const float acc[2]) {
 extern "C" int euler_set_heat(euler_sim* S, const euler_heat* h, const euler_heat_box* boxes) {
   const char* who = "euler_set_heat";
   if (!S) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle (a slab keeps the reference's homogeneous water, as it keeps the reference's transport)", who); return EULER_ESTATE; }
+  if (S->slab_on && !S->has_comm) { eu_set_error("%s: row-slab handle without a communicator", who); return EULER_ESTATE; }      // (collective there: the ranks agree on the record)
   if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
-  if (!h) { S->heat_on = 0; return EULER_OK; }      // off: the buffers stay, the next switching-on starts from ambient
   char why[320];
-  if (eu_heat_check(h, boxes, S->X, S->Y, S->heat_on ? &S->heat.ambient : nullptr, why, sizeof why)) { eu_set_error("%s: %s", who, why); return EULER_EINVAL; }
-  int rc = eu_devbuf_reserve(S, who, "the temperature and its scratch copy", &S->heat_buf, 2 * S->C * sizeof(float));
+  int rc = EULER_OK;
+  if (h && eu_heat_check(h, boxes, S->X, S->Y, S->heat_on ? &S->heat.ambient : nullptr, why, sizeof why)) { eu_set_error("%s: %s", who, why); rc = EULER_EINVAL; }
+  // a slab handle: every rank takes part in the comparison, whatever its own check said, switching off included - a rank with heat off would skip an exchange its
+  // neighbour waits in; nothing has changed yet (docs/heat.md "On row slabs")
+  if (S->slab_on) rc = eu_slab_agree(S, who, rc, rc ? 0ull : eu_heat_digest(h, boxes));
   if (rc) return rc;
+  if (!h) { S->heat_on = 0; return EULER_OK; }      // off: the buffers stay, the next switching-on starts from ambient
+  rc = eu_devbuf_reserve(S, who, "the temperature and its scratch copy", &S->heat_buf, 2 * S->Cw * sizeof(float));      // (the window: the grid without slabs)
   unsigned int ntiles = 0;
-  if (h->nboxes > 0 && (rc = eu_box_table_upload(S, who, &S->heat_box_buf, boxes, h->nboxes, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, &ntiles))) return rc;
+  if (!rc && h->nboxes > 0) rc = eu_box_table_upload(S, who, &S->heat_box_buf, boxes, h->nboxes, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, &ntiles);
+  // a slab handle: a rank that alone could not reserve its buffers must not stay off beside neighbours that switch on and wait for it in T's exchange - the failure
+  // is every rank's.  Heat stays on or off as it was, on every rank WITHOUT boxes (the buffers of the ranks that succeeded already hold the new table)
+  if (S->slab_on && (rc = eu_slab_all_ok(S, who, rc))) { S->heat.nboxes = 0; S->heat_ntiles = 0; }
+  if (rc) return rc;
   const int was_on = S->heat_on;
   S->heat = *h;
   S->heat_ntiles = ntiles;
@@ -299,33 +330,45 @@ extern "C" int euler_get_heat(euler_sim* S, euler_heat* h, euler_heat_box* boxes
 // the refusals the field calls share: a null argument, a slab handle, nothing loaded, heat off
 static int heat_field_enter(euler_sim* S, const void* arg, const char* who) {
   if (!S || !arg) { eu_set_error("%s: null argument", who); return EULER_EINVAL; }
-  if (S->slab_on) { eu_set_error("%s: not on a row-slab handle", who); return EULER_ESTATE; }
+  if (S->slab_on && !S->has_comm) { eu_set_error("%s: row-slab handle without a communicator", who); return EULER_ESTATE; }
   if (!S->loaded) { eu_set_error("%s: no scenario loaded", who); return EULER_ESTATE; }
   if (!S->heat_on) { eu_set_error("%s: heat is off (euler_set_heat)", who); return EULER_ESTATE; }
   return EULER_OK;
 }
 
+// (a row-slab handle moves its own rows, (row_hi - row_lo) X floats, as euler_get_field / euler_set_field do there)
 extern "C" int euler_heat_get_field(euler_sim* S, float* dst, size_t bytes) {
   const char* who = "euler_heat_get_field";
   int rc = heat_field_enter(S, dst, who);
   if (rc) return rc;
-  if (bytes != S->C * sizeof(float)) { eu_set_error("%s: %zu bytes, the field has %zu", who, bytes, S->C * sizeof(float)); return EULER_EINVAL; }
-  HIPCHK(hipMemcpyAsync(dst, heat_t(S), bytes, hipMemcpyDeviceToHost, S->stream));
+  const size_t n = heat_own_n(S);
+  if (bytes != n * sizeof(float)) { eu_set_error("%s: %zu bytes, the field has %zu", who, bytes, n * sizeof(float)); return EULER_EINVAL; }
+  HIPCHK(hipMemcpyAsync(dst, heat_t(S) + heat_own0(S), bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;
 }
 
+// On a row slab COLLECTIVE, as euler_set_field(EULER_F_U) is there: it ends with the exchange of T's ghost rows
 extern "C" int euler_heat_set_field(euler_sim* S, const float* src, size_t bytes) {
   const char* who = "euler_heat_set_field";
   int rc = heat_field_enter(S, src, who);
   if (rc) return rc;
-  if (bytes != S->C * sizeof(float)) { eu_set_error("%s: %zu bytes, the field has %zu", who, bytes, S->C * sizeof(float)); return EULER_EINVAL; }
-  for (size_t i = 0; i < S->C; ++i)
-    if (!eu_heat_value_ok(src[i])) { eu_set_error("%s: cell %zu holds %g (finite and at most 1e4 in size)", who, i, (double)src[i]); return EULER_EINVAL; }
+  const size_t n = heat_own_n(S);
+  if (bytes != n * sizeof(float)) { eu_set_error("%s: %zu bytes, the field has %zu", who, bytes, n * sizeof(float)); rc = EULER_EINVAL; }
+  for (size_t i = 0; i < n && !rc; ++i)
+    if (!eu_heat_value_ok(src[i])) { eu_set_error("%s: cell %zu holds %g (finite and at most 1e4 in size)", who, i, (double)src[i]); rc = EULER_EINVAL; }
+  if (S->slab_on) {      // (one rank's bad value is every rank's refusal: nobody waits in the exchange below for a rank that has left)
+    int worst = 0;
+    const int rs = eu_slab_status_sync(S, rc, &worst);
+    if (rs) return rs;
+    if (!rc && worst) { eu_set_error("%s: another rank refused its values", who); rc = EULER_ESTATE; }
+  }
+  if (rc) return rc;
   // up into the other half, then through the count mask into this one (the copy is waited for: src is the caller's)
-  HIPCHK(hipMemcpyAsync(heat_other(S), src, bytes, hipMemcpyHostToDevice, S->stream));
-  LAUNCH(S, KC_MISC, k_heat_mask, dim3(eu_blocks(S->C, 256)), dim3(256), heat_other(S), heat_t(S), S->count, S->C, S->heat.ambient);
+  HIPCHK(hipMemcpyAsync(heat_other(S) + heat_own0(S), src, bytes, hipMemcpyHostToDevice, S->stream));
+  LAUNCH(S, KC_MISC, k_heat_mask, dim3(eu_blocks(n, 256)), dim3(256), heat_other(S) + heat_own0(S), heat_t(S) + heat_own0(S), S->count + heat_own0(S), n, S->heat.ambient);
   HIPCHK(hipGetLastError());
+  if (S->slab_on && (rc = eu_slab_exchange_heat(S))) return rc;
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;
 }
@@ -340,24 +383,46 @@ extern "C" int euler_heat_fill(euler_sim* S, int32_t x0, int32_t y0, int32_t x1,
   const euler_heat_box b = {x0, y0, x1, y1, value, EULER_HEAT_FIX};      // the boxes' kernel on a one-box list
   unsigned int ntiles = 0;
   if ((rc = eu_box_table_upload(S, who, &S->heat_fill_buf, &b, 1, sizeof(euler_heat_box), EULER_HEAT_BOXES_MAX, &ntiles))) return rc;
-  if ((rc = heat_launch_boxes(S, KC_MISC, &S->heat_fill_buf, ntiles, 0.f))) return rc;      // (outside a substep: the class of k_colorize, not one a cost tool sums)
+  // (outside a substep: the class of k_colorize, not one a cost tool sums.  A row slab: the rank's own entries of the one-box table, nothing where the box lies on
+  // other ranks; then T's ghost rows - every rank refuses alike above, so the call is collective there)
+  if (ntiles && (rc = heat_launch_boxes(S, KC_MISC, &S->heat_fill_buf, ntiles, 0.f))) return rc;
+  if (S->slab_on && (rc = eu_slab_exchange_heat(S))) return rc;
   HIPCHK(hipStreamSynchronize(S->stream));
   return EULER_OK;
 }
 
 extern "C" int euler_heat_raster(euler_sim* S, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t W, int32_t H, euler_heat_px* out, size_t out_bytes) {
   const char* who = "euler_heat_raster";
-  int rc = eu_observe_enter(S, who, "the temperature lives on whole-grid handles", out, x0, y0, x1, y1);
+  int rc = eu_observe_enter(S, who, nullptr, out, x0, y0, x1, y1);      // (collective on a row-slab handle, like every observer pass there)
   if (rc) return rc;
   if (!S->heat_on) { eu_set_error("%s: heat is off (euler_set_heat)", who); return EULER_ESTATE; }
   const int Bw = x1 - x0 + 1, Bh = y1 - y0 + 1;
   if (W < 1 || H < 1 || W > Bw || H > Bh) { eu_set_error("%s: a raster of %d x %d for a box of %d x %d cells", who, W, H, Bw, Bh); return EULER_EINVAL; }
   const size_t n = (size_t)W * (size_t)H;
   if (out_bytes != n * sizeof(euler_heat_px)) { eu_set_error("%s: %zu bytes given, %zu expected", who, out_bytes, n * sizeof(euler_heat_px)); return EULER_EINVAL; }
-  if ((rc = eu_devbuf_reserve(S, who, "the records", &S->heat_ras_buf, out_bytes))) return rc;
+  rc = eu_devbuf_reserve(S, who, "the records", &S->heat_ras_buf, out_bytes);
+  if (S->slab_on) {      // each rank reduces its own rows of the box into its share of the staging area; the shares fold on the device (k_observe_slab.hip): integer sums and
+                         // maxima of bit patterns, so every rank reads the whole-grid bytes.  No row beyond the own ones is read: no exchange
+    eu_slab_plan plan;
+    const int rp = eu_observe_slab_plan(S, &plan, y0, y1, W, H);      // (the same on every rank)
+    if (rp) return rp;
+    if ((rc = eu_observe_slab_open(S, who, rc, (size_t)plan.total * sizeof(euler_heat_px), EU_OBS_ROWS_NONE))) return rc;
+    const int r = S->cfg.slab_rank;
+    if (plan.cnt[r]) {
+      euler_heat_px* mine = (euler_heat_px*)eu_observe_slab_mine(S, &plan, EU_OBS_REC_HEAT);
+      const int Hl = plan.p_hi[r] - plan.p_lo[r] + 1, ya = plan.ya[r], nrows = plan.yb[r] - plan.ya[r] + 1;
+      LAUNCH(S, KC_MISC, k_heat_ras_init, dim3(eu_blocks((size_t)W * Hl, 256)), dim3(256), mine, W, H, Bw, Bh, Hl, plan.p_lo[r], y1, ya, plan.yb[r]);
+      LAUNCH(S, KC_MISC, k_heat_raster, dim3((Bw + 63) / 64, (nrows + 3) / 4), dim3(256), heat_t(S), S->solid, S->sink, S->count, mine, S->X, x0, ya, nrows, y1, Bw, Bh, W, H,
+             plan.p_lo[r], S->heat.ambient);
+      HIPCHK(hipGetLastError());
+    }
+    if ((rc = eu_observe_slab_fold(S, &plan, EU_OBS_REC_HEAT, S->heat_ras_buf.p))) return rc;
+    return eu_observe_readback(S, out, &S->heat_ras_buf, out_bytes);
+  }
+  if (rc) return rc;
   euler_heat_px* rec = (euler_heat_px*)S->heat_ras_buf.p;
-  LAUNCH(S, KC_MISC, k_heat_ras_init, dim3(eu_blocks(n, 256)), dim3(256), rec, W, H, Bw, Bh);
-  LAUNCH(S, KC_MISC, k_heat_raster, dim3((Bw + 63) / 64, (Bh + 3) / 4), dim3(256), heat_t(S), S->solid, S->sink, S->count, rec, S->X, x0, y0, y1, Bw, Bh, W, H, S->heat.ambient);
+  LAUNCH(S, KC_MISC, k_heat_ras_init, dim3(eu_blocks(n, 256)), dim3(256), rec, W, H, Bw, Bh, H, 0, y1, y0, y1);
+  LAUNCH(S, KC_MISC, k_heat_raster, dim3((Bw + 63) / 64, (Bh + 3) / 4), dim3(256), heat_t(S), S->solid, S->sink, S->count, rec, S->X, x0, y0, Bh, y1, Bw, Bh, W, H, 0, S->heat.ambient);
   HIPCHK(hipGetLastError());
   return eu_observe_readback(S, out, &S->heat_ras_buf, out_bytes);
 }

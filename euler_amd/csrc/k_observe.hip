@@ -53,10 +53,12 @@ int eu_observe_readback(euler_sim* S, void* out, const eu_devbuf* b, size_t byte
 // a list of boxes with its tile table (k_boxes.h): built on the host, then up in one copy
 int eu_box_table_upload(euler_sim* S, const char* who, eu_devbuf* buf, const void* boxes, int32_t n, size_t box_bytes, int32_t max_boxes, unsigned int* ntiles) {
   const size_t head = (size_t)max_boxes * box_bytes;      // (1536 bytes for either list: the table stays 8-byte aligned)
-  const size_t nt = eu_force_tiles(boxes, box_bytes, n, S->X, S->Y, nullptr);
+  // (a row-slab handle keeps the entries of its own bands: a tile belongs to one rank.  Its table may be empty - the callers launch nothing then)
+  const int b_lo = S->slab_on ? S->band_lo : 0, b_hi = S->slab_on ? S->band_hi : (S->Y + 63) >> 6;
+  const size_t nt = eu_force_tiles_bands(boxes, box_bytes, n, S->X, S->Y, b_lo, b_hi, nullptr);
   const size_t bytes = head + (nt == (size_t)-1 ? 0 : nt) * sizeof(eu_force_tile);
   char* st = nt == (size_t)-1 ? nullptr : (char*)calloc(1, bytes);
-  if (!st || eu_force_tiles(boxes, box_bytes, n, S->X, S->Y, (eu_force_tile*)(st + head)) != nt) {
+  if (!st || eu_force_tiles_bands(boxes, box_bytes, n, S->X, S->Y, b_lo, b_hi, (eu_force_tile*)(st + head)) != nt) {
     free(st);
     eu_set_error("%s: host memory for the tile table", who);
     return EULER_ENOMEM;

@@ -25,16 +25,18 @@ static const FoldOps fold_ops[EU_OBS_REC__COUNT] = {
   {{A, A, A, A, Q, Q, Q, Q, Q, Q, Q, X, X, X, A}},                   // euler_flow_px: cells water nodes nonfinite | u_pos ... w_neg p_sum | max_speed2 max_abs_w max_p | reserved
   {{Q, Q, Q, Q, Q, Q, Q, Q, Q, X, A, X, X}},                         // euler_diag: cells ... ke_lo | count_max | nonfinite | max_div max_speed2
   {{A, A, N, X, N, X, A, A, Q, Q, Q, Q, X, X}},                      // euler_gauge_rec: cells fluid | lo_x hi_x lo_y hi_y | terms nonfinite | a_pos ... b_neg | max_a max_b
+  {{A, A, Q, Q, X, X}},                                              // euler_heat_px: cells water | t_pos t_neg | max_above max_below
 };
 #undef A
 #undef X
 #undef N
 #undef Q
-static const int fold_words[EU_OBS_REC__COUNT] = {12, 22, 22, 18};
+static const int fold_words[EU_OBS_REC__COUNT] = {12, 22, 22, 18, 8};
 static_assert(sizeof(euler_overview_px) == 48 && sizeof(euler_flow_px) == 88 && sizeof(euler_diag) == 88 && sizeof(euler_gauge_rec) == 72, "the fold tables are written for these records");
 static_assert(offsetof(euler_overview_px, max_speed2) == 20 && offsetof(euler_overview_px, dye) == 24, "euler_overview_px: five counts, a maximum, three 64-bit sums");
 static_assert(offsetof(euler_flow_px, u_pos) == 16 && offsetof(euler_flow_px, max_speed2) == 72 && offsetof(euler_flow_px, reserved) == 84, "euler_flow_px: four counts, seven 64-bit sums, three maxima");
 static_assert(offsetof(euler_diag, count_max) == 72 && offsetof(euler_diag, nonfinite) == 76 && offsetof(euler_diag, max_div) == 80, "euler_diag: nine 64-bit sums, a maximum, a count, two maxima");
+static_assert(sizeof(euler_heat_px) == 32 && offsetof(euler_heat_px, t_pos) == 8 && offsetof(euler_heat_px, max_above) == 24, "euler_heat_px: two counts, two 64-bit sums, two maxima");
 static_assert(offsetof(euler_gauge_rec, lo_x) == 8 && offsetof(euler_gauge_rec, terms) == 24 && offsetof(euler_gauge_rec, a_pos) == 32 && offsetof(euler_gauge_rec, max_a) == 64, "euler_gauge_rec");
 
 size_t eu_observe_rec_bytes(int type) { return (size_t)fold_words[type] * 4; }
@@ -134,6 +136,7 @@ int eu_observe_slab_fold(euler_sim* S, const eu_slab_plan* P, int type, void* ds
   const dim3 grid(eu_blocks((size_t)P->W * (size_t)P->H, 256));
   if (type == EU_OBS_REC_OVERVIEW) LAUNCH(S, KC_MISC, (k_observe_fold<12, 4>), grid, dim3(256), a);
   else if (type == EU_OBS_REC_GAUGE) LAUNCH(S, KC_MISC, (k_observe_fold<18, 2>), grid, dim3(256), a);
+  else if (type == EU_OBS_REC_HEAT) LAUNCH(S, KC_MISC, (k_observe_fold<8, 4>), grid, dim3(256), a);
   else LAUNCH(S, KC_MISC, (k_observe_fold<22, 2>), grid, dim3(256), a);
   HIPCHK(hipGetLastError());
   return EULER_OK;

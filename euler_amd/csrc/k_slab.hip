@@ -200,6 +200,28 @@ int eu_slab_exchange_dye(euler_sim* S) {
   const GhostField f[3] = {{S->dye[0], 4, 1, 1}, {S->dye[1], 4, 1, 1}, {S->dye[2], 4, 1, 1}};
   return exchange_rows(S, f, 3);
 }
+// the temperature (euler_set_heat): one ghost row of T either side - the 3 x 3 of k_heat_extend, k_heat_advect's interpolation (back-trace <= 0.75 cell), the four
+// neighbours of k_heat_diffuse, t[i + X] of k_heat_buoyancy.  Alone where a reader waits for it, else as one more field of a group that travels anyway (heat_rows)
+static inline GhostField heat_rows(const euler_sim* S) { return GhostField{eu_heat_field(S), 4, 1, 1}; }
+int eu_slab_exchange_heat(euler_sim* S) {
+  if (!S->heat_on) return EULER_OK;
+  if (!S->has_comm) { eu_set_error("row-slab handle without a communicator"); return EULER_ESTATE; }
+  const GhostField f[1] = {heat_rows(S)};
+  const int rc = exchange_rows(S, f, 1);
+  if (!rc) S->heat_ghost_stale = 0;
+  return rc;
+}
+// behind the sources: the dye's three channels and T in ONE exchange (either may be off)
+static int exchange_dye_heat(euler_sim* S) {
+  GhostField f[4];
+  int nf = 0;
+  if (S->dye[0]) for (int c = 0; c < 3; ++c) f[nf++] = GhostField{S->dye[c], 4, 1, 1};
+  if (S->heat_on) f[nf++] = heat_rows(S);
+  if (!nf) return EULER_OK;
+  const int rc = exchange_rows(S, f, nf);
+  if (!rc) S->heat_ghost_stale = 0;
+  return rc;
+}
 // The ghost rows an observer pass reads across a row edge (k_observe_slab.hip), in ONE exchange.  u, v and the count grid are current there at every point where the
 // own rows are, except the count grid between the refresh and the sources stage; the sink grid's are stale behind a local euler_set_field(EULER_F_SINK).  Writing the
 // neighbours' current rows over them leaves no trace in the run: no stage reads the sink grid outside the own rows (k_bin_markers_slab), and the next reader of the
@@ -222,9 +244,14 @@ int eu_slab_exchange_observed(euler_sim* S, int rows) {
     default: return EULER_OK;
   }
 }
+// (... and T's ghost rows where the velocity stage left them stale: kappa == 0 and beta == 0, no reader inside the stage asked for them)
 static int exchange_vtmp(euler_sim* S) {
-  const GhostField f[1] = {{S->vtmp, 4, 1, 0}};
-  return exchange_rows(S, f, 1);
+  GhostField f[2] = {{S->vtmp, 4, 1, 0}};
+  const bool heat = S->heat_on && S->heat_ghost_stale;
+  if (heat) f[1] = heat_rows(S);
+  const int rc = exchange_rows(S, f, heat ? 2 : 1);
+  if (!rc && heat) S->heat_ghost_stale = 0;
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------ timestep
@@ -274,6 +301,28 @@ int eu_slab_same_everywhere(euler_sim* S, const double* vals, int n, int* same) 
   HIPCHK(hipMemcpyAsync(v, s->vec, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   for (int k = 0; k < n; ++k) if (v[2 * k] != -v[2 * k + 1]) *same = 0;
+  return EULER_OK;
+}
+// collective: euler_set_forcing / euler_set_heat on a slab handle, behind each rank's own check of its arguments (local_rc: its result, the reason already set) and in
+// front of any change.  The ranks compare their status and the digest of record and list (euler_host.c) in ONE all-reduce; EULER_OK only when every rank passed its
+// check with the same bytes.  A rank that failed its own check keeps its code and reason; the others get EULER_ESTATE - so nobody switches on what a neighbour lacks
+int eu_slab_agree(euler_sim* S, const char* who, int local_rc, unsigned long long digest) {
+  const double vals[3] = {local_rc ? 1.0 : 0.0, local_rc ? 0.0 : (double)(digest >> 32), local_rc ? 0.0 : (double)(digest & 0xffffffffull)};
+  int same = 1;
+  const int rc = eu_slab_same_everywhere(S, vals, 3, &same);
+  if (rc) return rc;
+  if (local_rc) return local_rc;
+  if (!same) { eu_set_error("%s: the record or the box list differs between ranks, or another rank refused its own (a row-slab job sets the same on every rank)", who); return EULER_ESTATE; }
+  return EULER_OK;
+}
+// collective: behind the reservations and uploads that follow the agreement - they can fail on one rank alone (EULER_ENOMEM).  That rank keeps its code and reason,
+// the others get EULER_ENOMEM: no rank switches on what a neighbour could not allocate, and nobody waits in an exchange the other never enters (eu_observe_slab_open)
+int eu_slab_all_ok(euler_sim* S, const char* who, int local_rc) {
+  int worst = local_rc;
+  const int rs = eu_slab_status_sync(S, local_rc, &worst);
+  if (rs) return rs;
+  if (local_rc) return local_rc;
+  if (worst) { eu_set_error("%s: another rank could not reserve its device buffers", who); return EULER_ENOMEM; }
   return EULER_OK;
 }
 int eu_slab_timestep(euler_sim* S, float frame_time_left) {   // k_maxsq over the own rows has been launched
@@ -635,7 +684,11 @@ int eu_slab_substep(euler_sim* S, float dt) {
   if ((rc = slab_sources(S))) return rc;
   if ((rc = eu_launch_dye_sources(S))) return rc;
   if ((rc = exchange_counts(S))) return rc;
-  if ((rc = eu_slab_exchange_dye(S))) return rc;
+  // the temperature's extension and source cells (k_heat.hip): its 3 x 3 reads prev_count and T across the row edges.  prev_count's ghost rows are current behind the
+  // exchange above - the sources add to count only, and of count the pass reads the own rows -, so the count grids travel no extra time for it; T's are current by the
+  // invariant.  What it writes travels with the dye's channels
+  if (S->heat_on && (rc = eu_launch_heat_sources(S))) return rc;
+  if ((rc = exchange_dye_heat(S))) return rc;
   // extrapolate, zero_bounds (main.c:865-868): u, v of the own rows; then their ghost rows
   if ((rc = eu_launch_extrapolate(S))) return rc;
   if ((rc = exchange_uv(S))) return rc;
@@ -670,7 +723,11 @@ int eu_slab_stage(euler_sim* S, int stage, float dt) {
       const unsigned long long n_upper = S->n_markers_host + 2 * s->mig_cap;
       return slab_refresh(S, n_upper < S->max_markers ? n_upper : S->max_markers);
     }
-    case EULER_STAGE_SOURCES: if ((rc = slab_sources(S))) return rc; return exchange_counts(S);
+    case EULER_STAGE_SOURCES:      // (with the temperature's extension behind the count grids' exchange and T's ghost rows behind it, as in eu_slab_substep)
+      if ((rc = slab_sources(S))) return rc;
+      if ((rc = exchange_counts(S))) return rc;
+      if (S->heat_on && (rc = eu_launch_heat_sources(S))) return rc;
+      return eu_slab_exchange_heat(S);
     case EULER_STAGE_EXTRAPOLATE: if ((rc = eu_launch_extrapolate(S))) return rc; return exchange_uv(S);
     case EULER_STAGE_ADVECT_VELOCITY:
       if ((rc = eu_launch_advect_velocity(S, dt))) return rc;

@@ -606,12 +606,17 @@ typedef struct euler_forcing {     /* 48 bytes, no padding */
   double  reserved2;               /* must be 0 */
 } euler_forcing;
 int euler_forcing_default(euler_forcing* f);
-/* Refusals, in this order: a null sim or f (EULER_EINVAL); a row-slab handle (EULER_ESTATE: a slab keeps the reference's gravity); nothing loaded
+/* Refusals, in this order: a null sim or f (EULER_EINVAL); a row-slab handle without a communicator (EULER_ESTATE, "slab" in the text); nothing loaded
  * (EULER_ESTATE); reserved or reserved2 not 0; a non-finite value or |gx|, |gy|, |shake_x|, |shake_y| > 1e4; shake_hz < 0 or non-finite, a non-finite
  * phase; nboxes outside [0, EULER_FORCE_BOXES_MAX] or boxes == NULL with nboxes > 0; a box's fx or fy non-finite or beyond 1e4 in size (a value comes in
  * front of any box's place); a box outside the interior or with x0 > x1 / y0 > y1, naming the index of the first such box (all EULER_EINVAL).  A refused call changes and allocates nothing.  May be called between any two calls - frames,
  * substeps, stages; touches no grid.  The boxes and their tile table go to a device buffer of the handle once per call (grown on demand, counted in
- * euler_hbm_bytes, released by euler_destroy). */
+ * euler_hbm_bytes, released by euler_destroy).  On a row-slab handle with a communicator the call is COLLECTIVE (docs/forcing.md "On row slabs"): behind its own
+ * checks every rank compares a digest of the record and the list with the others; if any rank refused its own or the digests differ, every rank returns an error
+ * and nothing has changed.  The codes are NOT the same on every rank: the rank whose own record was refused returns its EULER_EINVAL with its reason, every other rank
+ * EULER_ESTATE with "differs between ranks" in the text - a job tests for != EULER_OK.  Last refusal there, behind the agreement: a buffer that one rank could not
+ * reserve is EULER_ENOMEM on every rank, and every rank is left without boxes.  A rank keeps the table entries of its own bands.  The
+ * uniform part is formed from the rank's own clock: euler_set_time is local, the caller keeps the ranks' clocks equal. */
 int euler_set_forcing(euler_sim* sim, const euler_forcing* f, const euler_force_box* boxes);   /* boxes may be NULL when nboxes == 0 */
 int euler_get_forcing(euler_sim* sim, euler_forcing* f, euler_force_box* boxes, int32_t cap);  /* boxes may be NULL (the record alone); else cap >= nboxes */
 int euler_forcing_at(const euler_forcing* f, double t, float a[2]);   /* host only, no GPU */
@@ -656,13 +661,16 @@ int euler_heat_default(euler_heat* h);
 /* h == NULL switches heat off: the handle launches what it launched before and keeps its buffers; the next switching-on starts from `ambient` everywhere.
  * The first call with a record reserves the arrays (device buffers of the handle, counted in euler_hbm_bytes, grow-only, released by euler_destroy) and sets
  * every cell to `ambient`; a later one replaces beta, kappa, source_t and the boxes and keeps the field.  Refusals, in this order: a null sim
- * (EULER_EINVAL); a row-slab handle (EULER_ESTATE); nothing loaded (EULER_ESTATE); then EULER_EINVAL for: reserved or reserved2 not 0; a non-finite value or
+ * (EULER_EINVAL); a row-slab handle without a communicator (EULER_ESTATE, "slab"); nothing loaded (EULER_ESTATE); then EULER_EINVAL for: reserved or reserved2 not 0; a non-finite value or
  * |ambient|, |beta|, |source_t| > 1e4; kappa outside [0, 2.5]; another ambient than the live one (the dry cells hold it); nboxes outside
  * [0, EULER_HEAT_BOXES_MAX] or boxes == NULL with nboxes > 0; a box with an unknown kind, a non-finite value or |value| > 1e4, outside the interior or
- * inverted, naming the first such box.  A refused call changes and allocates nothing. */
+ * inverted, naming the first such box.  A refused call changes and allocates nothing.  On a row-slab handle with a communicator the call is COLLECTIVE, h == NULL
+ * included, with the agreement of euler_set_forcing behind its own checks and its codes - the refusing rank its own EULER_EINVAL, the others EULER_ESTATE; a failed
+ * reservation on one rank EULER_ENOMEM on all, heat on or off as it was and without boxes (docs/heat.md "On row slabs"); the field is the rank's window, two halves of it. */
 int euler_set_heat(euler_sim* sim, const euler_heat* h, const euler_heat_box* boxes);
 int euler_get_heat(euler_sim* sim, euler_heat* h, euler_heat_box* boxes, int32_t cap);   /* EULER_ESTATE while heat is off; boxes may be NULL, else cap >= nboxes */
-/* The field, X * Y floats, row-major.  Refused: a null argument (EULER_EINVAL), a row-slab handle, nothing loaded or heat off (EULER_ESTATE), another byte
+/* The field, X * Y floats, row-major; on a row-slab handle the rank's own rows, (row_hi - row_lo) * X floats, and euler_heat_set_field / euler_heat_fill are COLLECTIVE
+ * there (they end with the exchange of T's ghost rows).  Refused: a null argument (EULER_EINVAL), a row-slab handle without a communicator, nothing loaded or heat off (EULER_ESTATE), another byte
  * count, a box outside the interior or inverted, a value that is not finite or beyond 1e4 in size (EULER_EINVAL).  euler_heat_set_field writes `ambient`
  * over what the caller gave for cells without markers; euler_heat_fill sets T = value in the cells of the box that hold markers, now. */
 int euler_heat_get_field(euler_sim* sim, float* dst, size_t bytes);
@@ -672,7 +680,8 @@ int euler_heat_fill(euler_sim* sim, int32_t x0, int32_t y0, int32_t x1, int32_t 
  * euler_overview_box's.  d = T - ambient of a water cell goes to the sum of its sign - t_pos += qv(d) for d >= 0 (-0.f too), t_neg += qv(-d) for d < 0,
  * qv the flow raster's: min(a, 4096) * 2^20, truncated - and to the maximum of its side, taken on bit patterns; a NaN goes to neither (the cell still counts
  * as water), an infinity is the clamp's 4096 in the sums and itself in the maxima.  Integer sums and bit-pattern maxima: the record does not depend on the
- * launch geometry.  Refusals: a null argument (EULER_EINVAL), a row-slab handle, nothing loaded or heat off (EULER_ESTATE), a box outside the interior, W or
+ * launch geometry.  On a row-slab handle COLLECTIVE like euler_overview_box: every rank reads the whole-grid bytes.  Refusals: a null argument (EULER_EINVAL), a row-slab
+ * handle without a communicator, nothing loaded or heat off (EULER_ESTATE), a box outside the interior, W or
  * H < 1 or above the box's extent, another byte count than W * H records (EULER_EINVAL).  Reads the state only. */
 typedef struct euler_heat_px {       /* 32 bytes */
   uint32_t cells;                    /* cells of the pixel */
